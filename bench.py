@@ -5,7 +5,13 @@ step-4i shuffle) on synthetic inputs already resident in HBM.  Defa
 B = 65536, l = 32, 2048-bit Paillier + 2048-bit DGK on one GPU.  With N > 1 ranks each rank runs its own shard of B
 comparisons (weak scaling, no data-path collective) and the [[x<=y]] results are all-gathered over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--l 32] [--pbits 2048]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--l 32] [--pbits 2048] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, ms_per_step, ...).  `--full`
+adds everything else the line can carry: the diagnostics before and after the timed loop, the decrypt and CPU-oracle checks of the
+results, the roofline figures, the CPU baseline, the informational legs and the sub-lines of the other BASELINE shapes
+(`--no-cpu-baseline`, `--no-extras`, `--no-other-configs` leave parts of that out again).  `--dump-outputs DIR` writes what the
+last timed step returned to its caller as DIR/*.npy (see dump_outputs).
 
 `--gpus N` with N > 1 and no launcher environment starts N rank processes itself (protocols.secure_comparison_amd.launcher:
 the parent never touches the GPU); under `python -m torch.distributed.run --nproc-per-node N` the launcher's WORLD_SIZE must
@@ -35,6 +41,8 @@ DEFAULT_FB_WINDOW = 20  # fixed-base window of the tables for h: 6.2 GB per GPU 
                         # A/B -- less than the four saved products of 71 would give; presumably row fetches that miss the address translation caches -- and the configs[1] sub-line beside the
                         # 82 GB drops from 114 k to 94 k/s (profiles/r04_fixed_base_window_24.txt): not the default
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_BYTES = 32 << 20  # --dump-outputs: at most this many bytes of result words; a larger result is sampled by rows
+DUMP_SEED = 2026       # the row sample of --dump-outputs (fixed: two builds write the same rows)
 
 
 def literal_macs_per_comparison(l: int, pbits: int, dbits: int, rbits: int) -> float:
@@ -182,6 +190,22 @@ def export_sample(path, eng, idx, l, x_enc, y_enc, draws, result):
            "rho_zeta_2": rows(draws.rho_zeta_2), "rho_delta_b": rows(draws.rho_delta_b), "gpu_result": rows(result)}
     with open(path, "w") as f:
         json.dump(doc, f)
+
+
+def dump_outputs(out_dir: str, res) -> dict:
+    """--dump-outputs: the result array the timed path returned in its last step (rows = comparisons of all ranks, columns = the
+    32-bit words of each [[x <= y]] Paillier ciphertext, least significant first) as float64 -- exact for 32-bit words -- in
+    DIR/result_words.npy.  A result larger than DUMP_BYTES keeps a fixed, seeded, ascending sample of its rows.  Inputs and draws
+    are seeded, so two builds that compute the same thing write the same file."""
+    import numpy as np
+
+    rows, cols = res.shape
+    keep = min(rows, max(1, DUMP_BYTES // (8 * cols)))
+    idx = np.arange(rows) if keep == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+    words = res.cpu().numpy().view(np.uint32)[idx].astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "result_words.npy"), words)
+    return {"dir": out_dir, "arrays": {"result_words": list(words.shape)}, "rows_of": rows}
 
 
 def policy_of(eng) -> dict:
@@ -586,19 +610,26 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=0, help="concurrent shards per GPU (one library context, HIP stream and host thread each); 1 = a single stream; "
                     "0 = automatic: 2 once every shard's widest launches still fill the chip (128 comparisons of 2048-bit keys per CU and shard, scaled by the square of the key size)")
     ap.add_argument("--side-stream", type=int, default=-1, help="run the randomizer exponentiations of a step on a second library context and stream per shard, "
-                    "concurrently with the protocol's critical path (batch._AheadOfTime): 1 on, 0 off, -1 automatic (on while the batch leaves most wave slots empty: up to 32 comparisons per CU; measured +15 % at 4096, -2 % at 16384 on 256 CUs)")
+                    "concurrently with the protocol's critical path (batch._AheadOfTime): 1 on, 0 off, -1 automatic (on while the batch leaves most wave slots empty: up to 32 comparisons per CU; measured +15 %% at 4096, -2 %% at 16384 on 256 CUs)")
     ap.add_argument("--side-fork", type=int, default=1, help="fork mode (sc_ctx_set_fork_mode) of the second contexts: 0 = the halves of the key holder's CRT in sequence, 1 = automatic (the q-side on a second stream of that context for small batches, and for large ones when the context has the chip to itself), 2 = always side by side")
     ap.add_argument("--fork-mode", type=int, default=1, help="fork mode of the shard contexts (sc_ctx_set_fork_mode): 0 never, 1 automatic (small batches), 2 always")
     ap.add_argument("--latency-mode", type=int, default=1, help="small-batch kernel policy (sc_ctx_set_latency_mode): 0 never, 1 automatic, 2 always")
     ap.add_argument("--onelane-mode", type=int, default=1, help="large-batch kernel policy for the 1024-bit primes (sc_ctx_set_onelane_mode): 0 never, 1 automatic, 2 always")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline: diagnostics before and after the timed loop, "
+                    "decrypt and CPU-oracle checks, roofline figures, CPU baseline, informational legs, sub-lines of the other BASELINE shapes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step returned to its caller "
+                    "(the result ciphertexts as float64 32-bit words; a fixed, seeded sample of rows beyond %d MB) as DIR/<name>.npy" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle rows of the sub-lines")
     ap.add_argument("--cpu-sample", type=int, default=0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational legs (window sensitivity, online phase, PCIe-inclusive)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the compact sub-lines of BASELINE configs[1] and the configs[4] per-GPU share")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the informational legs (window sensitivity, online phase, PCIe-inclusive)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the compact sub-lines of BASELINE configs[1] and the configs[4] per-GPU share")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even for one rank (exercises the RCCL path)")
     ap.add_argument("--c-abi-gather", action="store_true", help="after the timed region, repeat the reassembly through the C ABI's own RCCL communicator "
                     "(sc_comm_init / sc_allgather) and report whether it equals torch.distributed's gather")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class GpuRuntime:
@@ -703,7 +734,7 @@ def main(argv=None, runtime=None, script: str | None = None) -> None:
         # a rank that never arrives must not hang the others for torch's default half hour
         dist.init_process_group(rt.backend, rank=rank, world_size=world, device_id=rt.dist_device(local_rank),
                                 timeout=datetime.timedelta(seconds=int(os.environ.get("SC_AMD_RENDEZVOUS_TIMEOUT_S", launcher.RENDEZVOUS_TIMEOUT_S))))
-    line = measure(args, torch, dist, rank, world, full=True, rt=rt)
+    line = measure(args, torch, dist, rank, world, headline=True, rt=rt)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:
@@ -711,10 +742,10 @@ def main(argv=None, runtime=None, script: str | None = None) -> None:
         dist.destroy_process_group()
 
 
-def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
-    """One configuration: set-up, warm-up, the timed steps, and (rank 0) the line's content.  full: the headline run with every
-    diagnostic and informational leg; otherwise a compact sub-line (value, ms per step, whole-step fraction) of another BASELINE shape
-    measured by the same code path."""
+def measure(args, torch, dist, rank: int, world: int, headline: bool, rt=None):
+    """One configuration: set-up, warm-up, the timed steps, and (rank 0) the line's content.  headline: the run the line is about --
+    with --full, every diagnostic, check and informational leg as well; otherwise (--full only) a compact sub-line (value, ms per
+    step, whole-step fraction) of another BASELINE shape measured by the same code path."""
     from protocols.secure_comparison_amd import DGK, Paillier, launcher
     from protocols.secure_comparison_amd.batch import (BatchDraws, ConcurrentShards, PartySet, boot_pools, secure_comparison_batch,
                                                        split_draws)
@@ -730,7 +761,7 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
     p, q = int(pj["p"], 16), int(pj["q"], 16)
     H = lambda name: int(dj[name], 16)  # noqa: E731
     use_crt = not args.no_crt
-    eng = rt.default_engine() if full else rt.new_engine()
+    eng = rt.default_engine() if headline else rt.new_engine()
     cus = rt.cu_count(eng)
     # Two concurrent shards pay once each shard's widest launches still fill the chip by themselves: a pair launch holds 16 items per
     # wave and 8 waves per CU, so 128 comparisons of 2048-bit keys per CU and shard (256 CUs: from 32768 comparisons per GPU, +1.4 %
@@ -874,8 +905,9 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
 
     # ---- diagnostics BEFORE anything else has loaded the chip (rank 0 of the headline run): the dominant launch, the probe and the
     # in-kernel clock -- repeated after the timed loop, so that the line itself says whether the chip's clock state moved
+    diag = headline and args.full
     diag_before = None
-    if full:       # every rank: with N GPUs the slowest one sets a weak-scaling step, and the line must be able to say which it was
+    if diag:       # every rank: with N GPUs the slowest one sets a weak-scaling step, and the line must be able to say which it was
         ls_, _, pk_ = dominant_launch(reps=2)
         diag_before = {"launch_ms": ls_ * 1e3, "probe_peak": pk_ / 1e12, "clock_ghz": clock_ghz()}
 
@@ -883,14 +915,14 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
     for _ in range(args.warmup):
         res = gather(step())
     rt.synchronize()
-    # parity spot check outside the timed region: decrypt the results on the GPU and compare with x <= y
+    # parity spot check outside the timed region (--full): decrypt the results on the GPU and compare with x <= y
     expect = (x <= y).to(torch.int32)
 
     def all_correct(full):
         dec = bob_p.decrypt_raw_batch((full[rank * B:(rank + 1) * B] if world > 1 else full).contiguous())
         return bool(((dec[:, 0] == expect) & (dec[:, 1:] == 0).all(dim=1)).all().item())
 
-    if res is not None and not all_correct(res):
+    if args.full and res is not None and not all_correct(res):
         raise SystemExit("bench.py: decrypted results differ from x <= y")
     rccl_ranks, devices = 1, [rt.current_device()]
     if dist is not None:   # prove the collective sees every rank, and where the ranks sit
@@ -908,12 +940,13 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
     executed_macs = sum(e_.mac_counter() for e_ in engines + side_engines)
     value = world * B * args.steps / elapsed
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(len(marks) - 1))
-    if not all_correct(res):
+    dumped = dump_outputs(args.dump_outputs, res) if headline and rank == 0 and args.dump_outputs else None
+    if args.full and not all_correct(res):
         raise SystemExit("bench.py: decrypted results of the timed steps differ from x <= y")
     # ---- per-rank view (outside the timed region): this rank's step WITHOUT the collective (what its GPU does alone), its dominant
     # launch, probe and clock before / after -- gathered into rank 0's line with one small all-gather
     per_rank, weak_eff = None, None
-    if full:
+    if diag:
         solo_marks = [rt.event() for _ in range(3)]
         solo_marks[0].record()
         for i_ in range(2):
@@ -941,7 +974,7 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
         weak_eff = value / (world * B / (slowest * 1e-3))
     close_step()      # the single-stream measurements below run with the policies of a context that has the chip to itself
     nominal_peak = cus * 64 * MAX_CLOCK_HZ   # 4 SIMDs x 16 lanes per CU, one multiply-add per lane and cycle
-    if not full:      # a compact sub-line of another BASELINE shape
+    if not headline:      # a compact sub-line of another BASELINE shape
         sub = None
         if rank == 0:
             sub = {"workload": workload_name(B, l, args.pbits, dbits), "value": value, "unit": "comparisons/s", "ms_per_step": elapsed / args.steps * 1e3,
@@ -979,6 +1012,28 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
         except Exception as exc:  # pragma: no cover
             c_abi_gather = {"error": str(exc)[:200]}
 
+    # ---- the line of a plain run: the headline and what the set-up already knows; everything below it is --full
+    line = {
+        "metric": "secure comparisons/sec (l=%d, %d-bit keys)" % (l, args.pbits), "value": value, "unit": "comparisons/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64 (29-bit limbs held in u32, 32x32+64->64 multiply-accumulate)",
+        "data": "synthetic", "rccl_ranks": rccl_ranks, "rank_devices": devices, "c_abi_gather": c_abi_gather,
+        **({"rehearsal": rt.rehearsal} if getattr(rt, "rehearsal", None) else {}),
+        "step_ms": {"min": step_ms[0], "median": step_ms[len(step_ms) // 2], "max": step_ms[-1],
+                    "note": "per-step device time between events on the caller's stream inside the timed region (no synchronisation added)"},
+        "config": {"workload": workload_name(B, l, args.pbits, dbits),
+                   "batch_per_gpu": B, "l": l, "paillier_bits": args.pbits, "dgk_bits": dbits, "dgk_key": dname, "dgk_randomizer_bits": args.rbits,
+                   "fixed_base_window": args.fb_window, "fixed_base_window_requested": requested_window, "fixed_base_window_note": window_note,
+                   "keyholder_crt": use_crt, "shuffle_4i": not args.no_shuffle,
+                   "parallelism": "shard%d" % world, "streams_per_gpu": ns, "randomizers_on_side_stream": use_side,
+                   "fixed_base_table_bytes": table_bytes, "table_build_s": table_build_s,
+                   "table_note": "device bytes of Alice's table for h mod n plus the key holder's CRT tables for h mod p, h mod q, built once per GPU "
+                                 "(untimed set-up, SURVEY 8(d)) and shared read-only by the %d shard context(s)" % ns},
+        **({"outputs": dumped} if dumped else {}),
+    }
+    if not args.full:
+        return line if rank == 0 else None
+
     out = None
     if rank == 0:
         # ---- roofline of the dominant kernel: Alice's Paillier randomizer rho^N mod N^2 (k_pvm<4,18> + assembly launch),
@@ -1008,27 +1063,13 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
                 traffic = json.load(open(tpath)).get("hbm_bytes_per_launch")
                 break
         out = {
-            "metric": "secure comparisons/sec (l=%d, %d-bit keys)" % (l, args.pbits), "value": value, "unit": "comparisons/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64 (29-bit limbs held in u32, 32x32+64->64 multiply-accumulate)",
-            "data": "synthetic", "rccl_ranks": rccl_ranks, "rank_devices": devices, "c_abi_gather": c_abi_gather,
-            **({"rehearsal": rt.rehearsal} if getattr(rt, "rehearsal", None) else {}),
-            "step_ms": {"min": step_ms[0], "median": step_ms[len(step_ms) // 2], "max": step_ms[-1],
-                        "note": "per-step device time between events on the caller's stream inside the timed region (no synchronisation added)"},
+            **line,
             "per_rank": per_rank,
             "weak_scaling_efficiency": weak_eff,
             "per_rank_note": "one row per rank, gathered outside the timed region: its steps inside the timed loop (median / min / max, collective included), "
                              "its step WITHOUT the collective (solo_step_ms, best of two), its dominant launch, in-kernel clock and multiply-add probe before the "
                              "warm-up and after the loop, its table; weak_scaling_efficiency = value / (N x B / slowest rank's solo step): what the collective "
                              "and the slowest GPU cost together",
-            "config": {"workload": workload_name(B, l, args.pbits, dbits),
-                       "batch_per_gpu": B, "l": l, "paillier_bits": args.pbits, "dgk_bits": dbits, "dgk_key": dname, "dgk_randomizer_bits": args.rbits,
-                       "fixed_base_window": args.fb_window, "fixed_base_window_requested": requested_window, "fixed_base_window_note": window_note,
-                       "keyholder_crt": use_crt, "shuffle_4i": not args.no_shuffle,
-                       "parallelism": "shard%d" % world, "streams_per_gpu": ns, "randomizers_on_side_stream": use_side,
-                       "fixed_base_table_bytes": table_bytes, "table_build_s": table_build_s,
-                       "table_note": "device bytes of Alice's table for h mod n plus the key holder's CRT tables for h mod p, h mod q, built once per GPU "
-                                     "(untimed set-up, SURVEY 8(d)) and shared read-only by the %d shard context(s)" % ns},
             "roofline": {"bound": "valu-int",
                          "bound_note": "v_mad_u64_u32 issue rate; neither HBM nor MFMA bounds this path (SURVEY 8(d)); the HBM view is in roofline_hbm",
                          "kernel": "k_pvm<4,18>: Paillier randomizer rho^N mod N^2 for B items, pair arithmetic modulo N (one launch) "
@@ -1211,7 +1252,7 @@ def measure(args, torch, dist, rank: int, world: int, full: bool, rt=None):
                 a2.streams, a2.side_stream = 0, -1
                 a2.fb_window = min(args.fb_window, 20)      # other keys: their own tables beside the headline's 82 GB
                 try:
-                    others.append(measure(a2, torch, None, 0, 1, full=False, rt=rt))
+                    others.append(measure(a2, torch, None, 0, 1, headline=False, rt=rt))
                 except Exception as exc:  # pragma: no cover
                     others.append({"workload": workload_name(kw["batch"], kw["l"], kw["pbits"], None), "error": str(exc)[:200]})
             out["other_configs"] = others

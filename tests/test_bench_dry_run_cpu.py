@@ -11,7 +11,7 @@ from conftest import ROOT
 
 DRY = os.path.join(ROOT, "tests", "_bench_dry_run.py")
 ARGS = ["--batch", "3", "--l", "16", "--pbits", "1024", "--dgk", "dgk_tiny_l16", "--rbits", "50", "--fb-window", "4", "--steps", "2", "--warmup", "1",
-        "--no-cpu-baseline", "--no-extras", "--no-other-configs"]
+        "--full", "--no-cpu-baseline", "--no-extras", "--no-other-configs"]
 
 
 def _clean_env():
@@ -87,3 +87,46 @@ def test_two_ranks_under_a_launcher_environment():
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cp = subprocess.run([sys.executable, DRY, "--gpus", "2"] + ARGS, env=env, capture_output=True, text=True, timeout=300)
     assert cp.returncode != 0 and "WORLD_SIZE" in cp.stderr and "{" not in cp.stdout
+
+
+def test_a_plain_run_is_lean_and_dumps_what_the_last_step_returned(tmp_path, keys):
+    """Without --full the line holds the headline and the configuration only.  --dump-outputs writes the result ciphertexts of the
+    last timed step as float64 32-bit words: the same in two runs with the same arguments, real ciphertexts of 0 or 1, and with two
+    ranks one row per comparison of every rank (rank 0's first)."""
+    import numpy as np
+
+    from conftest import oracle_paillier
+
+    plain = [a for a in ARGS if a not in ("--full", "--no-cpu-baseline", "--no-extras", "--no-other-configs")]
+    lines = {}
+    for run, gpus in (("a", "1"), ("b", "1"), ("two", "2")):
+        cp = subprocess.run([sys.executable, DRY, "--gpus", gpus] + plain + ["--dump-outputs", str(tmp_path / run)], env=_clean_env(),
+                            capture_output=True, text=True, timeout=600)
+        assert cp.returncode == 0, cp.stderr[-2000:]
+        lines[run] = _line(cp.stdout)
+    d = lines["a"]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["steps"] == 2
+    assert abs(d["value"] - 3 * 2 / (d["ms_per_step"] * 2 / 1e3)) < 1e-6 * d["value"]
+    assert not {"per_rank", "roofline", "roofline_whole_step", "policy", "cpu_baseline", "interactive_protocol", "other_configs"} & set(d)
+    a, b, two = (np.load(tmp_path / run / "result_words.npy") for run in ("a", "b", "two"))
+    assert a.dtype == np.float64 and a.shape == (3, 64) and (a == b).all()
+    assert two.shape == (6, 64) and (two[:3] == a).all() and lines["two"]["outputs"]["rows_of"] == 6
+    osk = oracle_paillier(keys, 1024)
+    assert {osk.dec_raw(sum(int(w) << (32 * i) for i, w in enumerate(row))) for row in two} <= {0, 1}
+
+
+def test_dumped_outputs_of_a_large_result_are_a_fixed_sample_of_rows(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1000 * 4 * 8)
+    res = torch.arange(4096 * 4, dtype=torch.int32).reshape(4096, 4) - 7          # the first words are negative: read as u32
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), res)
+    a, b = np.load(tmp_path / "a" / "result_words.npy"), np.load(tmp_path / "b" / "result_words.npy")
+    assert a.shape == (1000, 4) and (a == b).all()
+    rows = ((a[:, 0].astype(np.int64) + 7) % (1 << 32)) // 4
+    assert (np.diff(rows) > 0).all()
+    assert (a == (res[torch.from_numpy(rows)].to(torch.int64) & 0xFFFFFFFF).numpy()).all()

@@ -167,7 +167,7 @@ def test_bench_rank_handling_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     bench = os.path.join(ROOT, "bench.py")
     cp = subprocess.run([sys.executable, bench, "--gpus", "1", "--force-dist", "--c-abi-gather", "--batch", "512", "--l", "16", "--dgk", "dgk_2048_l16", "--fb-window", "8",
-                         "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
+                         "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
     assert cp.returncode == 0, cp.stderr[-2000:]
     line = json.loads(cp.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["rank_devices"] == [0] and line["value"] > 0

@@ -180,7 +180,7 @@ def test_two_ranks_rehearse_the_multi_gpu_bench_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["SC_BENCH_SHARE_GPU"] = "1"
     cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "1024", "--l", "16", "--dgk", "dgk_2048_l16", "--fb-window", "8",
-                         "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
+                         "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True, timeout=900)
     assert cp.returncode == 0, cp.stderr[-3000:]
     line = json.loads([ln for ln in cp.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["rank_devices"] == [0, 0] and "rehearsal" in line

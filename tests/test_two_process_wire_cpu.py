@@ -87,6 +87,13 @@ def test_two_processes_bytes_only(keys):
     assert child.exitcode == 0
 
 
+def _socket_in(tmp_path, monkeypatch) -> str:
+    """A Unix socket path for the two processes, relative to tmp_path, which becomes the working directory of this process and of the
+    child it spawns: sun_path holds 107 bytes, and the absolute path of a deep temporary directory can be longer than that."""
+    monkeypatch.chdir(tmp_path)
+    return "sc.sock"
+
+
 def _keyholder_over_a_socket(path, root, batches):
     sys.path.insert(0, root)
     sys.path.insert(0, os.path.join(root, "tests"))
@@ -111,14 +118,14 @@ def _keyholder_over_a_socket(path, root, batches):
     asyncio.run(serve())
 
 
-def test_two_processes_over_a_socket(keys, tmp_path):
+def test_two_processes_over_a_socket(keys, tmp_path, monkeypatch):
     """The same exchange over communicator.StreamCommunicator (a Unix socket driven by the event loop): the transport the GPU-box tool
     tools/gpu_two_process.py uses.  Chunked sub-sessions interleave their frames on the one connection."""
     from _oracle_engine import OracleEngine
     from protocols.secure_comparison_amd import Initiator, StreamCommunicator
 
     osk, od = oracle_paillier(keys, 1024), oracle_dgk(keys, "dgk_tiny_l16")
-    path = str(tmp_path / "sc.sock")
+    path = _socket_in(tmp_path, monkeypatch)
     ctx = mp.get_context("spawn")
     child = ctx.Process(target=_keyholder_over_a_socket, args=(path, ROOT, 2), daemon=True)
     child.start()
@@ -219,7 +226,7 @@ def _keyholder_sessions_over_a_socket(path, root, sessions, rounds):
     asyncio.run(serve())
 
 
-def test_concurrent_single_comparisons_between_two_processes(keys, tmp_path):
+def test_concurrent_single_comparisons_between_two_processes(keys, tmp_path, monkeypatch):
     """The reference's call shape between two processes: N concurrent `perform_secure_comparison` sessions on one Initiator here and
     one KeyHolder in a child process, over communicator.StreamCommunicator -- the scheme pair as its public document, every
     ciphertext message in wire.pack_session_message's form, each process coalescing its own sessions' steps.  Plaintext and
@@ -228,7 +235,7 @@ def test_concurrent_single_comparisons_between_two_processes(keys, tmp_path):
     from protocols.secure_comparison_amd import Initiator, Paillier, PaillierCiphertext, StreamCommunicator
 
     osk = oracle_paillier(keys, 1024)
-    path = str(tmp_path / "sc.sock")
+    path = _socket_in(tmp_path, monkeypatch)
     sessions, rounds = 12, 2
     ctx = mp.get_context("spawn")
     child = ctx.Process(target=_keyholder_sessions_over_a_socket, args=(path, ROOT, sessions, rounds), daemon=True)

@@ -16,15 +16,15 @@ PY
 }
 for rep in 1 2; do
   for hold in 0 13 7 5; do
-    SC_PAIR_HOLD_MS=$hold python bench.py --steps 10 --warmup 2 --no-extras --no-other-configs --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || tail -3 /tmp/ab.err >> $out
+    SC_PAIR_HOLD_MS=$hold python bench.py --full --steps 10 --warmup 2 --no-extras --no-other-configs --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || tail -3 /tmp/ab.err >> $out
     echo "B=65536  hold_ms=$hold  $(line /tmp/ab.json)" >> $out
   done
 done
 for hold in 0 5; do
-  SC_PAIR_HOLD_MS=$hold python bench.py --batch 131072 --steps 4 --warmup 1 --no-extras --no-other-configs --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || tail -3 /tmp/ab.err >> $out
+  SC_PAIR_HOLD_MS=$hold python bench.py --full --batch 131072 --steps 4 --warmup 1 --no-extras --no-other-configs --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || tail -3 /tmp/ab.err >> $out
   echo "B=131072 hold_ms=$hold  $(line /tmp/ab.json)" >> $out
 done
 for hold in 0 13 5; do
-  SC_PAIR_HOLD_MS=$hold python bench.py --batch 32768 --l 64 --pbits 3072 --dgk dgk_2048_l64 --steps 4 --warmup 1 --no-extras --no-other-configs --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || tail -3 /tmp/ab.err >> $out
+  SC_PAIR_HOLD_MS=$hold python bench.py --full --batch 32768 --l 64 --pbits 3072 --dgk dgk_2048_l64 --steps 4 --warmup 1 --no-extras --no-other-configs --no-cpu-baseline > /tmp/ab.json 2> /tmp/ab.err || tail -3 /tmp/ab.err >> $out
   echo "cfg4 share hold_ms=$hold  $(line /tmp/ab.json)" >> $out
 done

@@ -17,12 +17,12 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/$name -o pmc -- python3 $BENCH --streams 1 > $OUT/$name.log 2>&1 || { tail -5 $OUT/$name.log; exit 1; }
 done
 echo "== bench lines"
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_cfg2_B65536.json 2> $OUT/bench_cfg2.err || exit 1
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --batch 4096 --l 16 --dgk dgk_2048_l16 --no-extras --no-cpu-baseline > $OUT/bench_cfg1_B4096.json 2>> $OUT/bench_other.err || exit 1
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --batch 4096 --l 16 --dgk dgk_2048_l16 --no-extras --no-cpu-baseline --side-stream 0 > $OUT/bench_cfg1_B4096_one_context.json 2>> $OUT/bench_other.err || exit 1
-timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --batch 131072 --no-extras --no-cpu-baseline > $OUT/bench_cfg3share_B131072.json 2>> $OUT/bench_other.err || exit 1
-timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --batch 32768 --l 64 --pbits 3072 --dgk dgk_3072_l64 --no-extras --no-cpu-baseline > $OUT/bench_cfg4share_dgk3072.json 2>> $OUT/bench_other.err || exit 1
-timeout -k 10 300 python3 bench.py --steps 4 --warmup 1 --batch 32768 --l 64 --pbits 3072 --dgk dgk_2048_l64 --no-extras --no-cpu-baseline > $OUT/bench_cfg4share_dgk2048.json 2>> $OUT/bench_other.err || exit 1
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_cfg2_B65536.json 2> $OUT/bench_cfg2.err || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --batch 4096 --l 16 --dgk dgk_2048_l16 --no-extras --no-cpu-baseline > $OUT/bench_cfg1_B4096.json 2>> $OUT/bench_other.err || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --batch 4096 --l 16 --dgk dgk_2048_l16 --no-extras --no-cpu-baseline --side-stream 0 > $OUT/bench_cfg1_B4096_one_context.json 2>> $OUT/bench_other.err || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 6 --warmup 2 --batch 131072 --no-extras --no-cpu-baseline > $OUT/bench_cfg3share_B131072.json 2>> $OUT/bench_other.err || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 4 --warmup 1 --batch 32768 --l 64 --pbits 3072 --dgk dgk_3072_l64 --no-extras --no-cpu-baseline > $OUT/bench_cfg4share_dgk3072.json 2>> $OUT/bench_other.err || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 4 --warmup 1 --batch 32768 --l 64 --pbits 3072 --dgk dgk_2048_l64 --no-extras --no-cpu-baseline > $OUT/bench_cfg4share_dgk2048.json 2>> $OUT/bench_other.err || exit 1
 timeout -k 10 300 python3 tools/gpu_kernel_rates.py > $OUT/kernel_rates.txt 2>&1
 echo "== two-shard step dispatches"
 python3 tools/step_dispatches.py $(find $OUT/stats -name "*kernel_trace.csv" | head -1) 2 > $OUT/step_dispatches_two_shards.txt 2>&1

@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-r04b}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 echo "== round-4 gpu tests"; timeout -k 10 500 python3 -m pytest tests/test_gpu_round4.py -x -q > $OUT/tests_r4.txt 2>&1; tail -15 $OUT/tests_r4.txt
-echo "== bench (default)"; timeout -k 10 500 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
+echo "== bench (default)"; timeout -k 10 500 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
 python3 tools/bench_brief.py < $OUT/bench_default.json
 BENCH="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-other-configs"
 echo "== kernel trace, two shards"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace2 -o t -- python3 $BENCH > $OUT/trace2.log 2>&1 || { tail -5 $OUT/trace2.log; exit 1; }
