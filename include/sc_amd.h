@@ -125,13 +125,16 @@ int sc_dgk_any_zero(sc_ctx* ctx, int key, const uint32_t* c_dptr, int planes, ui
 
 /* Initiator.step_1 + step_3 + the plaintext side of 4c / 4e / 7 for a batch (SC/initiator.py:228-270, :289, :373, :558-562):
  * z = [[y]] [[x]]^-1 [[2^l + r]] mod N^2, randomized with rho_z^N when rho_z is given (:109); alpha = r mod 2^l,
- * alpha_tilde = (r - N) mod 2^l, rsmall = [r < (N-1)/2] (uint64 each), rshift = r div 2^l ([count][nwords]). */
+ * alpha_tilde = (r - N) mod 2^l (flag rows, see FLAG ROWS below), rsmall = [r < (N-1)/2] (uint64), rshift = r div 2^l ([count][nwords]).
+ * FLAG ROWS (every protocol step and plaintext helper): 1 <= l <= 255.  alpha, alpha_tilde and beta hold lw = ceil(l / 64)
+ * little-endian uint64 words per comparison, laid out [count][lw], the bits above l zero; for l <= 64 that is one uint64 per
+ * comparison.  rsmall, delta_a, dbit and delta_b are one uint64 per comparison at every l. */
 int sc_initiator_step1(sc_ctx* ctx, int paillier_key, int l, const uint32_t* x_enc_dptr, const uint32_t* y_enc_dptr,
                        const uint32_t* r_dptr, const uint32_t* rho_z_dptr /* nullable */, int flags, uint32_t* z_out_dptr, uint64_t* alpha_dptr,
                        uint64_t* alpha_tilde_dptr, uint64_t* rsmall_dptr, uint32_t* rshift_dptr, uint64_t count);
 /* KeyHolder.step_2 + step_4a + step_4b (+ the l + 1 .randomize() of SC/keyholder.py:106-108 when r_rand is given): decrypt z,
  * derive beta / d / zeta_1 / zeta_2, and encrypt d and the bits of beta bit-major: d_beta_out[l+1][count][nwords(n)], plane 0 =
- * [d], plane 1 + i = [beta_i].  z_out: [count][nwords(N)]; beta / dbit uint64. */
+ * [d], plane 1 + i = [beta_i].  z_out: [count][nwords(N)]; beta: flag rows [count][ceil(l/64)] uint64; dbit uint64. */
 int sc_keyholder_step2_4b(sc_ctx* ctx, int paillier_key, int dgk_key, int l, const uint32_t* z_enc_dptr,
                           const uint32_t* r_rand_dptr /* nullable */, int r_words, int flags, uint32_t* z_out_dptr, uint64_t* beta_dptr,
                           uint64_t* dbit_dptr, uint32_t* zeta1_dptr, uint32_t* zeta2_dptr, uint32_t* d_beta_out_dptr, uint64_t count);
@@ -142,7 +145,8 @@ int sc_keyholder_step2_4b(sc_ctx* ctx, int paillier_key, int dgk_key, int l, con
  * is the shuffle (each item finds its output plane in the permutation row itself: no destination array, no extra launch).  beta: [l][count][nwords] bit-major; rhos / r_rand:
  * [l+1][count][words].  c_unblinded_out (nullable) receives the output of step 4h.  c_out: [l+1][count][nwords].
  * FLAG WORDS (here and in sc_initiator_step67): rsmall and delta_a hold 0 or 1 per comparison and only BIT 0 is read -- alpha and
- * alpha_tilde are bit fields (bit i = the i-th bit of r mod 2^l, of (r - N) mod 2^l), so every flag of a step is taken by position;
+ * alpha_tilde are flag rows of bit fields (bit i = the i-th bit of r mod 2^l, of (r - N) mod 2^l; [count][ceil(l/64)] uint64), so
+ * every flag of a step is taken by position;
  * a caller's own "true" must be the integer 1 (sc_initiator_step1 and sc_rng_coins produce exactly that). */
 int sc_initiator_step4(sc_ctx* ctx, int dgk_key, int l, const uint32_t* d_enc_dptr, const uint32_t* beta_enc_dptr,
                        const uint64_t* alpha_dptr, const uint64_t* alpha_tilde_dptr, const uint64_t* rsmall_dptr,

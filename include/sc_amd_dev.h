@@ -163,18 +163,21 @@ int sc_crt_combine(sc_ctx* ctx, int mod_p, int mod_full, int cst_k, int cst_negk
 /* ---- plaintext-side word arithmetic of the two parties (HBM-bound helpers) ------------------------ */
 /* From r[count][nw] and the Paillier N: m1 = 2^l + r ([count][nw+1], SC/initiator.py:256), alpha = r mod 2^l
  * (:270), alpha_tilde = (r - N) mod 2^l (:373), rsmall = [r < (N-1)/2] (:289, :559), rshift = r >> l (:562).
- * alpha / alpha_tilde / rsmall are uint64 per item. l <= 64. */
+ * 1 <= l <= 255.  alpha / alpha_tilde are flag rows of lw = ceil(l / 64) little-endian uint64 words per item ([count][lw], the
+ * bits above l zero: one uint64 per item for l <= 64); rsmall is one uint64 per item. */
 int sc_plain_alice(sc_ctx* ctx, const uint32_t* r_dptr, const uint32_t* n_hptr, int nw, int l, uint64_t count,
                    uint32_t* m1_dptr, uint64_t* alpha_dptr, uint64_t* alpha_tilde_dptr, uint64_t* rsmall_dptr,
                    uint32_t* rshift_dptr);
 /* From z[count][nw]: beta = z mod 2^l (SC/keyholder.py:196), dbit = [z < (N-1)/2] (:213), zeta1 = z >> l,
- * zeta2 = (z + N) >> l if dbit else z >> l (:274-282). */
+ * zeta2 = (z + N) >> l if dbit else z >> l (:274-282).  1 <= l <= 255; beta is a flag row [count][ceil(l/64)] uint64, dbit one
+ * uint64 per item. */
 int sc_plain_bob(sc_ctx* ctx, const uint32_t* z_dptr, const uint32_t* n_hptr, int nw, int l, uint64_t count,
                  uint64_t* beta_dptr, uint64_t* dbit_dptr, uint32_t* zeta1_dptr, uint32_t* zeta2_dptr);
 
 /* ---- fused Initiator steps 4c-4h (SC/initiator.py:272-485) --------------------------------------- */
 /* Inputs, all bit-major: beta[l][count][nw], beta_inv[l][count][nw], d[count][nw], d_inv[count][nw]
- * (DGK ciphertexts mod n and their inverses), alpha / alpha_tilde / rsmall / delta_a uint64 per comparison,
+ * (DGK ciphertexts mod n and their inverses), alpha / alpha_tilde flag rows [count][ceil(l/64)] uint64 (1 <= l <= 255),
+ * rsmall / delta_a uint64 per comparison,
  * cst_g / cst_ginv = registered g and g^-1.  Output c[l+1][count][nw] in the order c_-1, c_0 .. c_{l-1}
  * (SC/initiator.py:484), not blinded. */
 int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uint32_t* beta_dptr,

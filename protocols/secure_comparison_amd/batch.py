@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from ._views import cat_rows
+from .flags import check_l
 from .initiator import Initiator
 from .keyholder import KeyHolder
 from .schemes import DGK, Paillier
@@ -131,7 +132,9 @@ def secure_comparison_batch(x_enc: torch.Tensor, y_enc: torch.Tensor, l: int, al
     side: both parties' scheme objects bound to a SECOND engine and stream (same keys): with randomize=True the randomizer
     exponentiations run there, concurrently with the critical path on the caller's stream (see _AheadOfTime) -- inside this
     call, so they are part of the step; identical results.
-    out: the [B][2nw] array the results are written to (e.g. a shard's row block of the whole batch's result array)."""
+    out: the [B][2nw] array the results are written to (e.g. a shard's row block of the whole batch's result array).
+    l: 1 <= l <= 255 (flags.py); ValueError before anything is launched otherwise."""
+    check_l(l)
     if randomize == "pool":
         return _secure_comparison_batch_pooled(x_enc, y_enc, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, draws)
     if side is not None and randomize:
@@ -263,6 +266,7 @@ class ConcurrentShards:
         one array without a concatenation pass."""
         if len(shards) != len(self.parties):
             raise ValueError("one shard per party set")
+        check_l(l)
         caller = torch.cuda.current_stream()
         device = caller.device
         blocks = [None] * len(shards)

@@ -26,6 +26,7 @@
 
 #ifndef SC_INV_TOP
 #define SC_INV_TOP 2048
+#define SC_MAX_L 255      // widest comparison: l + 1 <= 256 bit planes (byte permutations, 8-bit flag fields; include/sc_amd.h)
 #endif
 #ifndef SC_PVM_WAVES
 #define SC_PVM_WAVES 2    // waves per SIMD the pair interpreter is compiled for (sc_kernel_pvm.h)

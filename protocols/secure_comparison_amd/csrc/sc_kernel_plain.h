@@ -8,9 +8,19 @@ namespace sc {
 // ---------------------------------------------------------------------------------------------
 // Plain-integer helper kernels on canonical 32-bit words (HBM-bound, one thread per item).
 // ---------------------------------------------------------------------------------------------
+// 64-bit word j of a number held as nw little-endian 32-bit words (0 past its end)
+__device__ __forceinline__ uint64_t word64(const uint32_t* x, int nw, int j) {
+  const int k = 2 * j;
+  return (k < nw ? (uint64_t)x[k] : 0ull) | ((k + 1 < nw) ? ((uint64_t)x[k + 1] << 32) : 0ull);
+}
+
+// Flag rows (include/sc_amd.h): alpha, alpha_tilde and beta are LW = ceil(l / 64) little-endian u64 words per item, [count][LW];
+// LW = 1 is the [count] array of l <= 64.  The launch picks the instance from l, so 64 (LW - 1) < l <= 64 LW.
+
 // Alice's plaintext-side values derived from r (SC/initiator.py:250-256, :270, :289, :373, :558-562):
-//   m1 = 2^l + r (as nw+1 words), alpha = r mod 2^l, alpha_tilde = (r - N) mod 2^l,
+//   m1 = 2^l + r (as nw+1 words), alpha = r mod 2^l, alpha_tilde = (r - N) mod 2^l (the borrow carried across the flag words),
 //   rsmall = [r < (N-1)/2], rshift = r >> l.
+template <int LW>
 __global__ void k_plain_alice(const uint32_t* __restrict__ r, const uint32_t* __restrict__ nmod,
                               const uint32_t* __restrict__ halfn /* (N-1)/2 */, int nw, int l, uint64_t count,
                               uint32_t* __restrict__ m1, uint64_t* __restrict__ alpha,
@@ -19,11 +29,18 @@ __global__ void k_plain_alice(const uint32_t* __restrict__ r, const uint32_t* __
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const uint32_t* ri = r + i * nw;
-  const uint64_t lmask = (l >= 64) ? ~0ull : ((1ull << l) - 1);
-  const uint64_t rlow = (uint64_t)ri[0] | ((nw > 1) ? ((uint64_t)ri[1] << 32) : 0ull);
-  const uint64_t nlow = (uint64_t)nmod[0] | ((nw > 1) ? ((uint64_t)nmod[1] << 32) : 0ull);
-  alpha[i] = rlow & lmask;
-  alpha_tilde[i] = (rlow - nlow) & lmask;
+  const int top = l - 64 * (LW - 1);   // bits of the top flag word, 1 .. 64
+  const uint64_t tmask = (top >= 64) ? ~0ull : ((1ull << top) - 1);
+  uint64_t borrow = 0;
+#pragma unroll
+  for (int j = 0; j < LW; j++) {
+    const uint64_t rw = word64(ri, nw, j), nwd = word64(nmod, nw, j);
+    const uint64_t mask = (j == LW - 1) ? tmask : ~0ull;
+    const uint64_t diff = rw - nwd - borrow;
+    borrow = (rw < nwd || rw - nwd < borrow) ? 1ull : 0ull;
+    alpha[i * LW + j] = rw & mask;
+    alpha_tilde[i * LW + j] = diff & mask;
+  }
   int cmp = 0;  // r ? halfn
   for (int k = nw - 1; k >= 0 && cmp == 0; k--) cmp = (ri[k] > halfn[k]) ? 1 : ((ri[k] < halfn[k]) ? -1 : 0);
   rsmall[i] = (cmp < 0) ? 1ull : 0ull;
@@ -43,9 +60,10 @@ __global__ void k_plain_alice(const uint32_t* __restrict__ r, const uint32_t* __
 }
 
 // Bob's plaintext-side values derived from z (SC/keyholder.py:196, :213, :274-282):
-//   beta = z mod 2^l, dbit = [z < (N-1)/2], zeta1 = z >> l, zeta2 = (z + N) >> l if dbit else z >> l.
+//   beta = z mod 2^l (LW words), dbit = [z < (N-1)/2], zeta1 = z >> l, zeta2 = (z + N) >> l if dbit else z >> l.
 //   bits (nullable): the plaintext bits of steps 4a / 4b as bytes, bit-major [l+1][count]: plane 0 = d, plane 1 + i = bit i of beta
 //   (SC/keyholder.py:213, 230-233) -- what the g^bit selection of the DGK encryption launch reads.
+template <int LW>
 __global__ void k_plain_bob(const uint32_t* __restrict__ z, const uint32_t* __restrict__ nmod,
                             const uint32_t* __restrict__ halfn, int nw, int l, uint64_t count,
                             uint64_t* __restrict__ beta, uint64_t* __restrict__ dbit, uint32_t* __restrict__ zeta1,
@@ -53,16 +71,25 @@ __global__ void k_plain_bob(const uint32_t* __restrict__ z, const uint32_t* __re
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const uint32_t* zi = z + i * nw;
-  const uint64_t lmask = (l >= 64) ? ~0ull : ((1ull << l) - 1);
-  const uint64_t zlow = (uint64_t)zi[0] | ((nw > 1) ? ((uint64_t)zi[1] << 32) : 0ull);
-  beta[i] = zlow & lmask;
+  const int tb = l - 64 * (LW - 1);   // bits of the top flag word, 1 .. 64
+  const uint64_t tmask = (tb >= 64) ? ~0ull : ((1ull << tb) - 1);
+  uint64_t bw[LW];
+#pragma unroll
+  for (int j = 0; j < LW; j++) {
+    bw[j] = word64(zi, nw, j) & ((j == LW - 1) ? tmask : ~0ull);
+    beta[i * LW + j] = bw[j];
+  }
   int cmp = 0;
   for (int k = nw - 1; k >= 0 && cmp == 0; k--) cmp = (zi[k] > halfn[k]) ? 1 : ((zi[k] < halfn[k]) ? -1 : 0);
   const bool d = cmp < 0;
   dbit[i] = d ? 1ull : 0ull;
   if (bits) {
     bits[i] = d ? 1 : 0;
-    for (int k = 0; k < l; k++) bits[(uint64_t)(k + 1) * count + i] = (uint8_t)((zlow >> k) & 1);
+#pragma unroll
+    for (int j = 0; j < LW; j++) {
+      const int nb = (j == LW - 1) ? tb : 64;
+      for (int k = 0; k < nb; k++) bits[(uint64_t)(64 * j + k + 1) * count + i] = (uint8_t)((bw[j] >> k) & 1);
+    }
   }
   const int ws = l >> 5, bs = l & 31;
   // zeta2: first the sum z + (d ? N : 0) (nw words + a carry word), then an in-place

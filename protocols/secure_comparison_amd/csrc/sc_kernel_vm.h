@@ -75,8 +75,9 @@ __global__ void __launch_bounds__(64, (G == 1 && L == 37) ? 2 : (L == 27 ? SC_L2
         } else if (akind == AK_TBLSEL) {
           const VmExt& ea = args.ext[op.w1 & 0xf];
           const VmExt& eb = args.ext[(op.w1 >> 12) & 0xf];
-          const uint64_t fa = ((const uint64_t*)ea.ptr)[idx] >> ((op.w1 >> 4) & 0xff);
-          const uint64_t fb = ((const uint64_t*)eb.ptr)[idx] >> ((op.w1 >> 16) & 0xff);
+          const uint32_t ba = (op.w1 >> 4) & 0xff, bb = (op.w1 >> 16) & 0xff;   // flag rows: 32-bit word (bit >> 5) of the item's row
+          const uint32_t fa = ((const uint32_t*)ea.ptr)[idx * ea.stride + (ba >> 5)] >> (ba & 31);
+          const uint32_t fb = ((const uint32_t*)eb.ptr)[idx * eb.stride + (bb >> 5)] >> (bb & 31);
           const uint32_t sel = (uint32_t)((fa & 1) * 2 + (fb & 1));
           src_limbs = my_tbl + (uint64_t)((op.w2 >> (8 * sel)) & 0xff) * S * TS;
           src_ts = TS;
@@ -156,9 +157,14 @@ __global__ void __launch_bounds__(64, (G == 1 && L == 37) ? 2 : (L == 27 ? SC_L2
         }
         case OP_LOADW:
         case OP_ADDW: {
-          // imm != 0: one of two arrays, chosen per item by bit (w1 >> 12) of the u64 flag ext (w1 >> 8) & 15: set -> ext w1 & 15,
+          // imm != 0: one of two arrays, chosen per item by bit (w1 >> 12) & 255 of the flag row in ext (w1 >> 8) & 15: set -> ext w1 & 15,
           // clear -> ext (w1 >> 4) & 15 (same shape; the step formulas' "a if flag else b" without a select pass over the batch)
-          const bool pick = imm && ((((const uint64_t*)args.ext[(op.w1 >> 8) & 0xf].ptr)[idx] >> ((op.w1 >> 12) & 0x3f)) & 1) == 0;
+          bool pick = false;
+          if (imm) {
+            const VmExt& fe = args.ext[(op.w1 >> 8) & 0xf];
+            const uint32_t bit = (op.w1 >> 12) & 0xff;
+            pick = ((((const uint32_t*)fe.ptr)[idx * fe.stride + (bit >> 5)] >> (bit & 31)) & 1) == 0;
+          }
           const VmExt& e = args.ext[(pick ? (op.w1 >> 4) : op.w1) & 0xf];
           const uint64_t flat = (uint64_t)op.w2 * args.count + idx;
           const uint32_t woff = op.w3 >> 16;
@@ -204,18 +210,24 @@ __global__ void __launch_bounds__(64, (G == 1 && L == 37) ? 2 : (L == 27 ? SC_L2
             const uint64_t b = idx % inner;
             const uint32_t jp = (uint32_t)(idx / inner);
             const int64_t* __restrict__ prow = (const int64_t*)pe.ptr + b * planes;
-            uint64_t seen0 = 0, seen1 = 0;
-            bool ok = true;
+            // values 0 .. 127 in a first pass, 128 .. 255 in a second one where there are more than 128 planes (l <= 255): two
+            // 64-bit masks either way, so the check costs the interpreter no registers
+            bool ok = planes <= 256;
             uint32_t found = jp;
+#pragma unroll 1
+            for (uint32_t half = 0; half < (planes > 128 ? 2u : 1u); half++) {
+              uint64_t seen0 = 0, seen1 = 0;
 #pragma unroll 4
-            for (uint32_t k = 0; k < planes; k++) {
-              const uint64_t v = (uint64_t)prow[k];
-              const bool inr = v < (uint64_t)planes;
-              const uint64_t bit = 1ull << (v & 63);
-              const uint64_t word = (v & 64) ? seen1 : seen0;
-              ok = ok && inr && !(word & bit);
-              if (inr) { if (v & 64) seen1 |= bit; else seen0 |= bit; }
-              found = (inr && (uint32_t)v == jp) ? k : found;
+              for (uint32_t k = 0; k < planes; k++) {
+                const uint64_t v = (uint64_t)prow[k];
+                const bool inr = v < (uint64_t)planes;
+                const bool mine = inr && (v >> 7) == half;
+                const uint64_t bit = 1ull << (v & 63);
+                const uint64_t word = (v & 64) ? seen1 : seen0;
+                ok = ok && inr && !(mine && (word & bit));
+                if (mine) { if (v & 64) seen1 |= bit; else seen0 |= bit; }
+                found = (inr && (uint32_t)v == jp) ? k : found;
+              }
             }
             flat = ok ? (uint64_t)found * inner + b : idx;
           } else if (op.w3) flat = ((const uint64_t*)args.ext[(op.w3 - 1) & 0xf].ptr)[idx];   // scatter to explicit rows; guarded by e.limit
@@ -269,9 +281,13 @@ __global__ void __launch_bounds__(64, (G == 1 && L == 37) ? 2 : (L == 27 ? SC_L2
           break;
         }
         case OP_ADD1: {
-          // imm != 0: add bit (w1 >> 4) & 63 of the u64 flag ext w1 & 15, inverted when w1 >> 12 is set, instead of 1
+          // imm != 0: add bit (w1 >> 4) & 255 of the flag row in ext w1 & 15, inverted when w1 >> 12 is set, instead of 1
           uint32_t one = 1u;
-          if (imm) one = (uint32_t)((((const uint64_t*)args.ext[op.w1 & 0xf].ptr)[idx] >> ((op.w1 >> 4) & 0x3f)) & 1) ^ ((op.w1 >> 12) & 1);
+          if (imm) {
+            const VmExt& fe = args.ext[op.w1 & 0xf];
+            const uint32_t bit = (op.w1 >> 4) & 0xff;
+            one = ((((const uint32_t*)fe.ptr)[idx * fe.stride + (bit >> 5)] >> (bit & 31)) & 1) ^ ((op.w1 >> 12) & 1);
+          }
           acc[0] += (gp.j == 0) ? one : 0u;
           gp.renorm(acc);
           break;

@@ -16,12 +16,26 @@ int sc_host::launch_xgcd(hipStream_t stream, const uint32_t* x, uint32_t* out, c
 }
 int sc_host::launch_plain_alice(hipStream_t stream, const uint32_t* r, const uint32_t* nmod, const uint32_t* halfn, int nw, int l, uint64_t count,
                                 uint32_t* m1, uint64_t* alpha, uint64_t* alpha_tilde, uint64_t* rsmall, uint32_t* rshift) {
-  hipLaunchKernelGGL(k_plain_alice, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, r, nmod, halfn, nw, l, count, m1, alpha, alpha_tilde, rsmall, rshift);
+  const dim3 grid((unsigned)((count + 255) / 256));
+  switch ((l + 63) / 64) {   // words per flag row (the caller has checked 1 <= l <= 255)
+    case 1: hipLaunchKernelGGL(k_plain_alice<1>, grid, dim3(256), 0, stream, r, nmod, halfn, nw, l, count, m1, alpha, alpha_tilde, rsmall, rshift); break;
+    case 2: hipLaunchKernelGGL(k_plain_alice<2>, grid, dim3(256), 0, stream, r, nmod, halfn, nw, l, count, m1, alpha, alpha_tilde, rsmall, rshift); break;
+    case 3: hipLaunchKernelGGL(k_plain_alice<3>, grid, dim3(256), 0, stream, r, nmod, halfn, nw, l, count, m1, alpha, alpha_tilde, rsmall, rshift); break;
+    case 4: hipLaunchKernelGGL(k_plain_alice<4>, grid, dim3(256), 0, stream, r, nmod, halfn, nw, l, count, m1, alpha, alpha_tilde, rsmall, rshift); break;
+    default: return -1;
+  }
   return launched();
 }
 int sc_host::launch_plain_bob(hipStream_t stream, const uint32_t* z, const uint32_t* nmod, const uint32_t* halfn, int nw, int l, uint64_t count,
                               uint64_t* beta, uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2, uint8_t* bits) {
-  hipLaunchKernelGGL(k_plain_bob, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, z, nmod, halfn, nw, l, count, beta, dbit, zeta1, zeta2, bits);
+  const dim3 grid((unsigned)((count + 255) / 256));
+  switch ((l + 63) / 64) {
+    case 1: hipLaunchKernelGGL(k_plain_bob<1>, grid, dim3(256), 0, stream, z, nmod, halfn, nw, l, count, beta, dbit, zeta1, zeta2, bits); break;
+    case 2: hipLaunchKernelGGL(k_plain_bob<2>, grid, dim3(256), 0, stream, z, nmod, halfn, nw, l, count, beta, dbit, zeta1, zeta2, bits); break;
+    case 3: hipLaunchKernelGGL(k_plain_bob<3>, grid, dim3(256), 0, stream, z, nmod, halfn, nw, l, count, beta, dbit, zeta1, zeta2, bits); break;
+    case 4: hipLaunchKernelGGL(k_plain_bob<4>, grid, dim3(256), 0, stream, z, nmod, halfn, nw, l, count, beta, dbit, zeta1, zeta2, bits); break;
+    default: return -1;
+  }
   return launched();
 }
 int sc_host::launch_rng_bits(hipStream_t stream, const RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count) {

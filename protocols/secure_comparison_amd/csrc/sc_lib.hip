@@ -223,7 +223,7 @@ struct Builder {
   void mul_extw(int ext, uint32_t off = 0) { emit(OP_MUL, AK_EXTW, 0, ext, off); muls++; }
   void mul_extl(int ext, uint32_t off = 0) { emit(OP_MUL, AK_EXTL, 0, ext, off); muls++; }
   void loadw(int ext, uint32_t off = 0, uint32_t woff = 0, uint32_t nw = 0) { emit(OP_LOADW, 0, 0, ext, off, (woff << 16) | nw); }
-  // ext_set where bit `bit` of the item's u64 flag (ext flag_ext) is set, else ext_clear (sc_vm.h)
+  // ext_set where bit `bit` (0 .. 255) of the item's flag row (ext flag_ext) is set, else ext_clear (sc_vm.h)
   void loadw_sel(int ext_set, int ext_clear, int flag_ext, int bit, uint32_t off = 0) { emit(OP_LOADW, 0, 1, ext_set | (ext_clear << 4) | (flag_ext << 8) | (bit << 12), off); }
   void add_flag(int flag_ext, int bit, bool invert) { emit(OP_ADD1, 0, 1, flag_ext | (bit << 4) | ((invert ? 1 : 0) << 12)); }
   void addw(int ext, uint32_t off = 0, uint32_t woff = 0, uint32_t nw = 0) { emit(OP_ADDW, 0, 0, ext, off, (woff << 16) | nw); }
@@ -833,7 +833,7 @@ static int modexp_var_impl(sc_ctx* ctx, int mod, const uint32_t* x, const uint32
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
   if (!valid_mod(ctx, mod) || !x || !e || !out || ewords <= 0 || ebits <= 0 || ebits > 32 * ewords)
     return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad argument");
-  if (perm && (dest || planes == 0 || planes > 128 || count % planes != 0)) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad permutation batch");
+  if (perm && (dest || planes == 0 || planes > SC_MAX_L + 1 || count % planes != 0)) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad permutation batch");
   const Fbt* f = nullptr;
   if (fbt >= 0) {
     if (fbt >= (int)ctx->fbts.size() || ctx->fbts[fbt].mod != mod || !e2 || e2words <= 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad fixed-base table");
@@ -936,7 +936,7 @@ int sc_paillier_l_mul(sc_ctx* ctx, int mod, int cst_k, const uint32_t* x, int x_
 int sc_plain_alice(sc_ctx* ctx, const uint32_t* r, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint32_t* m1,
                    uint64_t* alpha, uint64_t* alpha_tilde, uint64_t* rsmall, uint32_t* rshift) {
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!ctx || !r || !n_hptr || nw <= 0 || l <= 0 || l > 64 || !m1 || !alpha || !alpha_tilde || !rsmall || !rshift)
+  if (!ctx || !r || !n_hptr || nw <= 0 || l <= 0 || l > SC_MAX_L || !m1 || !alpha || !alpha_tilde || !rsmall || !rshift)
     return fail(ctx, SC_ERR_ARG, "sc_plain_alice: bad argument");
   if (count == 0) return SC_OK;
   uint32_t* d_n = nullptr;
@@ -955,7 +955,7 @@ int sc_plain_bob(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr, int nw,
 static int plain_bob_impl(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint64_t* beta,
                           uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2, uint8_t* bits) {
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!ctx || !z || !n_hptr || nw <= 0 || l <= 0 || l > 64 || !beta || !dbit || !zeta1 || !zeta2)
+  if (!ctx || !z || !n_hptr || nw <= 0 || l <= 0 || l > SC_MAX_L || !beta || !dbit || !zeta1 || !zeta2)
     return fail(ctx, SC_ERR_ARG, "sc_plain_bob: bad argument");
   if (count == 0) return SC_OK;
   uint32_t* d_n = nullptr;
@@ -1105,7 +1105,7 @@ int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uin
                  const uint32_t* d, const uint32_t* d_inv, const uint64_t* alpha, const uint64_t* alpha_tilde,
                  const uint64_t* rsmall, const uint64_t* delta_a, uint32_t* c_out, uint64_t count) {
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!valid_mod(ctx, mod) || l <= 0 || l > 64 || !beta || !beta_inv || !d || !d_inv || !alpha || !alpha_tilde || !rsmall || !delta_a || !c_out)
+  if (!valid_mod(ctx, mod) || l <= 0 || l > SC_MAX_L || !beta || !beta_inv || !d || !d_inv || !alpha || !alpha_tilde || !rsmall || !delta_a || !c_out)
     return fail(ctx, SC_ERR_ARG, "sc_dgk_step4: bad argument");
   if (cst_g < 0 || cst_ginv < 0 || cst_g >= (int)ctx->consts.size() || cst_ginv >= (int)ctx->consts.size() ||
       ctx->consts[cst_g].mod != mod || ctx->consts[cst_ginv].mod != mod)
@@ -1162,7 +1162,8 @@ int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uin
                    mk_ext(d_park, m.S, 0)};
     int rc = run_vm(ctx, mod, ita->second, ex, 5, count); if (rc) return rc;
   }
-  // ---- launch (b): the bit loop i = l-1 .. 0 (SC/initiator.py:471-482) then c_-1 (:484)
+  // ---- launch (b): the bit loop i = l-1 .. 0 (SC/initiator.py:471-482) then c_-1 (:484).  About 12 micro-ops per bit (each run of
+  // squarings is one op with a repeat count): some 3 000 ops, 48 KB, at l = 255, uploaded once per key and l like any program.
   auto itb = ctx->progs.find(kb);
   if (itb == ctx->progs.end()) {
     Builder bd; const int cg = bd.use_const(cst_g);
@@ -1192,8 +1193,9 @@ int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uin
   }
   int rc;
   {
+    const uint32_t fw = 2 * (uint32_t)((l + 63) / 64);   // 32-bit words per flag row of alpha / alpha~ (include/sc_amd.h)
     VmExt ex[6] = {mk_ext(beta, m.nwords, m.nwords), mk_ext(beta_inv, m.nwords, m.nwords), mk_ext(d_park, m.S, 0),
-                   mk_ext(alpha, 2, 2), mk_ext(alpha_tilde, 2, 2), mk_ext(c_out, m.nwords, m.nwords)};
+                   mk_ext(alpha, fw, fw), mk_ext(alpha_tilde, fw, fw), mk_ext(c_out, m.nwords, m.nwords)};
     rc = run_vm(ctx, mod, itb->second, ex, 6, count);
   }
   return rc;

@@ -510,7 +510,7 @@ int sc_initiator_step1(sc_ctx* ctx, int paillier_key_id, int l, const uint32_t* 
                        uint32_t* rshift, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
-  if (!kp || !x_enc || !y_enc || !r || !z_out || !alpha || !alpha_tilde || !rsmall || !rshift || l <= 0 || l > 64)
+  if (!kp || !x_enc || !y_enc || !r || !z_out || !alpha || !alpha_tilde || !rsmall || !rshift || l <= 0 || l > SC_MAX_L)
     return fail(ctx, SC_ERR_ARG, "sc_initiator_step1: bad argument");
   const PaillierKey k = *kp;
   if (l + 3 >= big_bits(k.n) - 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_step1: 2^(l+2) must be below N / 2 (SC/initiator.py:249)");
@@ -552,7 +552,7 @@ int sc_initiator_step4i(sc_ctx* ctx, int dgk_key_id, int l, const uint32_t* c_in
                         const uint32_t* r_rand, int r_words, int flags, uint32_t* c_out, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   const DgkKey* kp = dgk_key(ctx, dgk_key_id);
-  if (!kp || l <= 0 || l > 64 || !c_in || !rhos || rho_words <= 0 || !c_out || (r_rand && r_words <= 0))
+  if (!kp || l <= 0 || l > SC_MAX_L || !c_in || !rhos || rho_words <= 0 || !c_out || (r_rand && r_words <= 0))
     return fail(ctx, SC_ERR_ARG, "sc_initiator_step4i: bad argument");
   const DgkKey k = *kp;
   const bool ready = r_rand && (flags & SC_STEP_RANDOMIZERS_READY);     // r_rand holds h^r itself ([l+1][count][nwords]), computed ahead
@@ -576,7 +576,7 @@ int sc_initiator_step4(sc_ctx* ctx, int dgk_key_id, int l, const uint32_t* d_enc
                        uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   const DgkKey* kp = dgk_key(ctx, dgk_key_id);
-  if (!kp || l <= 0 || l > 64 || !d_enc || !beta_enc || !alpha || !alpha_tilde || !rsmall || !delta_a || !c_out ||
+  if (!kp || l <= 0 || l > SC_MAX_L || !d_enc || !beta_enc || !alpha || !alpha_tilde || !rsmall || !delta_a || !c_out ||
       (rhos && rho_words <= 0) || (r_rand && (r_words <= 0 || !rhos)))
     return fail(ctx, SC_ERR_ARG, "sc_initiator_step4: bad argument");
   const DgkKey k = *kp;
@@ -609,7 +609,7 @@ int sc_keyholder_step2_4b(sc_ctx* ctx, int paillier_key_id, int dgk_key_id, int 
   if (ctx && count == 0) return SC_OK;
   const PaillierKey* pk = paillier_key(ctx, paillier_key_id);
   const DgkKey* dk = dgk_key(ctx, dgk_key_id);
-  if (!pk || !dk || !pk->secret || l <= 0 || l > 64 || !z_enc || !z_out || !beta || !dbit || !zeta1 || !zeta2 || !d_beta_out || (r_rand && r_words <= 0))
+  if (!pk || !dk || !pk->secret || l <= 0 || l > SC_MAX_L || !z_enc || !z_out || !beta || !dbit || !zeta1 || !zeta2 || !d_beta_out || (r_rand && r_words <= 0))
     return fail(ctx, SC_ERR_ARG, "sc_keyholder_step2_4b: bad argument");
   if (big_bits(dk->u) <= l + 2) return fail(ctx, SC_ERR_ARG, "sc_keyholder_step2_4b: u must exceed 2^(l+2) (SC/keyholder.py:212)");
   const PaillierKey p = *pk; const DgkKey d = *dk;
@@ -641,7 +641,7 @@ int sc_keyholder_step4j_5(sc_ctx* ctx, int paillier_key_id, int dgk_key_id, int 
   if (ctx && count == 0) return SC_OK;
   const PaillierKey* pk = paillier_key(ctx, paillier_key_id);
   const DgkKey* dk = dgk_key(ctx, dgk_key_id);
-  if (!pk || !dk || !pk->secret || !dk->secret || l <= 0 || l > 64 || !c_enc || !zeta1 || !zeta2 || !delta_b_out || !out3)
+  if (!pk || !dk || !pk->secret || !dk->secret || l <= 0 || l > SC_MAX_L || !c_enc || !zeta1 || !zeta2 || !delta_b_out || !out3)
     return fail(ctx, SC_ERR_ARG, "sc_keyholder_step4j_5: bad argument");
   const PaillierKey p = *pk;
   const DgkKey d = *dk;

@@ -13,7 +13,7 @@ enum VmOpcode : uint32_t {
   OP_END = 0,
   OP_MUL = 1,        // ACC = mont(A, ACC)                     A given by akind
   OP_LOADW = 2,      // ACC = words  ext[w1] at (off = w2), word offset w3>>16, nwords w3&0xffff (0 = ext default)
-                     //   imm != 0: w1 = extA | extB<<4 | flag ext<<8 | bit<<12: ext A where the item's u64 flag bit is set, else ext B
+                     //   imm != 0: w1 = extA | extB<<4 | flag ext<<8 | bit<<12 (8 bits): ext A where bit `bit` of the item's flag row is set, else ext B
   OP_ADDW = 3,       // ACC += words (same addressing as LOADW), lazy limb-wise add
   OP_LOADT = 4,      // ACC = limb-form operand given by akind (table / const / fbt / ext-limbs)
   OP_REDC = 5,       // ACC = ACC / R mod n;  imm = 1 (modulus-multiple contexts): ACC = ACC c / R mod M
@@ -24,7 +24,7 @@ enum VmOpcode : uint32_t {
   OP_STOREFLAG = 7,  // (canonical(ACC) == const[w3]) -> u8 ext[w1] at off w2;  imm != 0: OR the flag into the u64 ext[w1][item mod ext.stride64]
                      //   instead (ext.limit = inner count): one flag per group of items, e.g. delta_B = OR over the l+1 zero tests
   OP_STT = 8,        // scratch[imm] = ACC
-  OP_ADD1 = 9,       // ACC += 1 (lazy);  imm != 0: ACC += bit (w1>>4)&63 of the item's u64 flag in ext w1&15, inverted if w1>>12
+  OP_ADD1 = 9,       // ACC += 1 (lazy);  imm != 0: ACC += bit (w1>>4)&255 of the item's flag row in ext w1&15, inverted if w1>>12
   OP_SUB1 = 10,      // ACC = (ACC - 1) mod R, exact limbs
   OP_QUOT = 11,      // ACC = ACC / n exactly (ACC must be an exact multiple of n, value < R)
   OP_STOREL = 12,    // limb-form store of ACC to ext[w1] at off w2 (ext stride = S)
@@ -53,7 +53,7 @@ enum VmAKind : uint32_t {
   AK_CONST = 0,   // w1 = LDS constant index (0 = R^2 mod n, 1 = R mod n, 2.. = extra constants)
   AK_ACC = 1,     // the accumulator itself (squaring)
   AK_TBL = 2,     // w1 = scratch entry
-  AK_TBLSEL = 3,  // w1 = flag descriptor (extA | bitA<<4 | extB<<12 | bitB<<16), w2 = 4 scratch entries (bytes) indexed by fa*2+fb
+  AK_TBLSEL = 3,  // w1 = flag descriptor (extA | bitA<<4 | extB<<12 | bitB<<16, 8-bit bit fields), w2 = 4 scratch entries (bytes) indexed by fa*2+fb
   AK_TBLDIG = 4,  // w1 = ext | bitpos<<4 | width<<24 ; w2 = base scratch entry ; entry = base + digit
   AK_FBT = 5,     // w1 = ext | bitpos<<4 | width<<24 ; w2 = window index ; row = fbt[(win << width) + digit]
   AK_EXTW = 6,    // w1 = ext, w2 = off : plain words operand (staged through LDS)
@@ -66,6 +66,8 @@ struct VmOp {
   uint32_t w1, w2, w3;
 };
 
+// Flag operands (AK_TBLSEL, OP_LOADW / OP_ADDW with imm, OP_ADD1 with imm) are flag rows: bit b of item idx is bit (b & 31) of the
+// 32-bit word idx * stride + (b >> 5).  A u64 per item is stride 2; the [count][lw] rows of l > 64 are stride 2 lw (include/sc_amd.h).
 struct VmExt {
   const void* ptr;
   uint32_t stride;   // u32 words between consecutive items (0 = broadcast one item)

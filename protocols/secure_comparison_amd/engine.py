@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .flags import check_l, flag_shape
 from .limbs import int_to_words, ints_to_words, words_to_ints
 
 ScError = _lib.ScError
@@ -458,10 +459,11 @@ class Engine:
         if r.dim() != 2:
             raise ValueError("r: expected [count][nwords]")
         count, nw = r.shape
+        check_l(l)
         m1 = self.empty(count, nw + 1)
-        alpha = torch.empty((count,), dtype=torch.int64, device=self.device)
+        alpha = torch.empty(flag_shape(count, l), dtype=torch.int64, device=self.device)
         alpha_t = torch.empty_like(alpha)
-        rsmall = torch.empty_like(alpha)
+        rsmall = torch.empty((count,), dtype=torch.int64, device=self.device)
         rshift = self.empty(count, nw)
         arr, p = self._host_n_words(n, nw)
         self._sync_stream()
@@ -474,8 +476,9 @@ class Engine:
         if z.dim() != 2:
             raise ValueError("z: expected [count][nwords]")
         count, nw = z.shape
-        beta = torch.empty((count,), dtype=torch.int64, device=self.device)
-        dbit = torch.empty_like(beta)
+        check_l(l)
+        beta = torch.empty(flag_shape(count, l), dtype=torch.int64, device=self.device)
+        dbit = torch.empty((count,), dtype=torch.int64, device=self.device)
         zeta1 = self.empty(count, nw)
         zeta2 = self.empty(count, nw)
         arr, p = self._host_n_words(n, nw)
@@ -489,14 +492,13 @@ class Engine:
                   rsmall: torch.Tensor, delta_a: torch.Tensor) -> torch.Tensor:
         count = self._items(d)
         nw = mod.nwords
+        check_l(l)
         self._arr(d, "d", count, nw)
         self._arr(d_inv, "d_inv", count, nw)
         self._arr(beta, "beta", l * count, nw)
         self._arr(beta_inv, "beta_inv", l * count, nw)
-        for name, t in (("alpha", alpha), ("alpha_tilde", alpha_tilde), ("rsmall", rsmall), ("delta_a", delta_a)):
-            self._arr(t, name, dtype=torch.int64)
-            if t.numel() != count:
-                raise ValueError(f"{name}: {t.numel()} items, expected {count}")
+        self._flags(count, rsmall=rsmall, delta_a=delta_a)
+        self._flag_rows(count, l, alpha=alpha, alpha_tilde=alpha_tilde)
         out = torch.empty((l + 1, count, nw), dtype=torch.int32, device=self.device)
         self._sync_stream()
         self._check(self.lib.sc_dgk_step4(self.ctx, mod.id, self.constant(mod, g), self.constant(mod, g_inv), l,
@@ -665,19 +667,31 @@ class Engine:
             if t.numel() != count:
                 raise ValueError(f"{name}: {t.numel()} items, expected {count}")
 
+    def _flag_rows(self, count: int, l: int, **arrays: torch.Tensor) -> None:
+        """alpha / alpha~: one word per comparison for l <= 64 (as _flags), exactly [count][ceil(l/64)] above (flags.py)."""
+        if l <= 64:
+            self._flags(count, **arrays)
+            return
+        want = flag_shape(count, l)
+        for name, t in arrays.items():
+            self._arr(t, name, dtype=torch.int64)
+            if tuple(t.shape) != want:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, expected flag rows {want} for l = {l}")
+
     def initiator_step1(self, key: PaillierKey, l: int, x_enc: torch.Tensor, y_enc: torch.Tensor, r: torch.Tensor,
                         rho_z: torch.Tensor | None = None, ready: bool = False, out: torch.Tensor | None = None):
         """(z_enc, alpha, alpha_tilde, r_small, r_shift): Initiator.step_1 / step_3 for a batch, [[z]] randomized with rho_z^N
         (`ready`: rho_z holds the finished randomizers rho_z^N mod N^2, [B][2nw], computed ahead of time)."""
         count = self._items(x_enc)
         nw = key.mod_n.nwords
+        check_l(l)
         self._arr(x_enc, "x_enc", count, 2 * nw)
         self._arr(y_enc, "y_enc", count, 2 * nw)
         self._arr(r, "r", count, nw)
         self._arr(rho_z, "rho_z", count, 2 * nw if ready else nw, optional=True)
         z = self._result(out, (count, 2 * nw), "z_out")
-        alpha = torch.empty((count,), dtype=torch.int64, device=self.device)
-        alpha_t, rsmall = torch.empty_like(alpha), torch.empty_like(alpha)
+        alpha = torch.empty(flag_shape(count, l), dtype=torch.int64, device=self.device)
+        alpha_t, rsmall = torch.empty_like(alpha), torch.empty((count,), dtype=torch.int64, device=self.device)
         rshift = self.empty(count, nw)
         self._sync_stream()
         rc = self.lib.sc_initiator_step1(self.ctx, key.id, int(l), self._ptr(x_enc), self._ptr(y_enc), self._ptr(r), self._ptr(rho_z), int(ready),
@@ -690,11 +704,12 @@ class Engine:
         """(z, beta, d, zeta_1, zeta_2, [d],[beta_i] as [l+1][B][nw]): KeyHolder.step_2 / 4a / 4b (+ their randomizations)."""
         count = self._items(z_enc)
         nw, nd = pkey.mod_n.nwords, dkey.mod_n.nwords
+        check_l(l)
         self._arr(z_enc, "z_enc", count, 2 * nw)
         self._arr(r_rand, "r_rand", (l + 1) * count, nd if ready else None, optional=True)
         z, zeta1, zeta2 = self.empty(count, nw), self.empty(count, nw), self.empty(count, nw)
-        beta = torch.empty((count,), dtype=torch.int64, device=self.device)
-        dbit = torch.empty_like(beta)
+        beta = torch.empty(flag_shape(count, l), dtype=torch.int64, device=self.device)
+        dbit = torch.empty((count,), dtype=torch.int64, device=self.device)
         out = self._result(out, (l + 1, count, nd), "d_beta_out")
         self._sync_stream()
         self._check(self.lib.sc_keyholder_step2_4b(self.ctx, pkey.id, dkey.id, int(l), self._ptr(z_enc), self._ptr(r_rand),
@@ -708,9 +723,11 @@ class Engine:
         """(c, c after step 4h or None): Initiator.step_4c .. 4i for a batch; see sc_initiator_step4 (`ready`: r_rand holds h^r)."""
         count = self._items(d_enc)
         nw = key.mod_n.nwords
+        check_l(l)
         self._arr(d_enc, "d_enc", count, nw)
         self._arr(beta_enc, "beta_enc", l * count, nw)
-        self._flags(count, alpha=alpha, alpha_tilde=alpha_tilde, rsmall=rsmall, delta_a=delta_a)
+        self._flags(count, rsmall=rsmall, delta_a=delta_a)
+        self._flag_rows(count, l, alpha=alpha, alpha_tilde=alpha_tilde)
         self._arr(rhos, "rhos", (l + 1) * count, optional=True)
         self._arr(r_rand, "r_rand", (l + 1) * count, nw if ready else None, optional=True)
         if permutation is not None:
@@ -731,6 +748,7 @@ class Engine:
                          r_rand: torch.Tensor | None = None, ready: bool = False) -> torch.Tensor:
         """Blinding c_i^rho_i [* h^r_i] and the per-comparison shuffle of a vector [l+1][B][nw] that is already there."""
         nw = key.mod_n.nwords
+        check_l(l)
         if c_in.dim() != 3 or c_in.shape[0] != l + 1:
             raise ValueError(f"c: expected [{l + 1}][B][{nw}], got {tuple(c_in.shape)}")
         count = c_in.shape[1]
@@ -752,6 +770,7 @@ class Engine:
         """(delta_B int64 [B], [[zeta_1]] | [[zeta_2]] | [[delta_B]] as [3B][2nw]): KeyHolder.step_4j / step_5 (+ randomizations)."""
         nw, nd = pkey.mod_n.nwords, dkey.mod_n.nwords
         count = self._items(zeta1)
+        check_l(l)
         self._arr(c_enc, "c_enc", (l + 1) * count, nd)
         self._arr(zeta1, "zeta_1", count, nw)
         self._arr(zeta2, "zeta_2", count, nw)

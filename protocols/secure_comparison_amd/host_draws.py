@@ -76,7 +76,9 @@ class HostDraws:
         return self._buf[at:at + nbytes]
 
     def randbelow(self, n: int) -> int:
-        """Uniform in [0, n)."""
+        """Uniform in [0, n), n >= 1 (a bound below 1 raises, as secrets.randbelow does)."""
+        if n < 1:
+            raise ValueError(f"randbelow: the bound must be at least 1, got {n}")
         k = n.bit_length()
         nbytes, mask = (k + 7) // 8, (1 << k) - 1
         while True:
@@ -102,9 +104,11 @@ class HostDraws:
     POOL_ROWS = 8192          # values / permutations drawn per vectorised refill of a pool
 
     def below_rows_nonzero(self, n: int, count: int) -> np.ndarray:
-        """`count` uniform integers in [1, n) as rows [count][ceil(bitlen(n)/32)], n < 2^127 (step 4i's rho_i = 1 + randbelow(u - 1)).
-        Independent draws are handed out from a pool that is refilled a few thousand values at a time: the numpy calls of a
-        refill cost the same for 33 values as for 8192, and a session asks for l + 1."""
+        """`count` uniform integers in [1, n) as rows [count][ceil(bitlen(n)/32)], n >= 2 of any width (step 4i's rho_i =
+        1 + randbelow(u - 1); u ~ 2^(l+2) is 259 bits at l = 255).  Independent draws are handed out from a pool that is refilled a
+        few thousand values at a time: the numpy calls of a refill cost the same for 33 values as for 8192, and a session asks for l + 1."""
+        if n < 2:
+            raise ValueError(f"below_rows_nonzero: the range [1, {n}) is empty")
         pools = self.__dict__.setdefault("_below_pools", {})
         rows, at = pools.get(n, (None, 0))
         if rows is None or at + count > len(rows):
@@ -113,6 +117,8 @@ class HostDraws:
         return rows[at:at + count]
 
     def _below_rows_nonzero(self, n: int, count: int) -> np.ndarray:
+        if n < 2:
+            raise ValueError(f"below_rows_nonzero: the range [1, {n}) is empty")
         m = n - 1                                  # draw v in [0, m), return v + 1
         k = m.bit_length()
         nw = (n.bit_length() + 31) // 32
@@ -123,7 +129,7 @@ class HostDraws:
                 got = np.concatenate([got, cand[cand < np.uint64(m)]])
             return (got[:count] + np.uint64(1)).view("<u4").reshape(count, 2)[:, :nw].copy()
         if k > 126:
-            raise ValueError("below_rows_nonzero: bounds of at most 126 bits")
+            return self._below_rows_wide(m, count, nw)
         out = np.empty((count, nw), dtype="<u4")
         filled = 0
         lo_mask, hi_bits = (1 << 64) - 1, k - 64
@@ -140,6 +146,34 @@ class HostDraws:
             words = np.stack([lo1 & np.uint64(0xFFFFFFFF), lo1 >> np.uint64(32), hi1 & np.uint64(0xFFFFFFFF), hi1 >> np.uint64(32)], axis=1).astype("<u4")
             out[filled:filled + len(lo)] = words[:, :nw]
             filled += len(lo)
+        return out
+
+    def _below_rows_wide(self, m: int, count: int, nw: int) -> np.ndarray:
+        """v + 1 for v uniform in [0, m), m of more than 126 bits: rejection sampling over c = ceil(bits / 64) little-endian 64-bit
+        columns per candidate, the top one masked to the bits of m (acceptance above one half)."""
+        k = m.bit_length()
+        c = (k + 63) // 64
+        mcol = [np.uint64((m >> (64 * j)) & ((1 << 64) - 1)) for j in range(c)]
+        top_mask = np.uint64((1 << (k - 64 * (c - 1))) - 1)
+        out = np.empty((count, nw), dtype="<u4")
+        filled = 0
+        while filled < count:
+            need = max(8, 2 * (count - filled) + 4)
+            raw = np.frombuffer(self.take(8 * c * need), dtype="<u8").reshape(need, c).copy()
+            raw[:, c - 1] &= top_mask
+            lt, eq = np.zeros(need, dtype=bool), np.ones(need, dtype=bool)
+            for j in range(c - 1, -1, -1):                           # v < m, compared from the top column down
+                lt |= eq & (raw[:, j] < mcol[j])
+                eq &= raw[:, j] == mcol[j]
+            v = raw[lt][: count - filled]
+            carry = np.ones(len(v), dtype=bool)                      # + 1 with the carry up the columns
+            for j in range(c):
+                v[:, j] += carry.astype("<u8")
+                carry &= v[:, j] == 0
+            words = np.zeros((len(v), 2 * c + 1), dtype="<u4")       # (v + 1 < m + 1 <= 2^k: the carry never leaves column c - 1)
+            words[:, : 2 * c] = v.view("<u4").reshape(len(v), 2 * c)
+            out[filled:filled + len(v)] = words[:, :nw]
+            filled += len(v)
         return out
 
     def coin(self) -> int:

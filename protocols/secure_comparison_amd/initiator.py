@@ -19,17 +19,19 @@ from typing import Any, Sequence, cast
 import torch
 
 from .communicator import Communicator
+from .flags import check_l, flag_rows_of
 from .schemes import DGK, DGKCiphertext, Paillier, PaillierCiphertext
 from .utils import to_bits
 
 
 @dataclass
 class AlicePlain:
-    """Plaintext-side values Alice derives from her blinding value r (one entry per comparison)."""
+    """Plaintext-side values Alice derives from her blinding value r (one entry per comparison).  alpha and alpha_tilde are flag
+    rows (flags.py): [B] u64 for l <= 64, [B][ceil(l/64)] little-endian u64 words for 64 < l <= 255."""
 
     r: torch.Tensor            # [B][nw]   r, 0 <= r < N                       (SC/initiator.py:250)
-    alpha: torch.Tensor        # [B] u64   r mod 2^l                           (:270)
-    alpha_tilde: torch.Tensor  # [B] u64   (r - N) mod 2^l                     (:373)
+    alpha: torch.Tensor        # [B] or [B][lw] u64   r mod 2^l                (:270)
+    alpha_tilde: torch.Tensor  # [B] or [B][lw] u64   (r - N) mod 2^l          (:373)
     r_small: torch.Tensor      # [B] u64   [r < (N-1)//2]                      (:289, :559)
     r_shift: torch.Tensor      # [B][nw]   r div 2^l                           (:562)
 
@@ -77,6 +79,8 @@ class Initiator:
         """All of Alice's steps with the message exchange of SC/initiator.py:69-175."""
         if self.communicator is None:
             raise ValueError("Communicator not properly initialized.")
+        if self.fuse_steps:
+            check_l(self.l_maximum_bit_length)     # the library's range, before anything is received, uploaded or launched
         self.session_id += 1
         sid = self.session_id
         await self.receive_encryption_schemes(sid)
@@ -259,7 +263,11 @@ class Initiator:
         rhos, exps = (np.empty((l + 1, k, w), dtype="<u4") for w in (ew, er))
         for b, it in enumerate(items):
             rhos[:, b], exps[:, b] = it[3], it[5]
-        flags = lambda col: e.upload_u64([it[1][col] & 0xFFFFFFFFFFFFFFFF for it in items])   # noqa: E731
+        def flags(col: int) -> torch.Tensor:     # alpha, alpha~ (cols 0, 1): the sessions' flag rows joined (flags.py), ceil(l/64) words
+            if l <= 64 or col == 2:              # each above l = 64; r_small (col 2) and every flag of l <= 64: one u64
+                return e.upload_u64([it[1][col] & 0xFFFFFFFFFFFFFFFF for it in items])
+            return e.upload_words(flag_rows_of([it[1][col] for it in items], l).view("<u4")).view(torch.int64)
+
         plain = AlicePlain(None, flags(0), flags(1), flags(2), None)
         tp = e.upload_words(planes)
         c, _ = Initiator.step_4_batch(tp[0], tp[1:], plain, e.upload_u64([it[2] for it in items]), dgk, e.upload_words(rhos),
@@ -300,6 +308,7 @@ class Initiator:
 
         if self.communicator is None:
             raise ValueError("Communicator not properly initialized.")
+        check_l(self.l_maximum_bit_length)
         comm = self.communicator
         self.session_id += 1
         sid = self.session_id

@@ -12,6 +12,7 @@ from typing import cast
 import torch
 
 from .communicator import Communicator
+from .flags import check_l, flag_bit_planes
 from .keygen import next_prime
 from .schemes import DGK, DGKCiphertext, Paillier, PaillierCiphertext
 from .utils import to_bits
@@ -19,10 +20,11 @@ from .utils import to_bits
 
 @dataclass
 class BobPlain:
-    """Plaintext-side values Bob derives from z (one entry per comparison)."""
+    """Plaintext-side values Bob derives from z (one entry per comparison).  beta is a flag row (flags.py): [B] u64 for l <= 64,
+    [B][ceil(l/64)] little-endian u64 words for 64 < l <= 255."""
 
     z: torch.Tensor        # [B][nw]
-    beta: torch.Tensor     # [B] u64  z mod 2^l                           (SC/keyholder.py:196)
+    beta: torch.Tensor     # [B] or [B][lw] u64  z mod 2^l                (SC/keyholder.py:196)
     d: torch.Tensor        # [B] u64  [z < (N-1)//2]                      (:213)
     zeta_1: torch.Tensor   # [B][nw]  z div 2^l                           (:274)
     zeta_2: torch.Tensor   # [B][nw]  (z + N) div 2^l if d else z div 2^l (:275-282)
@@ -65,6 +67,8 @@ class KeyHolder:
         """All of Bob's steps with the message exchange of SC/keyholder.py:70-133."""
         if self.communicator is None:
             raise ValueError("Communicator not properly initialized.")
+        if self.fuse_steps:
+            check_l(self.l_maximum_bit_length)     # the library's range, before anything is sent or launched
         self.session_id += 1
         sid = self.session_id
         await self.make_and_send_encryption_schemes(sid)
@@ -243,6 +247,7 @@ class KeyHolder:
 
         if self.communicator is None:
             raise ValueError("Communicator not properly initialized.")
+        check_l(self.l_maximum_bit_length)
         comm = self.communicator
         self.session_id += 1
         sid = self.session_id
@@ -369,8 +374,12 @@ class KeyHolder:
         row 1+i for beta_i) the `.randomize()` calls of SC/keyholder.py:106-108 are fused in: g^bit * h^r."""
         assert scheme_dgk.public_key.u > (1 << (l + 2))
         count = plain.beta.shape[0]
-        shifts = torch.arange(l, device=plain.beta.device, dtype=torch.int64).reshape(l, 1)
-        bits = torch.cat([plain.d.reshape(1, count), (plain.beta.reshape(1, count) >> shifts) & 1], dim=0)  # [l+1][B]
+        if l <= 64:
+            shifts = torch.arange(l, device=plain.beta.device, dtype=torch.int64).reshape(l, 1)
+            planes = (plain.beta.reshape(1, count) >> shifts) & 1
+        else:
+            planes = flag_bit_planes(plain.beta, l)                     # bit i from word i // 64 of the flag row
+        bits = torch.cat([plain.d.reshape(1, count), planes], dim=0)  # [l+1][B]
         if randomizer_exponents is not None:
             enc = scheme_dgk.encrypt_bits_randomized_batch(bits.reshape(-1), randomizer_exponents.reshape((l + 1) * count, -1))
         else:
