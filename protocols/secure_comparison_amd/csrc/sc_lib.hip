@@ -3,6 +3,8 @@
 // the sc_launch_*.hip translation units (sc_internal.h), so this file holds no device code.
 #include "sc_internal.h"
 
+#include <type_traits>
+
 using namespace sc;
 using namespace sc_host;
 
@@ -110,6 +112,41 @@ struct AuxFork {
   }
   ~AuxFork() { (void)join(); }      // error paths: never leave the context on its second stream, nor forked work unordered
 };
+// Times work enqueued on the context's stream between two events (created on first use); they are destroyed on every path.
+struct LaunchTimer {
+  sc_ctx* ctx;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  explicit LaunchTimer(sc_ctx* c) : ctx(c) {}
+  // *ms = the time of what `enqueue` queues (it returns SC_OK or an error code, which is passed on), waited for
+  template <class F> int time(F&& enqueue, float* ms) {
+    if (!e0) HIPCHK(ctx, hipEventCreate(&e0));
+    if (!e1) HIPCHK(ctx, hipEventCreate(&e1));
+    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
+    int rc = enqueue(); if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
+    HIPCHK(ctx, hipEventSynchronize(e1));
+    HIPCHK(ctx, hipEventElapsedTime(ms, e0, e1));
+    return SC_OK;
+  }
+  ~LaunchTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+// A measurement runs under a launch policy of its own and stays out of the MAC counter: the context's settings are restored on every
+// exit path.
+struct PolicyOverride {
+  sc_ctx* ctx;
+  const int latency_mode, onelane_mode, chip_share;
+  const double mac_counter;
+  explicit PolicyOverride(sc_ctx* c)
+      : ctx(c), latency_mode(c->latency_mode), onelane_mode(c->onelane_mode), chip_share(c->chip_share), mac_counter(c->mac_counter) {}
+  ~PolicyOverride() {
+    ctx->latency_mode = latency_mode; ctx->onelane_mode = onelane_mode; ctx->chip_share = chip_share; ctx->mac_counter = mac_counter;
+  }
+};
+// a device buffer of a measurement, freed on every exit path
+template <class T> struct DevBuf {
+  T* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
 // Should the two CRT halves of a call run side by side on two streams?  Small batches: when a second, independent launch fits
 // beside the first (a wave per SIMD for both: half of the chip's 4 x CUs SIMDs each; off with latency mode 0).  Large ones: when
 // this context has the chip to itself.
@@ -183,23 +220,20 @@ int device_n_half(sc_ctx* ctx, const uint32_t* n_hptr, int nw, uint32_t** out) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// program builder
+// program builders: every micro-op is emitted, and its cost counted, by one of these
 // ------------------------------------------------------------------------------------------------
+// k_vm programs.  Constants: LDS 0 = R^2, 1 = R, 2.. = the extra constants of use_const.
 struct Builder {
   std::vector<VmOp> ops;
   std::vector<int> consts;  // extra constant ids (LDS index = 2 + position)
-  uint32_t nscratch = 1;
-  double muls = 0, redcs = 0, sqrs = 0;
-  void touch(uint32_t e) { nscratch = std::max(nscratch, e + 1); }
-  void emit(uint32_t opc, uint32_t ak = 0, uint32_t imm = 0, uint32_t w1 = 0, uint32_t w2 = 0, uint32_t w3 = 0) {
-    ops.push_back(VmOp{opc | (ak << 8) | (imm << 16), w1, w2, w3});
-  }
   int use_const(int cid) {
     for (size_t i = 0; i < consts.size(); i++) if (consts[i] == cid) return 2 + (int)i;
     consts.push_back(cid);
     return 2 + (int)consts.size() - 1;
   }
   void mul_const(int lds_idx) { emit(OP_MUL, AK_CONST, 0, lds_idx); muls++; }
+  // times LDS constant lds0 where the item's byte in ext is 0, else lds1
+  void mul_constsel(int ext, int lds0, int lds1) { emit(OP_MUL, AK_CONSTSEL, 0, ext, (uint32_t)lds0 | ((uint32_t)lds1 << 8)); muls++; }
   void sqr() {   // consecutive squarings merge into one micro-op with a repeat count (imm, 16 bits)
     sqrs++;
     if (!ops.empty()) {
@@ -225,7 +259,11 @@ struct Builder {
   void loadw(int ext, uint32_t off = 0, uint32_t woff = 0, uint32_t nw = 0) { emit(OP_LOADW, 0, 0, ext, off, (woff << 16) | nw); }
   // ext_set where bit `bit` (0 .. 255) of the item's flag row (ext flag_ext) is set, else ext_clear (sc_vm.h)
   void loadw_sel(int ext_set, int ext_clear, int flag_ext, int bit, uint32_t off = 0) { emit(OP_LOADW, 0, 1, ext_set | (ext_clear << 4) | (flag_ext << 8) | (bit << 12), off); }
+  void add1() { emit(OP_ADD1); }
   void add_flag(int flag_ext, int bit, bool invert) { emit(OP_ADD1, 0, 1, flag_ext | (bit << 4) | ((invert ? 1 : 0) << 12)); }
+  void sub1() { emit(OP_SUB1); }
+  void neg() { emit(OP_NEG); }
+  void quot() { emit(OP_QUOT); redcs++; }
   void addw(int ext, uint32_t off = 0, uint32_t woff = 0, uint32_t nw = 0) { emit(OP_ADDW, 0, 0, ext, off, (woff << 16) | nw); }
   void loadt_const(int lds_idx) { emit(OP_LOADT, AK_CONST, 0, lds_idx); }
   void loadt_tbl(uint32_t e) { touch(e); emit(OP_LOADT, AK_TBL, 0, e); }
@@ -239,6 +277,8 @@ struct Builder {
   }
   void loadt_fbt(int ext, uint32_t bitpos, uint32_t width, uint32_t win) { emit(OP_LOADT, AK_FBT, 0, ext | (bitpos << 4) | (width << 24), win); }
   void loadt_extl(int ext, uint32_t off = 0) { emit(OP_LOADT, AK_EXTL, 0, ext, off); }
+  // ACC = the u64 accumulator ext_acc[item], which is reset to 0; the value also goes to ext_copy[item] (sc_vm.h)
+  void takeflag(int ext_acc, int ext_copy) { emit(OP_TAKEFLAG, 0, 0, ext_acc, ext_copy); }
   void stt(uint32_t e) { touch(e); emit(OP_STT, 0, e); }
   void addt(uint32_t e) { touch(e); emit(OP_ADDT, 0, e); }
   void redc(bool times_c = false) { emit(OP_REDC, 0, times_c ? 1 : 0); redcs++; }     // times_c / over_c: leaving a modulus-multiple context (sc_vm.h)
@@ -247,29 +287,120 @@ struct Builder {
     emit(OP_STOREW, 0, (over_c ? 1 : 0) | (by_perm ? 2 : 0), ext, 0, 1 + ext_index);
   }
   void storel(int ext, uint32_t off = 0) { emit(OP_STOREL, 0, 0, ext, off); }
-  void storeflag(int ext, uint32_t off, int lds_const) { emit(OP_STOREFLAG, 0, 0, ext, off, lds_const); }
-  void end() { emit(OP_END); }
+  // or_group: OR the verdict into the item's group flag (u64) instead of storing a byte
+  void storeflag(int ext, uint32_t off, int lds_const, bool or_group = false) { emit(OP_STOREFLAG, 0, or_group ? 1 : 0, ext, off, lds_const); }
+  // ends the program and uploads it with its constants for modulus `mod`
+  int finalize(sc_ctx* ctx, int mod, Prog* out) {
+    emit(OP_END);
+    if (consts.size() + 2 > VM_MAX_CONST) return fail(ctx, SC_ERR_ARG, "too many constants in program");
+    const Mod& m = ctx->mods[mod];
+    Prog p;
+    p.nops = (uint32_t)ops.size();
+    p.nscratch = nscratch;
+    p.nconst = (uint32_t)consts.size();
+    p.muls_per_item = muls;
+    p.redcs_per_item = redcs;
+    p.sqrs_per_item = sqrs;
+    int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops);
+    if (rc) return rc;
+    if (p.nconst) {
+      rc = dev_alloc(ctx, (size_t)p.nconst * m.S * 4, (void**)&p.d_consts);
+      if (rc) return rc;
+      for (uint32_t i = 0; i < p.nconst; i++)
+        HIPCHK(ctx, hipMemcpyAsync(p.d_consts + (size_t)i * m.S, ctx->consts[consts[i]].d_limbs, (size_t)m.S * 4,
+                                   hipMemcpyDeviceToDevice, ctx->stream));   // stream-ordered before the program's first launch
+    }
+    *out = p;
+    return SC_OK;
+  }
+
+ private:
+  uint32_t nscratch = 1;
+  double muls = 0, redcs = 0, sqrs = 0;
+  void touch(uint32_t e) { nscratch = std::max(nscratch, e + 1); }
+  void emit(uint32_t opc, uint32_t ak = 0, uint32_t imm = 0, uint32_t w1 = 0, uint32_t w2 = 0, uint32_t w3 = 0) {
+    ops.push_back(VmOp{opc | (ak << 8) | (imm << 16), w1, w2, w3});
+  }
 };
 
-int finalize_prog(sc_ctx* ctx, const Mod& m, Builder& b, Prog* out) {
-  if (b.consts.size() + 2 > VM_MAX_CONST) return fail(ctx, SC_ERR_ARG, "too many constants in program");
-  Prog p;
-  p.nops = (uint32_t)b.ops.size();
-  p.nscratch = b.nscratch;
-  p.nconst = (uint32_t)b.consts.size();
-  p.muls_per_item = b.muls;
-  p.redcs_per_item = b.redcs;
-  p.sqrs_per_item = b.sqrs;
-  int rc = upload(ctx, b.ops.data(), b.ops.size() * sizeof(VmOp), (void**)&p.d_ops);
-  if (rc) return rc;
-  if (p.nconst) {
-    rc = dev_alloc(ctx, (size_t)p.nconst * m.S * 4, (void**)&p.d_consts);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < p.nconst; i++)
-      HIPCHK(ctx, hipMemcpyAsync(p.d_consts + (size_t)i * m.S, ctx->consts[b.consts[i]].d_limbs, (size_t)m.S * 4,
-                                 hipMemcpyDeviceToDevice, ctx->stream));   // stream-ordered before the program's first launch
+// the encoding of one k_pvm micro-op (PairBuilder, and the segment cutter of sc_modexp_shared_sq)
+inline VmOp pv_op(uint32_t opc, uint32_t w1 = 0, uint32_t w2 = 0, uint32_t w3 = 0) { return VmOp{opc, w1, w2, w3}; }
+
+// Limb-form constant pairs of a modulus m for the pair arithmetic: pair(R^2) embeds an integer (u,0) -> u; pair(B R) is
+// the radix B = 2^(32 nwords) of the operand chunks.  Each pair (c0, c1) satisfies c0 + c1 m = value (mod m^2), c0, c1 < m.
+int get_pair_consts(sc_ctx* ctx, int mod, uint32_t** out) {
+  auto it = ctx->pair_consts.find(mod);
+  if (it != ctx->pair_consts.end()) { *out = it->second; return SC_OK; }
+  const Mod& m = ctx->mods[mod];
+  Big m2 = big_mul(m.n, m.n);
+  Big one(m2.size(), 0); one[0] = 1;
+  Big r2 = big_shl_mod(one, m2, 2 * m.W * m.S);                       // R^2 mod m^2
+  Big br = big_shl_mod(one, m2, m.W * m.S + 32 * m.nwords);           // B R mod m^2
+  std::vector<uint32_t> limbs;
+  for (const Big* v : {&r2, &br}) {
+    Big q, rem;
+    big_divmod(*v, m.n, &q, &rem);
+    q.resize(m.nwords);
+    for (const Big* part : {&rem, &q}) { auto l = to_limbs(*part, m.S, m.W); limbs.insert(limbs.end(), l.begin(), l.end()); }
   }
-  *out = p;
+  uint32_t* d = nullptr;
+  int rc = upload(ctx, limbs.data(), limbs.size() * 4, (void**)&d);
+  if (rc) return rc;
+  ctx->pair_consts[mod] = d;
+  *out = d;
+  return SC_OK;
+}
+
+// k_pvm programs.  Constants: LDS 2,3 = pair(R^2), 4,5 = pair(B R) (get_pair_consts).  Pair entry e of the table is limb-form
+// entries 2e and 2e + 1.  Costs: muls_per_item carries the exact multiply-adds per item -- a pair squaring is (a*a part) + 3 S^2,
+// a pair product 5 S^2 with the two-row pass, 6 S^2 in the one-lane form (three single passes over one staging area).
+struct PairBuilder {
+  std::vector<VmOp> ops;
+  explicit PairBuilder(const Mod& m)
+      : one_lane(m.G == 1), S2((double)m.S * m.S), SQ(S2 + (double)m.G * m.G * m.L * (m.L + 1) / 2.0 + 2.0 * S2),
+        MU((m.G == 1 ? 6.0 : 5.0) * S2) {}
+  // ACC0 = words ext[ext] (word offset woff, nw words), ACC1 = 0
+  void loadu(int ext, uint32_t woff, uint32_t nw) { ops.push_back(pv_op(PV_LOADU, ext, 0, (woff << 16) | nw)); }
+  void mul_const(uint32_t lds_idx) { ops.push_back(pv_op(PV_MULC, lds_idx)); macs += MU; muls++; }
+  void sqr() { ops.push_back(pv_op(PV_SQR)); macs += SQ; sqrs++; }
+  void mul_tbl(uint32_t e) { touch(e); ops.push_back(pv_op(PV_MULT, e)); macs += MU; muls++; }
+  void loadt_tbl(uint32_t e) { touch(e); ops.push_back(pv_op(PV_LOADT, e)); }
+  void stt(uint32_t e) { touch(e); ops.push_back(pv_op(PV_STT, e)); }
+  void addt(uint32_t e) { touch(e); ops.push_back(pv_op(PV_ADDT, e)); }
+  void out(int ext0, int ext1) { ops.push_back(pv_op(PV_OUT, ext0, ext1)); macs += 2.0 * S2; }
+  // ends the program and uploads it; the host copy of the ops stays with it (segments are cut from it on demand)
+  int finalize(sc_ctx* ctx, int mod, Prog* out) {
+    ops.push_back(pv_op(PV_END));
+    Prog p;
+    // one-lane pair products park an intermediate in a spare row (the last one) of the slot's table
+    p.nops = (uint32_t)ops.size(); p.nscratch = nscratch + (one_lane ? 1 : 0); p.nconst = 4; p.muls_per_item = macs;
+    p.pair_sqrs = sqrs; p.pair_muls = muls;
+    p.host_ops = std::make_shared<std::vector<VmOp>>(ops);
+    int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops); if (rc) return rc;
+    rc = get_pair_consts(ctx, mod, &p.d_consts); if (rc) return rc;
+    *out = p;
+    return SC_OK;
+  }
+
+ private:
+  bool one_lane;
+  double S2, SQ, MU, macs = 0;
+  uint32_t nscratch = 2, sqrs = 0, muls = 0;
+  void touch(uint32_t e) { nscratch = std::max(nscratch, 2 * e + 2); }
+};
+
+// The program cached under `key` in the context, or the one `build` emits into `bd`, finalized for modulus `mod` and cached.
+// `build` may return an error code, which is passed on (nothing is cached then).
+template <class F, class B = Builder>
+int cached_prog(sc_ctx* ctx, const std::string& key, int mod, F&& build, const Prog** out, B bd = B()) {
+  auto it = ctx->progs.find(key);
+  if (it == ctx->progs.end()) {
+    if constexpr (std::is_void_v<decltype(build(bd))>) build(bd);
+    else { int rc = build(bd); if (rc) return rc; }
+    Prog p; int rc = bd.finalize(ctx, mod, &p); if (rc) return rc;
+    it = ctx->progs.emplace(key, p).first;
+  }
+  *out = &it->second;
   return SC_OK;
 }
 
@@ -386,16 +517,17 @@ int best_window(int bits) {
 }
 inline int ebit(const Big& e, int i) { return (e[i >> 5] >> (i & 31)) & 1; }
 
-// emit sliding-window exponentiation of the Montgomery-form value currently in ACC; leaves ACC = x^e (Montgomery form)
-void emit_pow_shared(Builder& b, const Exp& ex) {
+// emit sliding-window exponentiation (ex.bits > 0) of the Montgomery-form value currently in the accumulator, with the table of odd
+// powers x^1, x^3, .. in entries T0, T0 + 1, .. and x^2 in the entry after them; leaves x^e.  Either builder (k_vm or k_pvm).
+template <class B>
+void emit_window_pow(B& b, const Exp& ex, uint32_t T0) {
   const int bits = ex.bits;
-  if (bits == 0) { b.loadt_const(1); return; }
   const int w = best_window(bits);
-  const int NT = 1 << (w - 1);            // odd powers x^1, x^3, ..
-  b.stt(0);
+  const uint32_t NT = 1u << (w - 1);
+  b.stt(T0);
   if (NT > 1) {
-    b.sqr(); b.stt(NT);                   // x^2
-    for (int k = 1; k < NT; k++) { b.loadt_tbl(k - 1); b.mul_tbl(NT); b.stt(k); }
+    b.sqr(); b.stt(T0 + NT);
+    for (uint32_t k = 1; k < NT; k++) { b.loadt_tbl(T0 + k - 1); b.mul_tbl(T0 + NT); b.stt(T0 + k); }
   }
   bool first = true;
   int i = bits - 1;
@@ -405,10 +537,16 @@ void emit_pow_shared(Builder& b, const Exp& ex) {
     while (!ebit(ex.e, j)) j++;
     int v = 0;
     for (int k = i; k >= j; k--) v = (v << 1) | ebit(ex.e, k);
-    if (first) { b.loadt_tbl((v - 1) / 2); first = false; }
-    else { for (int k = 0; k < i - j + 1; k++) b.sqr(); b.mul_tbl((v - 1) / 2); }
+    if (first) { b.loadt_tbl(T0 + (v - 1) / 2); first = false; }
+    else { for (int k = 0; k < i - j + 1; k++) b.sqr(); b.mul_tbl(T0 + (v - 1) / 2); }
     i = j - 1;
   }
+}
+
+// x^e of the Montgomery-form value in ACC, left in ACC (Montgomery form); x^0 is the constant 1
+void emit_pow_shared(Builder& b, const Exp& ex) {
+  if (ex.bits == 0) b.loadt_const(1);
+  else emit_window_pow(b, ex, 0);
 }
 
 int get_const_kred(sc_ctx* ctx, int mod, int* out_cid);
@@ -618,18 +756,14 @@ int sc_modmul(sc_ctx* ctx, int mod, const uint32_t* a, int a_stride, const uint3
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
   if (!valid_mod(ctx, mod) || !a || !b || !out) return fail(ctx, SC_ERR_ARG, "sc_modmul: bad argument");
   const Mod& m = ctx->mods[mod];
-  std::string key = "modmul:" + std::to_string(mod);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd;
+  const Prog* p;
+  int rc = cached_prog(ctx, "modmul:" + std::to_string(mod), mod, [&](Builder& bd) {
     bd.loadw(0); bd.mul_const(0);      // a * R
     bd.mul_extw(1);                    // (aR) * b / R = a b
-    bd.storew(2); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.storew(2);
+  }, &p); if (rc) return rc;
   VmExt ex[3] = {mk_ext(a, a_stride, m.nwords), mk_ext(b, b_stride, m.nwords), mk_ext(out, m.nwords, m.nwords)};
-  return run_vm(ctx, mod, it->second, ex, 3, count);
+  return run_vm(ctx, mod, *p, ex, 3, count);
 }
 
 int sc_modmul_const(sc_ctx* ctx, int mod, const uint32_t* a, int cst, uint32_t* out, uint64_t count) {
@@ -637,18 +771,14 @@ int sc_modmul_const(sc_ctx* ctx, int mod, const uint32_t* a, int cst, uint32_t* 
   if (!valid_mod(ctx, mod) || !a || !out || cst < 0 || cst >= (int)ctx->consts.size() || ctx->consts[cst].mod != mod)
     return fail(ctx, SC_ERR_ARG, "sc_modmul_const: bad argument");
   const Mod& m = ctx->mods[mod];
-  std::string key = "modmulc:" + std::to_string(mod) + ":" + std::to_string(cst);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd;
+  const Prog* p;
+  int rc = cached_prog(ctx, "modmulc:" + std::to_string(mod) + ":" + std::to_string(cst), mod, [&](Builder& bd) {
     int c = bd.use_const(cst);
     bd.loadw(0); bd.mul_const(c);      // a * (cR) / R = a c
-    bd.storew(1); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.storew(1);
+  }, &p); if (rc) return rc;
   VmExt ex[2] = {mk_ext(a, m.nwords, m.nwords), mk_ext(out, m.nwords, m.nwords)};
-  return run_vm(ctx, mod, it->second, ex, 2, count);
+  return run_vm(ctx, mod, *p, ex, 2, count);
 }
 
 int sc_modmul_const_sel(sc_ctx* ctx, int mod, const uint32_t* a, int cst0, int cst1, const uint8_t* flags, uint32_t* out, uint64_t count) {
@@ -657,19 +787,15 @@ int sc_modmul_const_sel(sc_ctx* ctx, int mod, const uint32_t* a, int cst0, int c
   for (int c : {cst0, cst1})
     if (c != -1 && (c < 0 || c >= (int)ctx->consts.size() || ctx->consts[c].mod != mod)) return fail(ctx, SC_ERR_ARG, "sc_modmul_const_sel: bad constant");
   const Mod& m = ctx->mods[mod];
-  std::string key = "mmsel:" + std::to_string(mod) + ":" + std::to_string(cst0) + ":" + std::to_string(cst1);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd;
+  const Prog* p;
+  int rc = cached_prog(ctx, "mmsel:" + std::to_string(mod) + ":" + std::to_string(cst0) + ":" + std::to_string(cst1), mod, [&](Builder& bd) {
     const int l0 = cst0 < 0 ? 1 : bd.use_const(cst0), l1 = cst1 < 0 ? 1 : bd.use_const(cst1);   // LDS constant 1 = R mod n = the residue 1
     bd.loadw(0);
-    bd.emit(OP_MUL, AK_CONSTSEL, 0, 2, (uint32_t)l0 | ((uint32_t)l1 << 8)); bd.muls++;           // a * (c R) / R = a c
-    bd.storew(1); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.mul_constsel(2, l0, l1);        // a * (c R) / R = a c
+    bd.storew(1);
+  }, &p); if (rc) return rc;
   VmExt ex[3] = {mk_ext(a, m.nwords, m.nwords), mk_ext(out, m.nwords, m.nwords), mk_ext(flags, 0, 0)};
-  return run_vm(ctx, mod, it->second, ex, 3, count);
+  return run_vm(ctx, mod, *p, ex, 3, count);
 }
 
 static int onelane_for(sc_ctx* ctx, int mod, uint64_t count);
@@ -690,9 +816,8 @@ static int modexp_shared_impl(sc_ctx* ctx, int mod, int exp, const uint32_t* x, 
   if (x_words <= 0) x_words = m.nwords;
   const int mode = any_flags ? 3 : (flags ? 2 : (mul_into ? 1 : 0));
   std::string key = "mexp:" + std::to_string(mod) + ":" + std::to_string(exp) + ":" + std::to_string(x_words) + ":" + std::to_string(mode);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd;
+  const Prog* p;
+  int rc = cached_prog(ctx, key, mod, [&](Builder& bd) -> int {
     if (x_words > m.nwords) {
       int kc; int rc = get_const_kred(ctx, mod, &kc); if (rc) return rc;
       emit_load_reduced(ctx, m, bd, 0, x_words, bd.use_const(kc));
@@ -703,16 +828,13 @@ static int modexp_shared_impl(sc_ctx* ctx, int mod, int exp, const uint32_t* x, 
     emit_pow_shared(bd, ctx->exps[exp]);
     if (mode == 0) { bd.redc(); bd.storew(1); }
     else if (mode == 1) { bd.mul_extw(2); bd.storew(1); }
-    else if (mode == 2) { bd.storeflag(1, 0, 1); }    // compare with R mod n (Montgomery one)
-    else { bd.emit(OP_STOREFLAG, 0, 1, 1, 0, 1); }    // ... and OR the verdict into the item's group flag
-    bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    else bd.storeflag(1, 0, 1, mode == 3);             // compare with R mod n (Montgomery one); mode 3: OR the verdict into the item's group flag
+    return SC_OK;
+  }, &p); if (rc) return rc;
   VmExt ex[3] = {mk_ext(x, x_words, x_words),
                  any_flags ? mk_ext(any_flags, 0, 0, inner) : (flags ? mk_ext(flags, 0, 0) : mk_ext(out, m.nwords, m.nwords)),
                  mk_ext(mul_into, m.nwords, m.nwords)};
-  return run_vm(ctx, mod, it->second, ex, 3, count);
+  return run_vm(ctx, mod, *p, ex, 3, count);
 }
 
 int sc_modexp_shared(sc_ctx* ctx, int mod, int exp, const uint32_t* x, int x_words, const uint32_t* mul_into, uint32_t* out, uint64_t count) {
@@ -747,8 +869,7 @@ int sc_fbt_create(sc_ctx* ctx, int mod, const uint32_t* base_hptr, int exp_bits,
     Builder bd; int c = bd.use_const(cbase);
     bd.loadt_const(c); bd.storel(0, 0);
     for (int j = 1; j < f.nwin; j++) { for (int k = 0; k < window; k++) bd.sqr(); bd.storel(0, j); }
-    bd.end();
-    Prog p; rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
+    Prog p; rc = bd.finalize(ctx, mod, &p); if (rc) return rc;
     VmExt ex[1] = {mk_ext(d_B, m.S, 0)};
     rc = run_vm(ctx, mod, p, ex, 1, 1); if (rc) return rc;
   }
@@ -766,8 +887,7 @@ int sc_fbt_create(sc_ctx* ctx, int mod, const uint32_t* base_hptr, int exp_bits,
     for (int k = lg - 2; k >= 0; k--) { bd.sqr(); bd.mul_tbldig(1, k, 1, 0); }
     bd.storel(2, 0);
     for (uint32_t i = 1; i < CH; i++) { bd.mul_tbl(2); bd.storel(2, i); }
-    bd.end();
-    Prog p; rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
+    Prog p; rc = bd.finalize(ctx, mod, &p); if (rc) return rc;
     for (int j = 0; j < f.nwin; j++) {
       VmExt ex[3] = {mk_ext(d_B + (size_t)j * m.S, 0, 0), mk_ext(d_idx, 1, 1),
                      mk_ext(f.d_rows + ((uint64_t)j << window) * m.S, m.S, 0)};
@@ -807,19 +927,15 @@ int sc_fixedbase_pow(sc_ctx* ctx, int fbt, const uint32_t* e, int ewords, const 
   if (!ctx || fbt < 0 || fbt >= (int)ctx->fbts.size() || !e || !out || ewords <= 0) return fail(ctx, SC_ERR_ARG, "sc_fixedbase_pow: bad argument");
   const Fbt& f = ctx->fbts[fbt];
   const Mod& m = ctx->mods[f.mod];
-  std::string key = "fbp:" + std::to_string(fbt) + ":" + std::to_string(mul_into ? 1 : 0);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd;
+  const Prog* p;
+  int rc = cached_prog(ctx, "fbp:" + std::to_string(fbt) + ":" + std::to_string(mul_into ? 1 : 0), f.mod, [&](Builder& bd) {
     bd.loadt_fbt(0, 0, f.window, 0);
     for (int j = 1; j < f.nwin; j++) bd.mul_fbt(0, j * f.window, f.window, j);
     if (mul_into) bd.mul_extw(2); else bd.redc();
-    bd.storew(1); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.storew(1);
+  }, &p); if (rc) return rc;
   VmExt ex[3] = {mk_ext(e, ewords, ewords), mk_ext(out, m.nwords, m.nwords), mk_ext(mul_into, m.nwords, m.nwords)};
-  return run_vm(ctx, f.mod, it->second, ex, 3, count, f.d_rows);
+  return run_vm(ctx, f.mod, *p, ex, 3, count, f.d_rows);
 }
 
 static int neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count);
@@ -848,11 +964,10 @@ static int modexp_var_impl(sc_ctx* ctx, int mod, const uint32_t* x, const uint32
   const int rmod = twin ? tmod : mod;
   const Mod& m = ctx->mods[mod];        // (taken after the twin exists: creating it may move the table of moduli)
   std::string key = "mvar:" + std::to_string(rmod) + ":" + std::to_string(ebits) + ":" + std::to_string(fbt) + (dest ? ":s" : "") + (perm ? ":q" : "") + (premul ? ":p" : "");
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
+  const Prog* p;
+  int rc = cached_prog(ctx, key, rmod, [&](Builder& bd) {
     const int w = ebits <= 4 ? 1 : (ebits <= 12 ? 2 : 3);
     const int nd = (ebits + w - 1) / w;
-    Builder bd;
     bd.loadw(0); bd.mul_const(0); bd.stt(1);          // t[1] = x (Montgomery)
     bd.loadt_const(1); bd.stt(0);                      // t[0] = 1
     for (int k = 2; k < (1 << w); k++) { bd.loadt_tbl(k - 1); bd.mul_tbl(1); bd.stt(k); }
@@ -861,14 +976,11 @@ static int modexp_var_impl(sc_ctx* ctx, int mod, const uint32_t* x, const uint32
     if (f) for (int j = 0; j < f->nwin; j++) bd.mul_fbt(3, j * f->window, f->window, j);
     if (premul) bd.mul_extw(5); else bd.redc(twin);      // (x^e R) * premul / R = x^e premul: leaves Montgomery form by itself
     if (dest || perm) bd.storew_at(2, 4, twin, perm != nullptr); else bd.storew(2, 0, twin);
-    bd.end();
-    Prog p; int rc = finalize_prog(ctx, ctx->mods[rmod], bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+  }, &p); if (rc) return rc;
   // a scattered store never leaves the output array: rows >= count are dropped by the limit of the output operand
   VmExt ex[6] = {mk_ext(x, m.nwords, m.nwords), mk_ext(e, ewords, ewords), mk_ext(out, m.nwords, m.nwords, (dest || perm) ? count : ~0ull),
                  mk_ext(e2, e2words, e2words), perm ? mk_ext(perm, planes, 0, count / planes) : mk_ext(dest, 2, 2), mk_ext(premul, m.nwords, m.nwords)};
-  return run_vm(ctx, rmod, it->second, ex, 6, count, f ? f->d_rows : nullptr);
+  return run_vm(ctx, rmod, *p, ex, 6, count, f ? f->d_rows : nullptr);
 }
 
 int sc_modexp_var(sc_ctx* ctx, int mod, const uint32_t* x, const uint32_t* e, int ewords, int ebits, int fbt,
@@ -898,17 +1010,15 @@ static int paillier_encrypt_raw_impl(sc_ctx* ctx, int mod_n2, int cst_n, const u
   const Mod& m = ctx->mods[mod_n2];
   if (m_words > m.nwords) return fail(ctx, SC_ERR_ARG, "sc_paillier_encrypt_raw: plaintext wider than N^2");
   std::string key = std::string(negate ? "pencn:" : "penc:") + std::to_string(mod_n2) + ":" + std::to_string(cst_n) + ":" + std::to_string(m_words);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd; int c = bd.use_const(cst_n);
+  const Prog* p;
+  int rc = cached_prog(ctx, key, mod_n2, [&](Builder& bd) {
+    int c = bd.use_const(cst_n);
     bd.loadw(0, 0, 0, m_words); bd.mul_const(c);   // m * (N R) / R = m N  (mod N^2)
-    if (negate) bd.emit(OP_NEG);                   // -m N: the inverse ciphertext (1 + mN)^-1 = 1 - mN (mod N^2)
-    bd.emit(OP_ADD1); bd.storew(1); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    if (negate) bd.neg();                          // -m N: the inverse ciphertext (1 + mN)^-1 = 1 - mN (mod N^2)
+    bd.add1(); bd.storew(1);
+  }, &p); if (rc) return rc;
   VmExt ex[2] = {mk_ext(mwords, m_words, m_words), mk_ext(out, m.nwords, m.nwords)};
-  return run_vm(ctx, mod_n2, it->second, ex, 2, count);
+  return run_vm(ctx, mod_n2, *p, ex, 2, count);
 }
 
 int sc_paillier_l_mul(sc_ctx* ctx, int mod, int cst_k, const uint32_t* x, int x_words, uint32_t* out, uint64_t count) {
@@ -916,21 +1026,18 @@ int sc_paillier_l_mul(sc_ctx* ctx, int mod, int cst_k, const uint32_t* x, int x_
   if (!valid_mod(ctx, mod) || cst_k < 0 || cst_k >= (int)ctx->consts.size() || ctx->consts[cst_k].mod != mod || !x || !out || x_words <= 0)
     return fail(ctx, SC_ERR_ARG, "sc_paillier_l_mul: bad argument");
   const Mod& m = ctx->mods[mod];
-  std::string key = "plmul:" + std::to_string(mod) + ":" + std::to_string(cst_k) + ":" + std::to_string(x_words);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd; int c = bd.use_const(cst_k);
+  const Prog* p;
+  int rc = cached_prog(ctx, "plmul:" + std::to_string(mod) + ":" + std::to_string(cst_k) + ":" + std::to_string(x_words), mod, [&](Builder& bd) {
+    int c = bd.use_const(cst_k);
     const int lw = std::min(x_words, (m.W * m.S + 31) / 32);   // only x mod R matters for the exact quotient
     bd.loadw(0, 0, 0, lw);
-    bd.emit(OP_SUB1);                 // y = (x - 1) mod R, exact limbs
-    bd.emit(OP_QUOT); bd.redcs++;     // y / n  (< n because x < n^2)
+    bd.sub1();                        // y = (x - 1) mod R, exact limbs
+    bd.quot();                        // y / n  (< n because x < n^2)
     bd.mul_const(c);                  // * k
-    bd.storew(1); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.storew(1);
+  }, &p); if (rc) return rc;
   VmExt ex[2] = {mk_ext(x, x_words, x_words), mk_ext(out, m.nwords, m.nwords)};
-  return run_vm(ctx, mod, it->second, ex, 2, count);
+  return run_vm(ctx, mod, *p, ex, 2, count);
 }
 
 int sc_plain_alice(sc_ctx* ctx, const uint32_t* r, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint32_t* m1,
@@ -1006,42 +1113,33 @@ static int modinv_rec(sc_ctx* ctx, int mod, const uint32_t* x, uint32_t* out, ui
   // divides out again:   x_i^-1 = u_i Q_{i-1} / R   and   u_{i-1} = u_i x_i / R = (x_0 .. x_{i-1})^-1 R^(i-1),   u_0 = x_0^-1.
   // Three products per element (round 3: six -- two conversions, a reduction pass and the same three).  Elements past the end
   // of the batch read as 1 and take part like any other factor.
-  std::string k1 = "inv1d:" + std::to_string(mod) + ":" + std::to_string(K), k2 = "inv2d:" + std::to_string(mod) + ":" + std::to_string(K);
-  auto it1 = ctx->progs.find(k1);
-  if (it1 == ctx->progs.end()) {
-    Builder bd;
+  const Prog *up, *down;
+  int rc = cached_prog(ctx, "inv1d:" + std::to_string(mod) + ":" + std::to_string(K), mod, [&](Builder& bd) {
     for (uint32_t i = 0; i < K; i++) {
       if (i == 0) bd.loadw(0, 0); else bd.mul_extw(0, i);
       bd.storel(1, i);
     }
-    bd.storew(2); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it1 = ctx->progs.emplace(k1, p).first;
-  }
-  auto it2 = ctx->progs.find(k2);
-  if (it2 == ctx->progs.end()) {
-    Builder bd;
+    bd.storew(2);
+  }, &up); if (rc) return rc;
+  rc = cached_prog(ctx, "inv2d:" + std::to_string(mod) + ":" + std::to_string(K), mod, [&](Builder& bd) {
     bd.loadw(3);                                           // u_{K-1}: the inverse of the chunk total
     for (uint32_t i = K - 1; i >= 1; i--) {
       bd.stt(0);
       bd.mul_extl(1, i - 1); bd.storew(4, i);              // x_i^-1 = u_i Q_{i-1} / R
       bd.loadt_tbl(0); bd.mul_extw(0, i);                  // u_{i-1} = u_i x_i / R
     }
-    bd.storew(4, 0); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it2 = ctx->progs.emplace(k2, p).first;
-  }
+    bd.storew(4, 0);
+  }, &down); if (rc) return rc;
   pend->levels.push_back(InvLevel{x, count, K, C});
-  int rc;
   {
     VmExt ex[3] = {mk_ext(x, m.nwords, m.nwords, count), mk_ext(d_P, m.S, 0, (uint64_t)K * C), mk_ext(d_tot, m.nwords, m.nwords)};
-    rc = run_vm(ctx, mod, it1->second, ex, 3, C);
+    rc = run_vm(ctx, mod, *up, ex, 3, C);
   }
   if (!rc) rc = modinv_rec(ctx, mod, d_tot, d_totinv, C, pend, depth + 1);
   if (!rc) {
     VmExt ex[5] = {mk_ext(x, m.nwords, m.nwords, count), mk_ext(d_P, m.S, 0, (uint64_t)K * C), mk_ext(nullptr, 0, 0),
                    mk_ext(d_totinv, m.nwords, m.nwords), mk_ext(out, m.nwords, m.nwords, count)};
-    rc = run_vm(ctx, mod, it2->second, ex, 5, C);
+    rc = run_vm(ctx, mod, *down, ex, 5, C);
   }
   return rc;
 }
@@ -1132,10 +1230,9 @@ int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uin
   const int NP = 7;
   uint32_t* d_park;
   { int rc0 = tmp_buf(ctx, TMP_PARK, (size_t)NP * count * m.S * 4, (void**)&d_park); if (rc0) return rc0; }
-  std::string ka = key + ":a3", kb = key + ":b3";
-  auto ita = ctx->progs.find(ka);
-  if (ita == ctx->progs.end()) {
-    Builder bd; const int cg = bd.use_const(cst_g), cgi = bd.use_const(cst_ginv);
+  const Prog *pa, *pb;
+  int rc = cached_prog(ctx, key + ":a3", mod, [&](Builder& bd) {
+    const int cg = bd.use_const(cst_g), cgi = bd.use_const(cst_ginv);
     // scratch (Montgomery form): 0 one, 1 g, 2 ginv, 3 d, 4 dinv, 5 d', 6 d'^-1, 7 g^s, 8 g d'^-1
     bd.loadt_const(1); bd.stt(0);
     bd.loadt_const(cg); bd.stt(1);
@@ -1153,20 +1250,16 @@ int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uin
     bd.loadt_tbl(7); bd.mul_tbl(1); bd.storel(4, 5);                               // C11 = g^s g            (alpha_i = 1, :476)
     bd.loadt_tbl(7); bd.mul_tbl(8); bd.storel(4, 4);                               // C10 = g^s g d'^-1
     bd.loadt_tblsel(3, 0, 3, 0, 0, 0, 1, 1); bd.redc(); bd.storel(4, 6);           // g^delta_a (:484), plain
-    bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    ita = ctx->progs.emplace(ka, p).first;
-  }
+  }, &pa); if (rc) return rc;
   {
     VmExt ex[5] = {mk_ext(d, m.nwords, m.nwords), mk_ext(d_inv, m.nwords, m.nwords), mk_ext(rsmall, 2, 2), mk_ext(delta_a, 2, 2),
                    mk_ext(d_park, m.S, 0)};
-    int rc = run_vm(ctx, mod, ita->second, ex, 5, count); if (rc) return rc;
+    rc = run_vm(ctx, mod, *pa, ex, 5, count); if (rc) return rc;
   }
   // ---- launch (b): the bit loop i = l-1 .. 0 (SC/initiator.py:471-482) then c_-1 (:484).  About 12 micro-ops per bit (each run of
   // squarings is one op with a repeat count): some 3 000 ops, 48 KB, at l = 255, uploaded once per key and l like any program.
-  auto itb = ctx->progs.find(kb);
-  if (itb == ctx->progs.end()) {
-    Builder bd; const int cg = bd.use_const(cst_g);
+  rc = cached_prog(ctx, key + ":b3", mod, [&](Builder& bd) {
+    const int cg = bd.use_const(cst_g);
     // ext: 0 beta, 1 beta_inv, 2 park, 3 alpha, 4 alpha_tilde, 5 out
     // scratch: 0 K00 = R^2, 1 K01, 2 K10, 3 K11 = g R^2, 4 C00, 5 C01, 6 C10, 7 C11, 8 w_sum, 9 w_sum^3
     bd.loadt_const(0); bd.stt(0);
@@ -1187,18 +1280,11 @@ int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uin
       if (i > 0) { bd.sqr(); bd.mul_tbl(8); bd.stt(9); }                  // its cube for the next bit
     }
     bd.loadt_extl(2, 6); bd.mul_tbl(8); bd.storew(5, 0);                  // c_-1 = g^delta_a * w_sum (:484)
-    bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    itb = ctx->progs.emplace(kb, p).first;
-  }
-  int rc;
-  {
-    const uint32_t fw = 2 * (uint32_t)((l + 63) / 64);   // 32-bit words per flag row of alpha / alpha~ (include/sc_amd.h)
-    VmExt ex[6] = {mk_ext(beta, m.nwords, m.nwords), mk_ext(beta_inv, m.nwords, m.nwords), mk_ext(d_park, m.S, 0),
-                   mk_ext(alpha, fw, fw), mk_ext(alpha_tilde, fw, fw), mk_ext(c_out, m.nwords, m.nwords)};
-    rc = run_vm(ctx, mod, itb->second, ex, 6, count);
-  }
-  return rc;
+  }, &pb); if (rc) return rc;
+  const uint32_t fw = 2 * (uint32_t)((l + 63) / 64);   // 32-bit words per flag row of alpha / alpha~ (include/sc_amd.h)
+  VmExt ex[6] = {mk_ext(beta, m.nwords, m.nwords), mk_ext(beta_inv, m.nwords, m.nwords), mk_ext(d_park, m.S, 0),
+                 mk_ext(alpha, fw, fw), mk_ext(alpha_tilde, fw, fw), mk_ext(c_out, m.nwords, m.nwords)};
+  return run_vm(ctx, mod, *pb, ex, 6, count);
 }
 
 int sc_crt_combine(sc_ctx* ctx, int mod_p, int mod_full, int cst_k, int cst_negk, int cst_mq, const uint32_t* a_p, int a_p_words,
@@ -1215,60 +1301,31 @@ int sc_crt_combine(sc_ctx* ctx, int mod_p, int mod_full, int cst_k, int cst_negk
   uint32_t* d_t;
   { int rc0 = tmp_buf(ctx, TMP_CRT, (size_t)count * mp.nwords * 4, (void**)&d_t); if (rc0) return rc0; }
   std::string k1 = "crt1:" + std::to_string(mod_p) + ":" + std::to_string(cst_k) + ":" + std::to_string(cst_negk) + ":" + std::to_string(a_p_words) + ":" + std::to_string(a_q_words);
-  auto it1 = ctx->progs.find(k1);
-  if (it1 == ctx->progs.end()) {
-    Builder bd; const int ck = bd.use_const(cst_k), cn = bd.use_const(cst_negk);
+  const Prog *p1, *p2;
+  int rc = cached_prog(ctx, k1, mod_p, [&](Builder& bd) -> int {
+    const int ck = bd.use_const(cst_k), cn = bd.use_const(cst_negk);
     int kc = -1;
     if (a_p_words > mp.nwords || a_q_words > mp.nwords) { int cid; int rc = get_const_kred(ctx, mod_p, &cid); if (rc) return rc; kc = bd.use_const(cid); }
     if (a_p_words > mp.nwords) emit_load_reduced(ctx, mp, bd, 0, a_p_words, kc); else bd.loadw(0, 0, 0, a_p_words);
     bd.mul_const(ck); bd.stt(0);                                     // a_p * k
     if (a_q_words > mp.nwords) emit_load_reduced(ctx, mp, bd, 1, a_q_words, kc); else bd.loadw(1, 0, 0, a_q_words);
     bd.mul_const(cn); bd.addt(0);                                    // + a_q * (m_p - k)  = (a_p - a_q) * m_q^-1  (mod m_p)
-    bd.storew(2); bd.end();
-    Prog p; int rc = finalize_prog(ctx, mp, bd, &p); if (rc) return rc;
-    it1 = ctx->progs.emplace(k1, p).first;
-  }
+    bd.storew(2);
+    return SC_OK;
+  }, &p1); if (rc) return rc;
   {
     VmExt ex[3] = {mk_ext(a_p, a_p_words, a_p_words), mk_ext(a_q, a_q_words, a_q_words), mk_ext(d_t, mp.nwords, mp.nwords)};
-    int rc = run_vm(ctx, mod_p, it1->second, ex, 3, count); if (rc) return rc;
+    rc = run_vm(ctx, mod_p, *p1, ex, 3, count); if (rc) return rc;
   }
   std::string k2 = "crt2:" + std::to_string(mod_full) + ":" + std::to_string(cst_mq) + ":" + std::to_string(mp.nwords) + ":" + std::to_string(a_q_words);
-  auto it2 = ctx->progs.find(k2);
-  if (it2 == ctx->progs.end()) {
-    Builder bd; const int cm = bd.use_const(cst_mq);
+  rc = cached_prog(ctx, k2, mod_full, [&](Builder& bd) {
+    const int cm = bd.use_const(cst_mq);
     bd.loadw(0, 0, 0, mp.nwords); bd.mul_const(cm);                  // m_q * t   (< m_p m_q: exact)
     bd.addw(1, 0, 0, a_q_words);                                     // + a_q
-    bd.storew(2); bd.end();
-    Prog p; int rc = finalize_prog(ctx, mf, bd, &p); if (rc) return rc;
-    it2 = ctx->progs.emplace(k2, p).first;
-  }
+    bd.storew(2);
+  }, &p2); if (rc) return rc;
   VmExt ex[3] = {mk_ext(d_t, mp.nwords, mp.nwords), mk_ext(a_q, a_q_words, a_q_words), mk_ext(out, mf.nwords, mf.nwords)};
-  return run_vm(ctx, mod_full, it2->second, ex, 3, count);
-}
-
-// Limb-form constant pairs of a modulus m for the pair arithmetic: pair(R^2) embeds an integer (u,0) -> u; pair(B R) is
-// the radix B = 2^(32 nwords) of the operand chunks.  Each pair (c0, c1) satisfies c0 + c1 m = value (mod m^2), c0, c1 < m.
-static int get_pair_consts(sc_ctx* ctx, int mod, uint32_t** out) {
-  auto it = ctx->pair_consts.find(mod);
-  if (it != ctx->pair_consts.end()) { *out = it->second; return SC_OK; }
-  const Mod& m = ctx->mods[mod];
-  Big m2 = big_mul(m.n, m.n);
-  Big one(m2.size(), 0); one[0] = 1;
-  Big r2 = big_shl_mod(one, m2, 2 * m.W * m.S);                       // R^2 mod m^2
-  Big br = big_shl_mod(one, m2, m.W * m.S + 32 * m.nwords);           // B R mod m^2
-  std::vector<uint32_t> limbs;
-  for (const Big* v : {&r2, &br}) {
-    Big q, rem;
-    big_divmod(*v, m.n, &q, &rem);
-    q.resize(m.nwords);
-    for (const Big* part : {&rem, &q}) { auto l = to_limbs(*part, m.S, m.W); limbs.insert(limbs.end(), l.begin(), l.end()); }
-  }
-  uint32_t* d = nullptr;
-  int rc = upload(ctx, limbs.data(), limbs.size() * 4, (void**)&d);
-  if (rc) return rc;
-  ctx->pair_consts[mod] = d;
-  *out = d;
-  return SC_OK;
+  return run_vm(ctx, mod_full, *p2, ex, 3, count);
 }
 
 // the context the pair kernel runs in for modulus `mod`: itself when its configuration has a pair kernel, otherwise a twin
@@ -1376,43 +1433,34 @@ static int onelane_calibrate(sc_ctx* ctx, OneLaneCal* out) {
   int rc = create_mod(ctx, n.data(), nw, false, &mod); if (rc) return rc;
   rc = sc_exp_create(ctx, e.data(), (int)e.size(), &exp); if (rc) return rc;
   const uint64_t n1 = (uint64_t)c.simds * 2 * 64, n2 = n1 / 2;                    // numbers of a full one-lane / two-lane round
-  uint32_t *x = nullptr, *y = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  DevBuf<uint32_t> x, y;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  struct Cleanup {       // every exit path frees the operands and the events
-    uint32_t **x, **y; hipEvent_t *e0, *e1;
-    ~Cleanup() { if (*x) (void)hipFree(*x); if (*y) (void)hipFree(*y); if (*e0) (void)hipEventDestroy(*e0); if (*e1) (void)hipEventDestroy(*e1); }
-  } cleanup{&x, &y, &e0, &e1};
-  HIPCHK(ctx, hipMalloc((void**)&x, n1 * nw * 4));
-  HIPCHK(ctx, hipMalloc((void**)&y, n1 * nw * 4));
-  HIPCHK(ctx, hipMemsetAsync(x, 0x5a, n1 * nw * 4, ctx->stream));
-  HIPCHK(ctx, hipEventCreate(&e0)); HIPCHK(ctx, hipEventCreate(&e1));
-  const int saved_lat = ctx->latency_mode, saved_one = ctx->onelane_mode, saved_share = ctx->chip_share;
-  const double saved_macs = ctx->mac_counter;
+  HIPCHK(ctx, hipMalloc((void**)&x.p, n1 * nw * 4));
+  HIPCHK(ctx, hipMalloc((void**)&y.p, n1 * nw * 4));
+  HIPCHK(ctx, hipMemsetAsync(x.p, 0x5a, n1 * nw * 4, ctx->stream));
+  LaunchTimer timer(ctx);
+  PolicyOverride keep(ctx);
   ctx->latency_mode = 0; ctx->chip_share = 1;
   auto timed = [&](int form, uint64_t count, double* ms) -> int {
-    ctx->onelane_mode = form;                       // 0: the modulus's own two-lane configuration, 2: the one-lane twin
+    ctx->onelane_mode = form;                     // 0: the modulus's own two-lane configuration, 2: the one-lane twin
     double best = 1e30;
     for (int rep = 0; rep < 2; rep++) {
-      HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-      int r = modexp_shared_impl(ctx, mod, exp, x, nw, nullptr, y, nullptr, count, nullptr, 0, false); if (r) return r;
-      HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-      HIPCHK(ctx, hipEventSynchronize(e1));
-      float t = 0; HIPCHK(ctx, hipEventElapsedTime(&t, e0, e1));
+      float t = 0;
+      int r = timer.time([&] { return modexp_shared_impl(ctx, mod, exp, x.p, nw, nullptr, y.p, nullptr, count, nullptr, 0, false); }, &t);
+      if (r) return r;
       if (t < best) best = t;
     }
     *ms = best;
     return SC_OK;
   };
   double two_15 = 0, warm = 0;
-  rc = timed(2, 64, &warm);                         // program build, code load
+  rc = timed(2, 64, &warm);                       // program build, code load
   if (!rc) rc = timed(0, 64, &warm);
   if (!rc) rc = timed(2, n1, &c.one_full);
   if (!rc) rc = timed(2, n1 / 2, &c.one_half);
   if (!rc) rc = timed(0, n2, &c.two_full);
   if (!rc) rc = timed(0, n2 / 2, &c.two_only_half);
   if (!rc) rc = timed(0, n2 + n2 / 2, &two_15);
-  ctx->latency_mode = saved_lat; ctx->onelane_mode = saved_one; ctx->chip_share = saved_share; ctx->mac_counter = saved_macs;
   if (rc) return rc;
   c.two_half = std::max(0.0, two_15 - c.two_full);
   // A calibration taken while something else used the chip (another context's launches, another process) gives ratios no idle
@@ -1488,8 +1536,7 @@ struct PairOpTimes { double sqr_ms = 0, mul_ms = 0; };
 static std::mutex g_pair_cal_mutex;
 static std::map<std::tuple<int, int, int, bool>, PairOpTimes> g_pair_cal;     // (device, G, L, neg1)
 
-static int pair_op_times(sc_ctx* ctx, int mod_m, uint64_t count, const uint32_t* x, int x_words, uint32_t* d_w, uint32_t* d_w1, int wm,
-                         double* sqr_ms, double* mul_ms) {
+static int pair_op_times(sc_ctx* ctx, int mod_m, uint64_t count, int x_words, const VmExt* ex3, double* sqr_ms, double* mul_ms) {
   int G, L; bool neg1;
   pvm_instance(ctx, ctx->mods[mod_m], count, &G, &L, &neg1);
   const auto key = std::make_tuple(ctx->device, G, L, neg1);
@@ -1498,50 +1545,32 @@ static int pair_op_times(sc_ctx* ctx, int mod_m, uint64_t count, const uint32_t*
   if (it != g_pair_cal.end()) { *sqr_ms = it->second.sqr_ms; *mul_ms = it->second.mul_ms; return SC_OK; }
   const Mod m = ctx->mods[mod_m];
   const uint32_t nw = (uint32_t)std::min(x_words, m.nwords);
-  auto build = [&](int nsq, int nmul, Prog* out) -> int {
-    std::vector<VmOp> ops;
-    ops.push_back(VmOp{PV_LOADU, 0, 0, nw});
-    ops.push_back(VmOp{PV_MULC, 2, 0, 0});
-    ops.push_back(VmOp{PV_STT, 1, 0, 0});
-    for (int i = 0; i < nsq; i++) ops.push_back(VmOp{PV_SQR, 0, 0, 0});
-    for (int i = 0; i < nmul; i++) ops.push_back(VmOp{PV_MULT, 1, 0, 0});
-    ops.push_back(VmOp{PV_OUT, 1, 2, 0});
-    ops.push_back(VmOp{PV_END, 0, 0, 0});
-    Prog p;
-    p.nops = (uint32_t)ops.size(); p.nscratch = 4 + (m.G == 1 ? 1 : 0); p.nconst = 4;
-    int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops); if (rc) return rc;
-    rc = get_pair_consts(ctx, mod_m, &p.d_consts); if (rc) return rc;
-    *out = p;
-    return SC_OK;
-  };
   Prog progs[4];
   const int shapes[4][2] = {{16, 0}, {48, 0}, {0, 8}, {0, 24}};
-  for (int i = 0; i < 4; i++) { int rc = build(shapes[i][0], shapes[i][1], &progs[i]); if (rc) return rc; }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  for (int i = 0; i < 4; i++) {
+    PairBuilder pb(m);
+    pb.loadu(0, 0, nw); pb.mul_const(2); pb.stt(1);
+    for (int k = 0; k < shapes[i][0]; k++) pb.sqr();
+    for (int k = 0; k < shapes[i][1]; k++) pb.mul_tbl(1);
+    pb.out(1, 2);
+    int rc = pb.finalize(ctx, mod_m, &progs[i]); if (rc) return rc;
+    progs[i].muls_per_item = 0; progs[i].pair_sqrs = progs[i].pair_muls = 0;     // probes, not work: nothing to count
+  }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(ctx, SC_ERR_HIP, "pair_op_times: no event"); }
-  const int saved_lat = ctx->latency_mode;
-  const double saved_macs = ctx->mac_counter;
+  LaunchTimer timer(ctx);
+  PolicyOverride keep(ctx);
   // the wave must run on the SAME instance as the launch it stands for: the batch-size policy is told the real batch size by keeping
   // the latency mode out of it (a tiny batch would otherwise pick the small-batch twin)
   ctx->latency_mode = use_latency_config(ctx, m, count) ? 2 : 0;
   const int occ = pvm_occupancy(ctx, G, L, neg1);
   const uint64_t one_wave = std::min<uint64_t>(count, (uint64_t)(64 / G) * (uint64_t)ctx->num_cu * (uint64_t)std::max(1, occ));   // (at most one round)
-  VmExt ex3[3] = {mk_ext(x, x_words, x_words), mk_ext(d_w, wm, wm), mk_ext(d_w1, wm, wm)};
   double ms[4] = {1e30, 1e30, 1e30, 1e30};
-  int rc = SC_OK;
-  for (int rep = 0; rep < 4 && !rc; rep++)          // the first pass loads the code
-    for (int i = 0; i < 4 && !rc; i++) {
-      if (hipEventRecord(e0, ctx->stream) != hipSuccess) { rc = fail(ctx, SC_ERR_HIP, "pair_op_times: event"); break; }
-      rc = run_pvm(ctx, mod_m, progs[i], ex3, 3, one_wave);
-      if (!rc && (hipEventRecord(e1, ctx->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = fail(ctx, SC_ERR_HIP, "pair_op_times: launch failed");
+  for (int rep = 0; rep < 4; rep++)                 // the first pass loads the code
+    for (int i = 0; i < 4; i++) {
       float t = 0;
-      if (!rc && hipEventElapsedTime(&t, e0, e1) == hipSuccess && rep > 0 && t < ms[i]) ms[i] = t;
+      int rc = timer.time([&] { return run_pvm(ctx, mod_m, progs[i], ex3, 3, one_wave); }, &t); if (rc) return rc;
+      if (rep > 0 && t < ms[i]) ms[i] = t;
     }
-  ctx->latency_mode = saved_lat; ctx->mac_counter = saved_macs;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  if (rc) return rc;
   PairOpTimes t;
   t.sqr_ms = std::max(1e-6, (ms[1] - ms[0]) / 32.0);
   t.mul_ms = std::max(1e-6, (ms[3] - ms[2]) / 16.0);
@@ -1588,15 +1617,132 @@ int sc_mod_supports_sq(sc_ctx* ctx, int mod) {
   return pair_twin(ctx, mod) >= 0 ? 1 : 0;
 }
 
+// ---- sc_modexp_shared_sq: x^e mod m^2 with products modulo m only --------------------------------------------------------------
+// Launch 1, the pair exponentiation in the m context: the operand embedded (Horner over chunks of nwords words, LDS constants
+// pair(R^2), pair(B R)), then the window schedule on pairs; leaves the raw pair halves w0, w1 in ext 1, 2.
+static int pair_pow_prog(sc_ctx* ctx, const std::string& key, int mod_m, int exp, int x_words, const Prog** out) {
+  const Mod& m = ctx->mods[mod_m];
+  return cached_prog(ctx, key, mod_m, [&](PairBuilder& pb) -> int {
+    const int nch = (x_words + m.nwords - 1) / m.nwords;
+    const uint32_t TMP_E = 0;                                            // scratch pair entry used while embedding
+    for (int t = nch - 1; t >= 0; t--) {
+      const int nw = std::min(m.nwords, x_words - t * m.nwords);
+      if (t != nch - 1) { pb.mul_const(4); pb.stt(TMP_E); }
+      pb.loadu(0, (uint32_t)(t * m.nwords), (uint32_t)nw);
+      pb.mul_const(2);
+      if (t != nch - 1) pb.addt(TMP_E);
+    }
+    const Exp& ex = ctx->exps[exp];
+    if (ex.bits == 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_shared_sq: zero exponent");
+    emit_window_pow(pb, ex, 1);                                          // table entries 1 .. NT, x^2 at 1 + NT
+    pb.out(1, 2);
+    return SC_OK;
+  }, out, PairBuilder(m));
+}
+
+// Into how many segments launch 1 is cut (1: left whole).
+// A context that shares the chip (concurrent shards, sc_ctx_set_chip_share) runs a SINGLE-ROUND pair launch -- every resident
+// wave holds its one group of items for the whole exponentiation: Alice's rho^N for a shard of 32768 is 2048 waves for 54 ms --
+// in SEGMENTS: the same micro-program cut at window boundaries into a few launches, the pair parked in a row of the slot's
+// table in between (slot = item while there is one round).  Waves of a launch retire together, so nothing another context
+// queues behind such a launch gets a wave slot before it ends: the other shard's short, latency-bound launches (the inversion
+// sweeps of steps 1 and 6 / 7, the assembly launch after ITS pair launch) were seen waiting 26 .. 32 ms each.  With segments
+// they wait for a quarter of that.  Multi-round launches need none of this (their waves retire a round apart).
+// Whether, and into how many segments: from MEASUREMENTS, not from the shape of the launch.  A resident wave holds its slot for
+// hold = (pair squarings x t_sqr + pair products x t_mul) of this program, with the two op times of this kernel instance measured on
+// the device (pair_op_times, once per process and instance: a lone wave, like each of two waves sharing a SIMD, issues one
+// multiply-add per ~9.5 cycles, so its time through the program is the time a round of resident waves takes).  The launch is cut when
+// it would take more than half of the chip's wave slots for that long on a SHARED chip (sc_ctx_set_chip_share), into
+// round(hold / pair_hold_ms) segments; launches of more than pair_max_rounds rounds stay whole (their waves retire a round apart
+// anyway, and every segment boundary costs a drain of the chip).  Both knobs: sc_ctx_set_pair_policy.
+static int pair_segment_count(sc_ctx* ctx, int mod_m, const Prog& prog, uint64_t count, int x_words, const VmExt* ex3, int* out_K) {
+  *out_K = 1;
+  int iG, iL; bool ineg1;
+  pvm_instance(ctx, ctx->mods[mod_m], count, &iG, &iL, &ineg1);
+  const int occ = pvm_occupancy(ctx, iG, iL, ineg1);
+  const uint64_t wave_items = (count + (uint64_t)(64 / iG) - 1) / (uint64_t)(64 / iG);
+  const uint64_t resident = (uint64_t)ctx->num_cu * (uint64_t)std::max(1, occ);
+  const double rounds = (double)wave_items / (double)resident;
+  if (ctx->pair_hold_ms > 0 && ctx->chip_share > 1 && !ctx->stamps && occ > 0 && wave_items * 2 > resident && rounds <= ctx->pair_max_rounds) {
+    double t_sqr = 0, t_mul = 0;
+    int rc = pair_op_times(ctx, mod_m, count, x_words, ex3, &t_sqr, &t_mul); if (rc) return rc;
+    const double hold_ms = prog.pair_sqrs * t_sqr + prog.pair_muls * t_mul;
+    *out_K = (int)std::min(16.0, std::max(1.0, std::floor(hold_ms / ctx->pair_hold_ms + 0.5)));
+  }
+  return SC_OK;
+}
+
+// Launch 1 in K segments, cut from the program's host copy (cached under `key`), each launched on a table slot per item.
+static int run_pair_segments(sc_ctx* ctx, int mod_m, const std::string& key, const Prog& full, int K, const VmExt* ex3, uint64_t count) {
+  auto its = ctx->seg_progs.find(key);
+  if (its == ctx->seg_progs.end()) {
+    if (!full.host_ops) return fail(ctx, SC_ERR_HIP, "sc_modexp_shared_sq: pair program without its host copy (internal error)");
+    const std::vector<VmOp>& ops = *full.host_ops;
+    // cut after a PV_MULT (the end of a window) nearest to each k / K of the op list past the table build
+    std::vector<size_t> mults;
+    size_t body = 0;
+    for (size_t i = 0; i < ops.size(); i++) if ((ops[i].w0 & 0xff) == PV_MULT) mults.push_back(i);
+    for (size_t i = 0; i < ops.size(); i++) if ((ops[i].w0 & 0xff) == PV_SQR && i > 0 && (ops[i - 1].w0 & 0xff) == PV_LOADT) body = i;   // first squaring run after the first window's load
+    std::vector<size_t> cuts;      // index of the first op of segments 1 .. K-1
+    for (int k = 1; k < K; k++) {
+      const size_t target = body + (ops.size() - body) * (size_t)k / (size_t)K;
+      size_t best = 0;
+      for (size_t mi : mults) if (mi + 1 > body && (best == 0 || (mi + 1 > target ? mi + 1 - target : target - mi - 1) < (best > target ? best - target : target - best))) best = mi + 1;
+      if (best > (cuts.empty() ? body : cuts.back()) && best + 1 < ops.size()) cuts.push_back(best);
+    }
+    const uint32_t E = full.nscratch / 2;            // one more pair row of the slot's table: the parked state
+    std::vector<Prog> segs;
+    size_t from = 0;
+    for (size_t c = 0; c <= cuts.size(); c++) {
+      const size_t to = c < cuts.size() ? cuts[c] : ops.size();     // the last segment ends with the program's own PV_OUT, PV_END
+      std::vector<VmOp> so;
+      if (c > 0) so.push_back(pv_op(PV_LOADT, E));
+      so.insert(so.end(), ops.begin() + from, ops.begin() + to);
+      if (c < cuts.size()) { so.push_back(pv_op(PV_STT, E)); so.push_back(pv_op(PV_END)); }
+      Prog sp = full;
+      sp.host_ops.reset();
+      sp.nops = (uint32_t)so.size(); sp.nscratch = full.nscratch + 2;
+      sp.muls_per_item = full.muls_per_item * (double)(to - from) / (double)ops.size();
+      int rc = upload(ctx, so.data(), so.size() * sizeof(VmOp), (void**)&sp.d_ops); if (rc) return rc;
+      segs.push_back(sp);
+      from = to;
+    }
+    its = ctx->seg_progs.emplace(key, segs).first;
+  }
+  ctx->slot_per_item = true;        // a table slot per item: what a segment parks is still there for the next one, whatever the rounds
+  ctx->stat_segmented_launches++; ctx->stat_segments += its->second.size();
+  int rc = SC_OK;
+  for (const Prog& sp : its->second) { rc = run_pvm(ctx, mod_m, sp, ex3, 3, count); if (rc) break; }
+  ctx->slot_per_item = false;
+  return rc;
+}
+
+// Launch 2, in the m^2 context: out = (w0 + w1 m) [* mul_into] mod m^2
+static int pair_assemble(sc_ctx* ctx, int mod_m, int mod_m2, const uint32_t* d_w, const uint32_t* d_w1, int wm, const uint32_t* mul_into,
+                         uint32_t* out, uint64_t count) {
+  int cst_m;
+  int rc = sc_const_create_cached(ctx, mod_m2, ctx->mods[mod_m].n, &cst_m); if (rc) return rc;
+  std::string key = "psq2:" + std::to_string(mod_m2) + ":" + std::to_string(cst_m) + ":" + std::to_string(wm) + ":" + std::to_string(mul_into ? 1 : 0);
+  const Prog* p;
+  rc = cached_prog(ctx, key, mod_m2, [&](Builder& bd) {
+    const int cm = bd.use_const(cst_m);
+    bd.loadw(1, 0, 0, wm); bd.mul_const(cm);           // w1 * m  (mod m^2)
+    bd.addw(0, 0, 0, wm);                              // + w0
+    if (mul_into) { bd.mul_const(0); bd.mul_extw(2); } // to Montgomery form, times the ciphertext
+    bd.storew(3);
+  }, &p); if (rc) return rc;
+  const Mod& m2 = ctx->mods[mod_m2];
+  VmExt ex4[4] = {mk_ext(d_w, wm, wm), mk_ext(d_w1, wm, wm), mk_ext(mul_into, m2.nwords, m2.nwords), mk_ext(out, m2.nwords, m2.nwords)};
+  return run_vm(ctx, mod_m2, *p, ex4, 4, count);
+}
+
 int sc_modexp_shared_sq(sc_ctx* ctx, int mod_m, int mod_m2, int exp, const uint32_t* x, int x_words, const uint32_t* mul_into,
                         uint32_t* out, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   if (!valid_mod(ctx, mod_m) || !valid_mod(ctx, mod_m2) || exp < 0 || exp >= (int)ctx->exps.size() || !x || !out || x_words <= 0)
     return fail(ctx, SC_ERR_ARG, "sc_modexp_shared_sq: bad argument");
-  {
-    const int lat = latency_pair_twin(ctx, mod_m, count);
-    mod_m = lat >= 0 ? lat : pair_twin(ctx, mod_m);
-  }
+  const int lat = latency_pair_twin(ctx, mod_m, count);
+  mod_m = lat >= 0 ? lat : pair_twin(ctx, mod_m);
   if (mod_m < 0) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_modexp_shared_sq: no pair configuration fits this modulus");
   {
     const Mod& m0 = ctx->mods[mod_m];
@@ -1608,167 +1754,22 @@ int sc_modexp_shared_sq(sc_ctx* ctx, int mod_m, int mod_m2, int exp, const uint3
     if (x_words > 4 * m0.nwords) return fail(ctx, SC_ERR_ARG, "sc_modexp_shared_sq: operand wider than 4 chunks");
   }
   // chip-filling batches of a (4,18) / (4,14) / (8,14) modulus: the pair launch runs modulo the multiple M = c m = -1 (mod 2^29),
-  // which needs no quotient multiply; the assembly launch below reduces w0 + w1 M modulo m^2 (m | M)
+  // which needs no quotient multiply; the assembly launch reduces w0 + w1 M modulo m^2 (m | M)
   if (!use_latency_config(ctx, ctx->mods[mod_m], count)) { const int t = neg1_twin(ctx, mod_m); if (t >= 0) mod_m = t; }
-  const Mod& m = ctx->mods[mod_m];
-  const Mod& m2 = ctx->mods[mod_m2];
-  const Exp& ex = ctx->exps[exp];
-  const int wm = m.nwords + 1;                                           // words of the raw pair halves (< 2m + 1)
+  const int wm = ctx->mods[mod_m].nwords + 1;                            // words of the raw pair halves (< 2m + 1)
   uint32_t* d_w;
-  { int rc0 = tmp_buf(ctx, TMP_PAIR, (size_t)count * wm * 4 * 2, (void**)&d_w); if (rc0) return rc0; }
+  int rc = tmp_buf(ctx, TMP_PAIR, (size_t)count * wm * 4 * 2, (void**)&d_w); if (rc) return rc;
   uint32_t* d_w1 = d_w + (size_t)count * wm;
-  // ---- launch 1: pair exponentiation in the m context
-  std::string k1 = "psq:" + std::to_string(mod_m) + ":" + std::to_string(exp) + ":" + std::to_string(x_words);
-  auto it1 = ctx->progs.find(k1);
-  if (it1 == ctx->progs.end()) {
-    std::vector<VmOp> ops;
-    uint32_t nsc = 2;
-    double macs = 0;
-    // multiply-adds: a pair squaring is (a*a part) + 3 S^2; a pair product 5 S^2 with the two-row pass, 6 S^2 in the one-lane
-    // form (three single passes over one staging area)
-    const double S2 = (double)m.S * m.S, SQ = S2 + (double)m.G * m.G * m.L * (m.L + 1) / 2.0 + 2.0 * S2, MU = (m.G == 1 ? 6.0 : 5.0) * S2;
-    auto emit = [&](uint32_t opc, uint32_t w1 = 0, uint32_t w2 = 0, uint32_t w3 = 0) { ops.push_back(VmOp{opc, w1, w2, w3}); };
-    auto touch = [&](uint32_t e) { nsc = std::max(nsc, 2 * e + 2); };
-    // embed the operand: Horner over chunks of nwords words; constants: LDS 2,3 = pair(R^2), 4,5 = pair(B R)
-    const int nch = (x_words + m.nwords - 1) / m.nwords;
-    const uint32_t TMP_E = 0;                                            // scratch pair entry used while embedding
-    for (int t = nch - 1; t >= 0; t--) {
-      const int nw = std::min(m.nwords, x_words - t * m.nwords);
-      if (t != nch - 1) { emit(PV_MULC, 4); macs += MU; emit(PV_STT, TMP_E); touch(TMP_E); }
-      emit(PV_LOADU, 0, 0, ((uint32_t)(t * m.nwords) << 16) | (uint32_t)nw);
-      emit(PV_MULC, 2); macs += MU;
-      if (t != nch - 1) emit(PV_ADDT, TMP_E);
-    }
-    // sliding-window exponentiation on pairs (same schedule as emit_pow_shared)
-    const int bits = ex.bits;
-    if (bits == 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_shared_sq: zero exponent");
-    const int w = best_window(bits), NT = 1 << (w - 1);
-    const uint32_t T0 = 1;                                               // table entries T0 .. T0+NT-1, x^2 at T0+NT
-    emit(PV_STT, T0); touch(T0);
-    if (NT > 1) {
-      emit(PV_SQR); macs += SQ; emit(PV_STT, T0 + NT); touch(T0 + NT);
-      for (int k = 1; k < NT; k++) { emit(PV_LOADT, T0 + k - 1); emit(PV_MULT, T0 + NT); macs += MU; emit(PV_STT, T0 + k); touch(T0 + k); }
-    }
-    bool first = true;
-    int i = bits - 1;
-    while (i >= 0) {
-      if (!ebit(ex.e, i)) { emit(PV_SQR); macs += SQ; i--; continue; }
-      int jj = std::max(0, i - w + 1);
-      while (!ebit(ex.e, jj)) jj++;
-      int v = 0;
-      for (int k = i; k >= jj; k--) v = (v << 1) | ebit(ex.e, k);
-      if (first) { emit(PV_LOADT, T0 + (v - 1) / 2); first = false; }
-      else { for (int k = 0; k < i - jj + 1; k++) { emit(PV_SQR); macs += SQ; } emit(PV_MULT, T0 + (v - 1) / 2); macs += MU; }
-      i = jj - 1;
-    }
-    emit(PV_OUT, 1, 2); macs += 2.0 * S2;
-    emit(PV_END);
-    Prog p;
-    if (m.G == 1) nsc += 1;   // one-lane pair products park an intermediate in a spare row (the last one) of the slot's table
-    p.nops = (uint32_t)ops.size(); p.nscratch = nsc; p.nconst = 4; p.muls_per_item = macs;
-    for (const VmOp& o : ops) {
-      const uint32_t oc = o.w0 & 0xff;
-      if (oc == PV_SQR) p.pair_sqrs++; else if (oc == PV_MULT || oc == PV_MULC) p.pair_muls++;
-    }
-    p.host_ops = std::make_shared<std::vector<VmOp>>(ops);
-    int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops); if (rc) return rc;
-    rc = get_pair_consts(ctx, mod_m, &p.d_consts); if (rc) return rc;
-    it1 = ctx->progs.emplace(k1, p).first;
-  }
-  {
-    VmExt ex3[3] = {mk_ext(x, x_words, x_words), mk_ext(d_w, wm, wm), mk_ext(d_w1, wm, wm)};
-    // A context that shares the chip (concurrent shards, sc_ctx_set_chip_share) runs a SINGLE-ROUND pair launch -- every resident
-    // wave holds its one group of items for the whole exponentiation: Alice's rho^N for a shard of 32768 is 2048 waves for 54 ms --
-    // in SEGMENTS: the same micro-program cut at window boundaries into a few launches, the pair parked in a row of the slot's
-    // table in between (slot = item while there is one round).  Waves of a launch retire together, so nothing another context
-    // queues behind such a launch gets a wave slot before it ends: the other shard's short, latency-bound launches (the inversion
-    // sweeps of steps 1 and 6 / 7, the assembly launch after ITS pair launch) were seen waiting 26 .. 32 ms each.  With segments
-    // they wait for a quarter of that.  Multi-round launches need none of this (their waves retire a round apart).
-    // Whether, and into how many segments: from MEASUREMENTS, not from the shape of the launch.  A resident wave holds its slot for
-    // hold = (pair squarings x t_sqr + pair products x t_mul) of this program, with the two op times of this kernel instance measured on
-    // the device (pair_op_times, once per process and instance: a lone wave, like each of two waves sharing a SIMD, issues one
-    // multiply-add per ~9.5 cycles, so its time through the program is the time a round of resident waves takes).  The launch is cut when
-    // it would take more than half of the chip's wave slots for that long on a SHARED chip (sc_ctx_set_chip_share), into
-    // round(hold / pair_hold_ms) segments; launches of more than pair_max_rounds rounds stay whole (their waves retire a round apart
-    // anyway, and every segment boundary costs a drain of the chip).  Both knobs: sc_ctx_set_pair_policy.
-    int iG, iL; bool ineg1;
-    pvm_instance(ctx, m, count, &iG, &iL, &ineg1);
-    const int occ = pvm_occupancy(ctx, iG, iL, ineg1);
-    const uint64_t wave_items = (count + (uint64_t)(64 / iG) - 1) / (uint64_t)(64 / iG);
-    const uint64_t resident = (uint64_t)ctx->num_cu * (uint64_t)std::max(1, occ);
-    const double rounds = (double)wave_items / (double)resident;
-    int K = 1;
-    if (ctx->pair_hold_ms > 0 && ctx->chip_share > 1 && !ctx->stamps && occ > 0 && wave_items * 2 > resident && rounds <= ctx->pair_max_rounds) {
-      double t_sqr = 0, t_mul = 0;
-      int rcc = pair_op_times(ctx, mod_m, count, x, x_words, d_w, d_w1, wm, &t_sqr, &t_mul); if (rcc) return rcc;
-      const double hold_ms = it1->second.pair_sqrs * t_sqr + it1->second.pair_muls * t_mul;
-      K = (int)std::min(16.0, std::max(1.0, std::floor(hold_ms / ctx->pair_hold_ms + 0.5)));
-    }
-    const bool segmented = K > 1;
-    if (!segmented) {
-      int rc = run_pvm(ctx, mod_m, it1->second, ex3, 3, count); if (rc) return rc;
-    } else {
-      std::string ks = k1 + ":seg" + std::to_string(K);
-      auto its = ctx->seg_progs.find(ks);
-      if (its == ctx->seg_progs.end()) {
-        const Prog& full = it1->second;
-        if (!full.host_ops) return fail(ctx, SC_ERR_HIP, "sc_modexp_shared_sq: pair program without its host copy (internal error)");
-        const std::vector<VmOp>& ops = *full.host_ops;
-        // cut after a PV_MULT (the end of a window) nearest to each k / K of the op list past the table build
-        std::vector<size_t> mults;
-        size_t body = 0;
-        for (size_t i = 0; i < ops.size(); i++) if ((ops[i].w0 & 0xff) == PV_MULT) mults.push_back(i);
-        for (size_t i = 0; i < ops.size(); i++) if ((ops[i].w0 & 0xff) == PV_SQR && i > 0 && (ops[i - 1].w0 & 0xff) == PV_LOADT) body = i;   // first squaring run after the first window's load
-        std::vector<size_t> cuts;      // index of the first op of segments 1 .. K-1
-        for (int k = 1; k < K; k++) {
-          const size_t target = body + (ops.size() - body) * (size_t)k / (size_t)K;
-          size_t best = 0;
-          for (size_t mi : mults) if (mi + 1 > body && (best == 0 || (mi + 1 > target ? mi + 1 - target : target - mi - 1) < (best > target ? best - target : target - best))) best = mi + 1;
-          if (best > (cuts.empty() ? body : cuts.back()) && best + 1 < ops.size()) cuts.push_back(best);
-        }
-        const uint32_t E = full.nscratch / 2;            // one more pair row of the slot's table: the parked state
-        std::vector<Prog> segs;
-        size_t from = 0;
-        for (size_t c = 0; c <= cuts.size(); c++) {
-          const size_t to = c < cuts.size() ? cuts[c] : ops.size();     // the last segment ends with the program's own PV_OUT, PV_END
-          std::vector<VmOp> so;
-          if (c > 0) so.push_back(VmOp{PV_LOADT, E, 0, 0});
-          so.insert(so.end(), ops.begin() + from, ops.begin() + to);
-          if (c < cuts.size()) { so.push_back(VmOp{PV_STT, E, 0, 0}); so.push_back(VmOp{PV_END, 0, 0, 0}); }
-          Prog sp = full;
-          sp.host_ops.reset();
-          sp.nops = (uint32_t)so.size(); sp.nscratch = full.nscratch + 2;
-          sp.muls_per_item = full.muls_per_item * (double)(to - from) / (double)ops.size();
-          int rc = upload(ctx, so.data(), so.size() * sizeof(VmOp), (void**)&sp.d_ops); if (rc) return rc;
-          segs.push_back(sp);
-          from = to;
-        }
-        its = ctx->seg_progs.emplace(ks, segs).first;
-      }
-      ctx->slot_per_item = true;        // a table slot per item: what a segment parks is still there for the next one, whatever the rounds
-      ctx->stat_segmented_launches++; ctx->stat_segments += its->second.size();
-      int rcs = SC_OK;
-      for (const Prog& sp : its->second) { rcs = run_pvm(ctx, mod_m, sp, ex3, 3, count); if (rcs) break; }
-      ctx->slot_per_item = false;
-      if (rcs) return rcs;
-    }
-  }
-  // ---- launch 2 (m^2 context): out = (w0 + w1 m) [* mul_into] mod m^2
-  int cst_m;
-  { int rc = sc_const_create_cached(ctx, mod_m2, m.n, &cst_m); if (rc) return rc; }
-  std::string k2 = "psq2:" + std::to_string(mod_m2) + ":" + std::to_string(cst_m) + ":" + std::to_string(wm) + ":" + std::to_string(mul_into ? 1 : 0);
-  auto it2 = ctx->progs.find(k2);
-  if (it2 == ctx->progs.end()) {
-    Builder bd; const int cm = bd.use_const(cst_m);
-    bd.loadw(1, 0, 0, wm); bd.mul_const(cm);           // w1 * m  (mod m^2)
-    bd.addw(0, 0, 0, wm);                              // + w0
-    if (mul_into) { bd.mul_const(0); bd.mul_extw(2); } // to Montgomery form, times the ciphertext
-    bd.storew(3); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m2, bd, &p); if (rc) return rc;
-    it2 = ctx->progs.emplace(k2, p).first;
-  }
-  VmExt ex4[4] = {mk_ext(d_w, wm, wm), mk_ext(d_w1, wm, wm), mk_ext(mul_into, m2.nwords, m2.nwords), mk_ext(out, m2.nwords, m2.nwords)};
-  return run_vm(ctx, mod_m2, it2->second, ex4, 4, count);
+  const std::string key = "psq:" + std::to_string(mod_m) + ":" + std::to_string(exp) + ":" + std::to_string(x_words);
+  const Prog* prog;
+  rc = pair_pow_prog(ctx, key, mod_m, exp, x_words, &prog); if (rc) return rc;
+  const VmExt ex3[3] = {mk_ext(x, x_words, x_words), mk_ext(d_w, wm, wm), mk_ext(d_w1, wm, wm)};
+  int K;
+  rc = pair_segment_count(ctx, mod_m, *prog, count, x_words, ex3, &K); if (rc) return rc;
+  if (K > 1) rc = run_pair_segments(ctx, mod_m, key + ":seg" + std::to_string(K), *prog, K, ex3, count);
+  else rc = run_pvm(ctx, mod_m, *prog, ex3, 3, count);
+  if (rc) return rc;
+  return pair_assemble(ctx, mod_m, mod_m2, d_w, d_w1, wm, mul_into, out, count);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1949,22 +1950,20 @@ int sc_rng_permutations(sc_ctx* ctx, int k, int64_t* out, uint64_t count) {
 
 int sc_peak_probe(sc_ctx* ctx, double* out_mac_per_s) {
   if (!ctx || !out_mac_per_s) return SC_ERR_ARG;
-  uint32_t* d_out;
+  DevBuf<uint32_t> d_out;
   const int grid = ctx->num_cu * 8;
-  HIPCHK(ctx, hipMalloc((void**)&d_out, (size_t)grid * 256 * 4));
-  hipEvent_t e0, e1; HIPCHK(ctx, hipEventCreate(&e0)); HIPCHK(ctx, hipEventCreate(&e1));
+  HIPCHK(ctx, hipMalloc((void**)&d_out.p, (size_t)grid * 256 * 4));
+  LaunchTimer timer(ctx);
   const int iters = 40000;
   double best = 0;
   for (int rep = 0; rep < 4; rep++) {
-    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-    if (launch_peak_probe(ctx->stream, grid, d_out, 12345u, 67890u, iters)) return fail(ctx, SC_ERR_HIP, "sc_peak_probe: launch failed");
-    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
+    float ms = 0;
+    int rc = timer.time([&] {
+      return launch_peak_probe(ctx->stream, grid, d_out.p, 12345u, 67890u, iters) ? fail(ctx, SC_ERR_HIP, "sc_peak_probe: launch failed") : SC_OK;
+    }, &ms); if (rc) return rc;
     double rate = (double)grid * 256 * (double)iters * 8 / (ms * 1e-3);
     if (rep > 0 && rate > best) best = rate;
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d_out);
   *out_mac_per_s = best;
   return SC_OK;
 }
@@ -1976,18 +1975,15 @@ int sc_table_traffic_probe(sc_ctx* ctx, int mod, const uint32_t* x, uint32_t* ou
   const Mod& m = ctx->mods[mod];
   if (out_row_limbs) *out_row_limbs = m.S;
   std::string key = "tprobe:" + std::to_string(mod) + ":" + std::to_string(entries) + ":" + std::to_string(reads);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd;
+  const Prog* p;
+  int rc = cached_prog(ctx, key, mod, [&](Builder& bd) {
     bd.loadw(0); bd.mul_const(0);                                   // x in Montgomery form
     for (int e = 0; e < entries; e++) bd.stt((uint32_t)e);          // `entries` rows written
     for (int r = 0; r < reads; r++) bd.loadt_tbl((uint32_t)((r * 7 + 3) % entries));   // `reads` rows read
-    bd.redc(); bd.storew(1); bd.end();
-    Prog p; int rc = finalize_prog(ctx, m, bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.redc(); bd.storew(1);
+  }, &p); if (rc) return rc;
   VmExt ex[2] = {mk_ext(x, m.nwords, m.nwords), mk_ext(out, m.nwords, m.nwords)};
-  return run_vm(ctx, mod, it->second, ex, 2, count);
+  return run_vm(ctx, mod, *p, ex, 2, count);
 }
 
 int sc_mac_counter(sc_ctx* ctx, int reset, double* out_macs) {

@@ -401,59 +401,52 @@ static int dgk_randomize_impl(sc_ctx* ctx, const DgkKey& k, const uint32_t* c, c
       rc = sc_fixedbase_pow(ctx, k.hq.fbt, r_red, vqw, nullptr, a_q, count); if (rc) return rc;                             // a_q = h^r mod q
     } else {
       const Fbt f = ctx->fbts[k.hq.fbt];
-      const Mod mq = ctx->mods[k.hq.m];
-      std::string key = "fbcrt0:" + std::to_string(k.hq.fbt) + ":" + std::to_string(k.hq.c_g);
-      auto it = ctx->progs.find(key);
-      if (it == ctx->progs.end()) {
-        Builder bd; const int cg = bd.use_const(k.hq.c_g);
+      const Prog* pr;
+      rc = cached_prog(ctx, "fbcrt0:" + std::to_string(k.hq.fbt) + ":" + std::to_string(k.hq.c_g), k.hq.m, [&](Builder& bd) {
+        const int cg = bd.use_const(k.hq.c_g);
         bd.loadt_fbt(0, 0, f.window, 0);
         for (int j = 1; j < f.nwin; j++) bd.mul_fbt(0, j * f.window, f.window, j);
-        bd.emit(OP_MUL, AK_CONSTSEL, 0, 2, (uint32_t)1 | ((uint32_t)cg << 8)); bd.muls++;   // times g mod q where the bit is set
-        bd.redc(); bd.storew(1); bd.end();                                                   // a_q = g^bit h^r mod q
-        Prog pr; rc = finalize_prog(ctx, mq, bd, &pr); if (rc) return rc;
-        it = ctx->progs.emplace(key, pr).first;
-      }
+        bd.mul_constsel(2, 1, cg);                                                           // times g mod q where the bit is set
+        bd.redc(); bd.storew(1);                                                             // a_q = g^bit h^r mod q
+      }, &pr); if (rc) return rc;
       VmExt ex[3] = {mk_ext(r_red, vqw, vqw), mk_ext(a_q, qw, qw), mk_ext(bits, 0, 0)};
-      rc = run_vm(ctx, k.hq.m, it->second, ex, 3, count, f.d_rows); if (rc) return rc;
+      rc = run_vm(ctx, k.hq.m, *pr, ex, 3, count, f.d_rows); if (rc) return rc;
     }
     rc = sc_modexp_shared(ctx, k.hp.m_v, k.exp_one, r, ewords, nullptr, r_red, count); if (rc) return rc;                 // r mod v_p
     {
       const Fbt f = ctx->fbts[k.hp.fbt];
       const Mod mp = ctx->mods[k.hp.m];
       std::string key = "fbcrt1:" + std::to_string(k.hp.fbt) + ":" + std::to_string(k.c_k) + ":" + std::to_string(k.c_negk) + ":" + std::to_string(qw) + (bits ? ":g" + std::to_string(k.hp.c_g) : "");
-      auto it = ctx->progs.find(key);
-      if (it == ctx->progs.end()) {
-        Builder bd; const int ck = bd.use_const(k.c_k), cn = bd.use_const(k.c_negk);
+      const Prog* pr;
+      rc = cached_prog(ctx, key, k.hp.m, [&](Builder& bd) -> int {
+        const int ck = bd.use_const(k.c_k), cn = bd.use_const(k.c_negk);
         int kc = -1;
-        if (qw > mp.nwords) { int cid; rc = get_const_kred(ctx, k.hp.m, &cid); if (rc) return rc; kc = bd.use_const(cid); }
+        if (qw > mp.nwords) { int cid; int rc = get_const_kred(ctx, k.hp.m, &cid); if (rc) return rc; kc = bd.use_const(cid); }
         bd.loadt_fbt(0, 0, f.window, 0);
         for (int j = 1; j < f.nwin; j++) bd.mul_fbt(0, j * f.window, f.window, j);
-        if (bits) { const int cg = bd.use_const(k.hp.c_g); bd.emit(OP_MUL, AK_CONSTSEL, 0, 3, (uint32_t)1 | ((uint32_t)cg << 8)); bd.muls++; }   // times g mod p where the bit is set
+        if (bits) bd.mul_constsel(3, 1, bd.use_const(k.hp.c_g));                          // times g mod p where the bit is set
         bd.redc();                                                                         // a_p = [g^bit] h^r mod p
         bd.mul_const(ck); bd.stt(0);                                                       // a_p k,  k = q^-1 mod p
         if (qw > mp.nwords) emit_load_reduced(ctx, mp, bd, 1, qw, kc); else bd.loadw(1, 0, 0, qw);
         bd.mul_const(cn); bd.addt(0);                                                      // + a_q (p - k)
-        bd.storew(2); bd.end();
-        Prog pr; rc = finalize_prog(ctx, mp, bd, &pr); if (rc) return rc;
-        it = ctx->progs.emplace(key, pr).first;
-      }
+        bd.storew(2);
+        return SC_OK;
+      }, &pr); if (rc) return rc;
       VmExt ex[4] = {mk_ext(r_red, vpw, vpw), mk_ext(a_q, qw, qw), mk_ext(tq, mp.nwords, mp.nwords), mk_ext(bits, 0, 0)};
-      rc = run_vm(ctx, k.hp.m, it->second, ex, bits ? 4 : 3, count, f.d_rows); if (rc) return rc;
+      rc = run_vm(ctx, k.hp.m, *pr, ex, bits ? 4 : 3, count, f.d_rows); if (rc) return rc;
     }
     {
       const Mod mn = ctx->mods[k.mod_n];
       std::string key = "fbcrt2:" + std::to_string(k.mod_n) + ":" + std::to_string(k.c_mq) + ":" + std::to_string(pw) + ":" + std::to_string(qw);
-      auto it = ctx->progs.find(key);
-      if (it == ctx->progs.end()) {
-        Builder bd; const int cm = bd.use_const(k.c_mq);
+      const Prog* pr;
+      rc = cached_prog(ctx, key, k.mod_n, [&](Builder& bd) {
+        const int cm = bd.use_const(k.c_mq);
         bd.loadw(0, 0, 0, pw); bd.mul_const(cm);                                           // q t  (< p q: exact)
         bd.addw(1, 0, 0, qw);                                                              // + a_q = [g^bit] h^r mod n
-        bd.storew(2); bd.end();
-        Prog pr; rc = finalize_prog(ctx, mn, bd, &pr); if (rc) return rc;
-        it = ctx->progs.emplace(key, pr).first;
-      }
+        bd.storew(2);
+      }, &pr); if (rc) return rc;
       VmExt ex[3] = {mk_ext(tq, pw, pw), mk_ext(a_q, qw, qw), mk_ext(out, mn.nwords, mn.nwords)};
-      return run_vm(ctx, k.mod_n, it->second, ex, 3, count);
+      return run_vm(ctx, k.mod_n, *pr, ex, 3, count);
     }
   } else {
     uint32_t *r_red, *part_p, *part_q;
@@ -528,22 +521,19 @@ int sc_initiator_step1(sc_ctx* ctx, int paillier_key_id, int l, const uint32_t* 
   uint32_t* dst = z_out;
   if (!fused_out) { rc = tmp_words(ctx, TMP_S_G, count * 2 * k.nw, &t); if (rc) return rc; dst = t; }
   const int w2 = ctx->mods[k.mod_n2].nwords;
-  std::string key = "step1:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n) + (ready ? ":r" : "");
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd; const int cn = bd.use_const(k.cst_n);
+  const Prog* p;
+  rc = cached_prog(ctx, "step1:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n) + (ready ? ":r" : ""), k.mod_n2, [&](Builder& bd) {
+    const int cn = bd.use_const(k.cst_n);
     bd.loadw(0); bd.mul_const(0); bd.mul_extw(1);        // [[y]] [[x]]^-1
     bd.mul_const(0); bd.stt(0);                          // ... in Montgomery form
-    bd.loadw(2, 0, 0, k.nw + 1); bd.mul_const(cn); bd.emit(OP_ADD1);   // [[2^l + r]] = 1 + (2^l + r) N  (mod N^2)
+    bd.loadw(2, 0, 0, k.nw + 1); bd.mul_const(cn); bd.add1();          // [[2^l + r]] = 1 + (2^l + r) N  (mod N^2)
     bd.mul_tbl(0);
     if (ready) { bd.mul_const(0); bd.mul_extw(4); }      // times rho_z^N
-    bd.storew(3); bd.end();
-    Prog p; rc = finalize_prog(ctx, ctx->mods[k.mod_n2], bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.storew(3);
+  }, &p); if (rc) return rc;
   VmExt ex[5] = {mk_ext(y_enc, w2, w2), mk_ext(xinv, w2, w2), mk_ext(m1, k.nw + 1, k.nw + 1),
                  mk_ext(dst, w2, w2), mk_ext(ready ? rho_z : nullptr, w2, w2)};
-  rc = run_vm(ctx, k.mod_n2, it->second, ex, 5, count); if (rc) return rc;
+  rc = run_vm(ctx, k.mod_n2, *p, ex, 5, count); if (rc) return rc;
   if (fused_out) return SC_OK;
   return sc_paillier_randomize(ctx, paillier_key_id, t, rho_z, z_out, count);                                         // .randomize() (:109)
 }
@@ -622,18 +612,15 @@ int sc_keyholder_step2_4b(sc_ctx* ctx, int paillier_key_id, int dgk_key_id, int 
     return sc_modmul_const_sel(ctx, d.mod_n, r_rand, -1, d.cst_g, bits, d_beta_out, items);
   if (r_rand) return dgk_randomize_impl(ctx, d, nullptr, bits, r_rand, r_words, d_beta_out, items);
   // unrandomized: g^bit -- the residue 1 times (1 or g), chosen per item inside the launch
-  std::string key = "bits1:" + std::to_string(d.mod_n) + ":" + std::to_string(d.cst_g);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd; const int cg = bd.use_const(d.cst_g);
+  const Prog* pr;
+  rc = cached_prog(ctx, "bits1:" + std::to_string(d.mod_n) + ":" + std::to_string(d.cst_g), d.mod_n, [&](Builder& bd) {
+    const int cg = bd.use_const(d.cst_g);
     bd.loadt_const(1);
-    bd.emit(OP_MUL, AK_CONSTSEL, 0, 1, (uint32_t)1 | ((uint32_t)cg << 8)); bd.muls++;
-    bd.redc(); bd.storew(0); bd.end();
-    Prog pr; rc = finalize_prog(ctx, ctx->mods[d.mod_n], bd, &pr); if (rc) return rc;
-    it = ctx->progs.emplace(key, pr).first;
-  }
+    bd.mul_constsel(1, 1, cg);
+    bd.redc(); bd.storew(0);
+  }, &pr); if (rc) return rc;
   VmExt ex[2] = {mk_ext(d_beta_out, d.nw, d.nw), mk_ext(bits, 0, 0)};
-  return run_vm(ctx, d.mod_n, it->second, ex, 2, items);
+  return run_vm(ctx, d.mod_n, *pr, ex, 2, items);
 }
 
 int sc_keyholder_step4j_5(sc_ctx* ctx, int paillier_key_id, int dgk_key_id, int l, const uint32_t* c_enc, const uint32_t* zeta1,
@@ -662,18 +649,15 @@ int sc_keyholder_step4j_5(sc_ctx* ctx, int paillier_key_id, int dgk_key_id, int 
   rc = sc_paillier_encrypt_raw(ctx, p.mod_n2, p.cst_n, zeta1, p.nw, enc, count); if (rc) return rc;
   rc = sc_paillier_encrypt_raw(ctx, p.mod_n2, p.cst_n, zeta2, p.nw, enc + blk, count); if (rc) return rc;
   {
-    std::string key = "encflag:" + std::to_string(p.mod_n2) + ":" + std::to_string(p.cst_n);
-    auto it = ctx->progs.find(key);
-    if (it == ctx->progs.end()) {
-      Builder bd; const int c = bd.use_const(p.cst_n);
-      bd.emit(OP_TAKEFLAG, 0, 0, 0, 1); bd.mul_const(c);       // delta_B N
-      bd.emit(OP_ADD1); bd.storew(2); bd.end();
-      Prog pr; rc = finalize_prog(ctx, ctx->mods[p.mod_n2], bd, &pr); if (rc) return rc;
-      it = ctx->progs.emplace(key, pr).first;
-    }
+    const Prog* pr;
+    rc = cached_prog(ctx, "encflag:" + std::to_string(p.mod_n2) + ":" + std::to_string(p.cst_n), p.mod_n2, [&](Builder& bd) {
+      const int c = bd.use_const(p.cst_n);
+      bd.takeflag(0, 1); bd.mul_const(c);                     // delta_B N
+      bd.add1(); bd.storew(2);
+    }, &pr); if (rc) return rc;
     const int w2 = 2 * p.nw;
     VmExt ex[3] = {mk_ext(acc, 2, 2), mk_ext(delta_b_out, 2, 2), mk_ext(enc + 2 * blk, w2, w2)};
-    rc = run_vm(ctx, p.mod_n2, it->second, ex, 3, count); if (rc) return rc;
+    rc = run_vm(ctx, p.mod_n2, *pr, ex, 3, count); if (rc) return rc;
     dirty.armed = false;
   }
   if (!rho3) return SC_OK;                                                                                             // unrandomized
@@ -699,23 +683,20 @@ int sc_initiator_step67(sc_ctx* ctx, int paillier_key_id, const uint64_t* delta_
   if (rc) return rc;
   // one launch for the rest: the selections "zeta_1 if r < (N-1)/2 else zeta_2" and "D" are per-item operand choices of the loads,
   // and [[-(r div 2^l)]] [[-1]]^(1 - delta_A) = 1 - (r div 2^l + 1 - delta_A) N  (mod N^2) is one encryption
-  std::string key = "step67:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n);
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    Builder bd; const int cn = bd.use_const(k.cst_n);
+  const Prog* p;
+  rc = cached_prog(ctx, "step67:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {
+    const int cn = bd.use_const(k.cst_n);
     bd.loadw(6, 0, 0, k.nw); bd.add_flag(5, 0, true);                      // r div 2^l + (1 - delta_A)
-    bd.mul_const(cn); bd.emit(OP_NEG); bd.emit(OP_ADD1);                   // 1 - (...) N
+    bd.mul_const(cn); bd.neg(); bd.add1();                                 // 1 - (...) N
     bd.mul_const(0); bd.stt(0);
     bd.loadw_sel(0, 1, 4, 0); bd.mul_const(0); bd.stt(1);                  // [[zeta]]  (SC/initiator.py:558-560)
     bd.loadw_sel(2, 3, 5, 0); bd.mul_const(0);                             // D: [[delta_B]]^-1 where delta_A = 1 (:529-531)
     bd.mul_tbl(1); bd.mul_tbl(0);
-    bd.redc(); bd.storew(7); bd.end();
-    Prog p; rc = finalize_prog(ctx, ctx->mods[k.mod_n2], bd, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
+    bd.redc(); bd.storew(7);
+  }, &p); if (rc) return rc;
   VmExt ex[8] = {mk_ext(zeta1_enc, w2, w2), mk_ext(zeta2_enc, w2, w2), mk_ext(inv, w2, w2), mk_ext(delta_b_enc, w2, w2),
                  mk_ext(rsmall, 2, 2), mk_ext(delta_a, 2, 2), mk_ext(rshift, k.nw, k.nw), mk_ext(out, w2, w2)};
-  return run_vm(ctx, k.mod_n2, it->second, ex, 8, count);
+  return run_vm(ctx, k.mod_n2, *p, ex, 8, count);
 }
 
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {
@@ -726,26 +707,22 @@ int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64
     return fail(ctx, SC_ERR_ARG, "sc_clock_probe: needs a public Paillier key with pair arithmetic (the dominant launch)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t max_waves = (size_t)ctx->num_cu * 16;
-  uint64_t* d_st = nullptr; uint32_t* d_out = nullptr;
-  HIPCHK(ctx, hipMalloc((void**)&d_st, max_waves * 4 * sizeof(uint64_t)));
-  if (hipMalloc((void**)&d_out, (size_t)count * 2 * k.nw * 4) != hipSuccess) { (void)hipFree(d_st); return fail(ctx, SC_ERR_HIP, "sc_clock_probe: out of memory"); }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-  (void)hipMemsetAsync(d_st, 0, max_waves * 4 * sizeof(uint64_t), ctx->stream);
-  ctx->stamps = d_st; ctx->stamp_grid = 0;
-  const double saved_macs = ctx->mac_counter;
-  (void)hipEventRecord(e0, ctx->stream);
-  int rc = sc_paillier_randomize(ctx, paillier_key_id, nullptr, rho, d_out, count);
-  (void)hipEventRecord(e1, ctx->stream);
-  ctx->stamps = nullptr; ctx->mac_counter = saved_macs;
-  const uint32_t grid = ctx->stamp_grid;
-  std::vector<uint64_t> st((size_t)grid * 4);
-  if (!rc && grid == 0) rc = fail(ctx, SC_ERR_UNSUPPORTED, "sc_clock_probe: this batch did not take the (4,18) modulus-multiple pair launch");
-  if (!rc && hipMemcpyAsync(st.data(), d_st, st.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, SC_ERR_HIP, "sc_clock_probe: copy failed");
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = fail(ctx, SC_ERR_HIP, "sc_clock_probe: launch failed");
-  float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d_st); (void)hipFree(d_out);
+  DevBuf<uint64_t> d_st; DevBuf<uint32_t> d_out;
+  HIPCHK(ctx, hipMalloc((void**)&d_st.p, max_waves * 4 * sizeof(uint64_t)));
+  if (hipMalloc((void**)&d_out.p, (size_t)count * 2 * k.nw * 4) != hipSuccess) return fail(ctx, SC_ERR_HIP, "sc_clock_probe: out of memory");
+  LaunchTimer timer(ctx);
+  (void)hipMemsetAsync(d_st.p, 0, max_waves * 4 * sizeof(uint64_t), ctx->stream);
+  PolicyOverride keep(ctx);                                      // the probe's launches stay out of the MAC counter
+  ctx->stamps = d_st.p; ctx->stamp_grid = 0;
+  float ms = 0;
+  const int rc = timer.time([&] { return sc_paillier_randomize(ctx, paillier_key_id, nullptr, rho, d_out.p, count); }, &ms);
+  ctx->stamps = nullptr;
   if (rc) return rc;
+  const uint32_t grid = ctx->stamp_grid;
+  if (grid == 0) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_clock_probe: this batch did not take the (4,18) modulus-multiple pair launch");
+  std::vector<uint64_t> st((size_t)grid * 4);
+  HIPCHK(ctx, hipMemcpyAsync(st.data(), d_st.p, st.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   int rate_khz = 0;                                              // rate of s_memrealtime
   if (hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || rate_khz <= 0) rate_khz = 100000;
   double sum = 0; uint64_t used = 0;
