@@ -106,6 +106,15 @@ int sc_modexp_shared(sc_ctx* ctx, int mod, int exp, const uint32_t* x_dptr, int 
 int sc_modexp_shared_sq(sc_ctx* ctx, int mod_m, int mod_m2, int exp, const uint32_t* x_dptr, int x_words,
                         const uint32_t* mul_into_dptr /* nullable */, uint32_t* out_dptr, uint64_t count);
 int sc_mod_supports_sq(sc_ctx* ctx, int mod);
+/* out[i] = prod_j x_j[i]^(e_j[i]) [* mul_into[i]] mod m^2, j < nbases (1 .. 3), with exponents PER ROW: the pair arithmetic of
+ * sc_modexp_shared_sq driven by an interleaved fixed-window schedule whose products pick their table entry from the item's own
+ * exponent bits (the batched twin of ct * k, and the exponentiations of a secure selection).  x: [nbases][count][x_words],
+ * x_words <= 4 * words(mod_m); e: [nbases][count][ewords], bits at or above ebits ignored (ebits = 0: out = 1 [* mul_into]);
+ * out / mul_into: [count][2 * words(mod_m)].  mod_m2 must be registered for m^2.  SC_ERR_UNSUPPORTED where
+ * sc_mod_supports_sq(mod_m) is 0 or the modulus's pair configuration has no per-row instance (Paillier N of 1024, 2048 and
+ * 3072 bits have one): compose sc_modexp_var on mod_m2 with sc_modmul then. */
+int sc_modexp_var_sq(sc_ctx* ctx, int mod_m, int mod_m2, int nbases, const uint32_t* x_dptr, int x_words, const uint32_t* e_dptr,
+                     int ewords, int ebits, const uint32_t* mul_into_dptr /* nullable */, uint32_t* out_dptr, uint64_t count);
 /* flags[i] = (x[i]^e mod n == 1): DGK.is_zero, SC/keyholder.py:249 (e = v_p, n = p). */
 int sc_modexp_shared_isone(sc_ctx* ctx, int mod, int exp, const uint32_t* x_dptr, int x_words,
                            uint8_t* flags_dptr, uint64_t count);
@@ -173,6 +182,22 @@ int sc_plain_alice(sc_ctx* ctx, const uint32_t* r_dptr, const uint32_t* n_hptr, 
  * uint64 per item. */
 int sc_plain_bob(sc_ctx* ctx, const uint32_t* z_dptr, const uint32_t* n_hptr, int nw, int l, uint64_t count,
                  uint64_t* beta_dptr, uint64_t* dbit_dptr, uint32_t* zeta1_dptr, uint32_t* zeta2_dptr);
+
+/* ---- secure selection ("Secure selection"): the plaintext-word halves of the two players -------------- */
+/* Layout of the packed plaintext of P = [[delta]] prod_j [[d_j]]^(2^off_j) (1 + R N) rho^N, low bits first: a = delta + r_a in
+ * [0, s), s = kappa + 1, then field j = d_j + r_b_j (d_j < 2^(widths[j] + 1)) of widths[j] + kappa + 2 bits; nfields <= 4,
+ * 1 <= kappa <= 62.  Both calls return SC_ERR_ARG when the fields, or one product a * b_j, would not fit below N (n_hptr, nw words).
+ * sc_select_prep (initiator): from r_a [count][aw] (aw <= 2, r_a < 2^kappa) and r_b [nfields][count][bw]: R = r_a + sum_j
+ * 2^off_j r_b_j [count][nw], e_j = r_b_j + 2^widths[j] [nfields][count][ew], rab_j = r_a r_b_j [nfields][count][nw]. */
+int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr,
+                   const uint32_t* r_a_dptr, int aw, const uint32_t* r_b_dptr, int bw, int ew, uint32_t* R_dptr, uint32_t* e_dptr,
+                   uint32_t* rab_dptr, uint64_t count);
+/* sc_select_split (key holder): from the decrypted P [count][nw]: prod_j = a * b_j [nfields][count][nw].  *bad_dptr (one uint32,
+ * not cleared here) is set to 1 when a row has a bit at or above the end of the last field: the initiator packed a WIDER layout
+ * than the one given here.  A narrower one cannot be detected from P; the two players' layouts must be compared as well
+ * (selection.py announces it in the message that carries P). */
+int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr,
+                    const uint32_t* p_dptr, uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
 
 /* ---- fused Initiator steps 4c-4h (SC/initiator.py:272-485) --------------------------------------- */
 /* Inputs, all bit-major: beta[l][count][nw], beta_inv[l][count][nw], d[count][nw], d_inv[count][nw]

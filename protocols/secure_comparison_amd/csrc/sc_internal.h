@@ -168,6 +168,7 @@ struct Prog {
   double sqrs_per_item = 0;   // squarings (a*a part costs L(L+1)/2 per block instead of L^2)
   std::shared_ptr<std::vector<VmOp>> host_ops;   // the micro-ops on the host (pair programs: cut into segments on demand)
   uint32_t pair_sqrs = 0, pair_muls = 0;         // pair programs: pair squarings / pair products per item (the hold-time model)
+  bool pair_dig = false;                         // pair programs with PV_MULTDIG: run on the k_pvm<.., DIG> instances
 };
 
 }  // namespace
@@ -209,6 +210,7 @@ struct sc_ctx {
   std::map<int, int> neg1_twins;                            // (4,18) mod n -> context of the multiple M = c n = -1 (mod 2^29)
   std::map<int, int> latency_pair_twins;                    // mod -> context of the same modulus in the (16,5) / (8,5) small-batch pair configuration
   std::map<int, uint32_t*> pair_consts;                     // mod -> 4 limb arrays: pair(R^2), pair(B R) for the pair arithmetic
+  uint32_t* d_one = nullptr;                                // the word 1 (a broadcast operand: the table entry x^0 of sc_modexp_var_sq)
   RngKey rng_key;                                           // ChaCha20 key of the context's generator (sc_rng_seed)
   // fork / join inside one library call (AuxFork): independent halves of a small batch -- the p- and q-side of the key holder's CRT
   // -- run on a second stream of the context with its own scratch arena and temporaries
@@ -247,6 +249,10 @@ int launch_vm_part2(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArg
 int launch_pvm_part0(sc_ctx* ctx, int G, int L, bool neg1, bool stamp, const sc::VmArgs& a);
 int launch_pvm_part1(sc_ctx* ctx, int G, int L, bool neg1, bool stamp, const sc::VmArgs& a);
 int launch_pvm_part2(sc_ctx* ctx, int G, int L, bool neg1, bool stamp, const sc::VmArgs& a);
+// the instances that also run PV_MULTDIG (per-row exponents); SC_ERR_UNSUPPORTED when (G, L) has none in that part
+int launch_pvm_dig_part0(sc_ctx* ctx, int G, int L, const sc::VmArgs& a);
+int launch_pvm_dig_part1(sc_ctx* ctx, int G, int L, const sc::VmArgs& a);
+int launch_pvm_dig_part2(sc_ctx* ctx, int G, int L, const sc::VmArgs& a);
 // resident waves per CU of that pair kernel instance (occupancy query, cached in the context); <= 0 when the instance lives elsewhere
 int pvm_occupancy_part0(sc_ctx* ctx, int G, int L, bool neg1);
 int pvm_occupancy_part1(sc_ctx* ctx, int G, int L, bool neg1);
@@ -257,6 +263,9 @@ int launch_plain_alice(hipStream_t stream, const uint32_t* r, const uint32_t* nm
                        uint64_t* alpha, uint64_t* alpha_tilde, uint64_t* rsmall, uint32_t* rshift);
 int launch_plain_bob(hipStream_t stream, const uint32_t* z, const uint32_t* nmod, const uint32_t* halfn, int nw, int l, uint64_t count, uint64_t* beta,
                      uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2, uint8_t* bits);
+int launch_select_prep(hipStream_t stream, const uint32_t* ra, int aw, const uint32_t* rb, int bw, const sc::SelLayout& lay, int nw, int ew,
+                       uint64_t count, uint32_t* R, uint32_t* e, uint32_t* rab);
+int launch_select_split(hipStream_t stream, const uint32_t* p, int nw, const sc::SelLayout& lay, uint64_t count, uint32_t* prod, uint32_t* bad);
 int launch_rng_bits(hipStream_t stream, const sc::RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count);
 int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, const uint32_t* d_n, int nbits, int nw, int nonzero, uint32_t* out, uint64_t count);
 int launch_rng_coins(hipStream_t stream, const sc::RngKey& key, uint64_t call, uint64_t* out, uint64_t count);

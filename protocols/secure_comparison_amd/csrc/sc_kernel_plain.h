@@ -113,4 +113,95 @@ __global__ void k_plain_bob(const uint32_t* __restrict__ z, const uint32_t* __re
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Secure selection (sc_select_prep / sc_select_split, include/sc_amd_dev.h).  Layout of the packed plaintext of P, low bits first:
+// the field a = delta + r_a in bits [0, s), s = kappa + 1, then field j = d_j + r_b_j in bits [off[j], off[j] + fbits[j]),
+// fbits[j] = width[j] + kappa + 2, off[0] = s, off[j + 1] = off[j] + fbits[j]; everything below the modulus (the host checks).
+// ---------------------------------------------------------------------------------------------
+// (SelLayout: sc_vm.h)
+
+// word k of (x >> bitpos) masked to `bits` bits; x has nw words (0 past its end)
+__device__ __forceinline__ uint32_t sel_field_word(const uint32_t* x, int nw, int bitpos, int bits, int k) {
+  const int b = bitpos + 32 * k, q = b >> 5, sh = b & 31;
+  if (32 * k >= bits) return 0u;
+  uint32_t v = (q < nw) ? (x[q] >> sh) : 0u;
+  if (sh && q + 1 < nw) v |= x[q + 1] << (32 - sh);
+  const int left = bits - 32 * k;
+  return left >= 32 ? v : (v & ((1u << left) - 1u));
+}
+// word k of (x << bitpos); x has xw words
+__device__ __forceinline__ uint32_t sel_shl_word(const uint32_t* x, int xw, int bitpos, int k) {
+  const int q = k - (bitpos >> 5), sh = bitpos & 31;
+  uint32_t v = (q >= 0 && q < xw) ? (x[q] << sh) : 0u;
+  if (sh && q - 1 >= 0 && q - 1 < xw) v |= x[q - 1] >> (32 - sh);
+  return v;
+}
+// out[0 .. nw) = a * b mod 2^(32 nw), a < 2^64, b of bw words
+__device__ __forceinline__ void sel_mul64(uint64_t a, const uint32_t* b, int bw, uint32_t* out, int nw) {
+  const uint64_t alo = a & 0xffffffffu, ahi = a >> 32;
+  uint64_t carry = 0;
+  for (int k = 0; k < nw; k++) {
+    const uint64_t p1 = (k < bw) ? (uint64_t)b[k] * alo : 0u;
+    const uint64_t p2 = (k >= 1 && k - 1 < bw) ? (uint64_t)b[k - 1] * ahi : 0u;
+    const uint64_t lo = (p1 & 0xffffffffu) + (p2 & 0xffffffffu) + (carry & 0xffffffffu);
+    carry = (p1 >> 32) + (p2 >> 32) + (carry >> 32) + (lo >> 32);
+    out[k] = (uint32_t)lo;
+  }
+}
+
+// The initiator's plaintext values of a selection from her draws r_a [count][aw] (< 2^kappa) and r_b [nf][count][bw]:
+//   R = r_a + sum_j 2^off[j] r_b_j ([count][nw]), e_j = r_b_j + 2^width[j] ([nf][count][ew]), rab_j = r_a r_b_j ([nf][count][nw]).
+__global__ void k_select_prep(const uint32_t* __restrict__ ra, int aw, const uint32_t* __restrict__ rb, int bw, SelLayout lay, int nw,
+                              int ew, uint64_t count, uint32_t* __restrict__ R, uint32_t* __restrict__ e, uint32_t* __restrict__ rab) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t* a = ra + i * aw;
+  const uint64_t av = (uint64_t)a[0] | (aw > 1 ? (uint64_t)a[1] << 32 : 0u);
+  for (int k = 0; k < nw; k++) {
+    uint32_t v = k < aw ? a[k] : 0u;
+    for (int j = 0; j < lay.nf; j++) v |= sel_shl_word(rb + ((uint64_t)j * count + i) * bw, bw, lay.off[j], k);
+    R[i * nw + k] = v;
+  }
+  for (int j = 0; j < lay.nf; j++) {
+    const uint32_t* b = rb + ((uint64_t)j * count + i) * bw;
+    uint32_t* ej = e + ((uint64_t)j * count + i) * ew;
+    uint32_t carry = 0;
+    for (int k = 0; k < ew; k++) {
+      const uint64_t t = (uint64_t)(k < bw ? b[k] : 0u) + carry + ((k == (lay.width[j] >> 5)) ? (1u << (lay.width[j] & 31)) : 0u);
+      ej[k] = (uint32_t)t;
+      carry = (uint32_t)(t >> 32);
+    }
+    sel_mul64(av, b, bw, rab + ((uint64_t)j * count + i) * nw, nw);
+  }
+}
+
+// The key holder's half: from the decrypted P [count][nw], prod_j = a * b_j ([nf][count][nw]) with a and b_j the fields of P.
+// A P with a bit at or above lay.end sets *bad (the players disagree on kappa or on the widths); its products are still written.
+__global__ void k_select_split(const uint32_t* __restrict__ p, int nw, SelLayout lay, uint64_t count, uint32_t* __restrict__ prod,
+                               uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t* x = p + i * nw;
+  const uint64_t a = (uint64_t)sel_field_word(x, nw, 0, lay.s, 0) | ((uint64_t)sel_field_word(x, nw, 0, lay.s, 1) << 32);
+  uint32_t over = 0;
+  for (int k = lay.end >> 5; k < nw; k++) over |= (k == (lay.end >> 5)) ? (x[k] >> (lay.end & 31)) : x[k];
+  if (over) *bad = 1u;
+  for (int j = 0; j < lay.nf; j++) {
+    uint32_t* o = prod + ((uint64_t)j * count + i) * nw;
+    const int fw = (lay.fbits[j] + 31) >> 5;
+    uint64_t carry = 0;
+    const uint64_t alo = a & 0xffffffffu, ahi = a >> 32;
+    uint32_t prev = 0;
+    for (int k = 0; k < nw; k++) {          // sel_mul64 with b = the field, extracted on the fly
+      const uint32_t bk = k < fw ? sel_field_word(x, nw, lay.off[j], lay.fbits[j], k) : 0u;
+      const uint64_t p1 = (uint64_t)bk * alo, p2 = (uint64_t)prev * ahi;
+      const uint64_t lo = (p1 & 0xffffffffu) + (p2 & 0xffffffffu) + (carry & 0xffffffffu);
+      carry = (p1 >> 32) + (p2 >> 32) + (carry >> 32) + (lo >> 32);
+      o[k] = (uint32_t)lo;
+      prev = bk;
+    }
+  }
+}
+
 }  // namespace sc

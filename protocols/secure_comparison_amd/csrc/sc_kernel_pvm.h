@@ -18,9 +18,11 @@ namespace sc {
 // STAMP: diagnostic twin (sc_clock_probe, never a timed launch): every wave records s_memtime (shader clock) and s_memrealtime
 // (constant-rate clock) at entry and exit in args.stamps[4 * blockIdx.x ..], from which the host derives the engine clock the
 // kernel actually held.
-template <int G, int L, int WB, bool NEG1 = false, bool STAMP = false>
+// DIG: the instances that also run PV_MULTDIG (exponents per row, sc_modexp_var_sq); the others compile without it.
+template <int G, int L, int WB, bool NEG1 = false, bool STAMP = false, bool DIG = false>
 __global__ void __launch_bounds__(64, ((G == 16 && L > 9) ? 1 : SC_PVM_WAVES)) k_pvm(const VmArgs args) {
   using GT = Grp<G, L, WB, NEG1>;
+  static_assert(!DIG || G > 1, "PV_MULTDIG has no one-lane form");
   uint64_t stamp_c0 = 0, stamp_r0 = 0;
   if constexpr (STAMP) { stamp_c0 = __builtin_amdgcn_s_memtime(); stamp_r0 = __builtin_amdgcn_s_memrealtime(); }
   constexpr int S = GT::S, NG = GT::NG, SP = GT::SP, WP = GT::WP;
@@ -145,7 +147,29 @@ __global__ void __launch_bounds__(64, ((G == 16 && L > 9) ? 1 : SC_PVM_WAVES)) k
           gp.store_words((uint32_t*)e1.ptr + idx * e1.stride, e1.nwords, x1, my_a, live);
           break;
         }
-        default: break;
+        default: {
+          if constexpr (DIG) {
+            if (opc == PV_MULTDIG) {
+              const VmExt& e = args.ext[op.w1 & 0xf];
+              const uint32_t bitpos = (op.w1 >> 4) & 0xfffff, width = op.w1 >> 24;
+              const uint32_t* ew = (const uint32_t*)e.ptr + idx * e.stride;
+              const uint32_t w0i = bitpos >> 5, sh = bitpos & 31;
+              uint64_t v = (w0i < e.nwords) ? ew[w0i] : 0u;
+              if (w0i + 1 < e.nwords) v |= (uint64_t)ew[w0i + 1] << 32;
+              const uint32_t digit = (uint32_t)(v >> sh) & ((1u << width) - 1);
+              const uint32_t* src = my_tbl + (uint64_t)(2 * (op.w2 + digit)) * S;
+              SC_WAVE_SYNC();
+#pragma unroll
+              for (int l = 0; l < L; l++) {
+                my_a[gp.j * L + l] = src[gp.j * L + l];
+                my_a2[gp.j * L + l] = src[S + gp.j * L + l];
+              }
+              SC_WAVE_SYNC();
+              gp.pair_mul(x0, x1, my_a, my_a2);
+            }
+          }
+          break;
+        }
       }
     }
   }

@@ -38,6 +38,15 @@ int sc_host::launch_plain_bob(hipStream_t stream, const uint32_t* z, const uint3
   }
   return launched();
 }
+int sc_host::launch_select_prep(hipStream_t stream, const uint32_t* ra, int aw, const uint32_t* rb, int bw, const SelLayout& lay, int nw,
+                                int ew, uint64_t count, uint32_t* R, uint32_t* e, uint32_t* rab) {
+  hipLaunchKernelGGL(k_select_prep, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, ra, aw, rb, bw, lay, nw, ew, count, R, e, rab);
+  return launched();
+}
+int sc_host::launch_select_split(hipStream_t stream, const uint32_t* p, int nw, const SelLayout& lay, uint64_t count, uint32_t* prod, uint32_t* bad) {
+  hipLaunchKernelGGL(k_select_split, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, p, nw, lay, count, prod, bad);
+  return launched();
+}
 int sc_host::launch_rng_bits(hipStream_t stream, const RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count) {
   hipLaunchKernelGGL(k_rng_bits, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, key, call, bits, nw, out, count);
   return launched();

@@ -10,22 +10,22 @@ using namespace sc;
 
 namespace {
 
-template <int G, int L, int WB = 29, bool NEG1 = false, bool STAMP = false>
+template <int G, int L, int WB = 29, bool NEG1 = false, bool STAMP = false, bool DIG = false>
 int pvm_occupancy(sc_ctx* ctx) {
-  const int key = 1000 + 100 * L + G + (NEG1 ? 100000 : 0) + (STAMP ? 200000 : 0);
+  const int key = 1000 + 100 * L + G + (NEG1 ? 100000 : 0) + (STAMP ? 200000 : 0) + (DIG ? 400000 : 0);
   auto it = ctx->occ_cache.find(key);
   if (it != ctx->occ_cache.end()) return it->second;
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_pvm<G, L, WB, NEG1, STAMP>), 64, 0) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_pvm<G, L, WB, NEG1, STAMP, DIG>), 64, 0) != hipSuccess) return 0;
   const int occ = std::max(1, std::min(nb, 16));
   ctx->occ_cache[key] = occ;
   return occ;
 }
 
-template <int G, int L, int WB = 29, bool NEG1 = false, bool STAMP = false>
+template <int G, int L, int WB = 29, bool NEG1 = false, bool STAMP = false, bool DIG = false>
 int launch_pvm_cfg(sc_ctx* ctx, const VmArgs& a) {
   constexpr int NG = 64 / G;
-  const int occ = pvm_occupancy<G, L, WB, NEG1, STAMP>(ctx);
+  const int occ = pvm_occupancy<G, L, WB, NEG1, STAMP, DIG>(ctx);
   if (occ <= 0) return sc_host::fail(ctx, SC_ERR_HIP, "occupancy query failed for k_pvm<%d,%d>", G, L);
   uint64_t need = (a.count + NG - 1) / NG;
   // slot_per_item (segmented launches of more than one round): one wave and one table slot per group of items, so that what a
@@ -35,7 +35,7 @@ int launch_pvm_cfg(sc_ctx* ctx, const VmArgs& a) {
   int rc = sc_host::ensure_scratch(ctx, (size_t)grid * NG * a.nscratch * (G * L) * 4, &args.scratch);
   if (rc) return rc;
   if constexpr (STAMP) { args.stamps = ctx->stamps; ctx->stamp_grid = grid; }
-  hipLaunchKernelGGL((k_pvm<G, L, WB, NEG1, STAMP>), dim3(grid), dim3(64), 0, ctx->stream, args);
+  hipLaunchKernelGGL((k_pvm<G, L, WB, NEG1, STAMP, DIG>), dim3(grid), dim3(64), 0, ctx->stream, args);
   HIPCHK(ctx, hipGetLastError());
   return SC_OK;
 }
@@ -57,6 +57,19 @@ int sc_host::SC_CAT(launch_pvm_part, SC_PART)(sc_ctx* ctx, int G, int L, bool ne
   SC_CASE_NEG1(4, 14) SC_CASE(4, 14) SC_CASE_NEG1(8, 14) SC_CASE(8, 14)
 #endif
   (void)ctx; (void)a; (void)stamp;
+  return SC_ERR_UNSUPPORTED;
+}
+
+// the instances with PV_MULTDIG (sc_modexp_var_sq): the pair configurations of Paillier moduli N -- (2,18) for 1024-bit,
+// (4,18) for 2048-bit, (8,14) for 3072-bit N -- without the latency and n = -1 (mod 2^29) variants
+int sc_host::SC_CAT(launch_pvm_dig_part, SC_PART)(sc_ctx* ctx, int G, int L, const sc::VmArgs& a) {
+#if SC_PART == 0
+  if (G == 2 && L == 18) return launch_pvm_cfg<2, 18, 29, false, false, true>(ctx, a);
+  if (G == 4 && L == 18) return launch_pvm_cfg<4, 18, 29, false, false, true>(ctx, a);
+#elif SC_PART == 2
+  if (G == 8 && L == 14) return launch_pvm_cfg<8, 14, 29, false, false, true>(ctx, a);
+#endif
+  (void)ctx; (void)a; (void)G; (void)L;
   return SC_ERR_UNSUPPORTED;
 }
 

@@ -359,11 +359,16 @@ struct PairBuilder {
   explicit PairBuilder(const Mod& m)
       : one_lane(m.G == 1), S2((double)m.S * m.S), SQ(S2 + (double)m.G * m.G * m.L * (m.L + 1) / 2.0 + 2.0 * S2),
         MU((m.G == 1 ? 6.0 : 5.0) * S2) {}
-  // ACC0 = words ext[ext] (word offset woff, nw words), ACC1 = 0
-  void loadu(int ext, uint32_t woff, uint32_t nw) { ops.push_back(pv_op(PV_LOADU, ext, 0, (woff << 16) | nw)); }
+  // ACC0 = words ext[ext] (row `row` of a [rows][count] operand, word offset woff, nw words), ACC1 = 0
+  void loadu(int ext, uint32_t woff, uint32_t nw, uint32_t row = 0) { ops.push_back(pv_op(PV_LOADU, ext, row, (woff << 16) | nw)); }
   void mul_const(uint32_t lds_idx) { ops.push_back(pv_op(PV_MULC, lds_idx)); macs += MU; muls++; }
   void sqr() { ops.push_back(pv_op(PV_SQR)); macs += SQ; sqrs++; }
   void mul_tbl(uint32_t e) { touch(e); ops.push_back(pv_op(PV_MULT, e)); macs += MU; muls++; }
+  // pair *= entry base + digit, the digit `width` bits at `bitpos` of the item's row in ext (k_pvm<.., DIG> instances only)
+  void mul_tbl_digit(int ext, uint32_t bitpos, uint32_t width, uint32_t base) {
+    touch(base + (1u << width) - 1); dig = true;
+    ops.push_back(pv_op(PV_MULTDIG, ext | (bitpos << 4) | (width << 24), base)); macs += MU; muls++;
+  }
   void loadt_tbl(uint32_t e) { touch(e); ops.push_back(pv_op(PV_LOADT, e)); }
   void stt(uint32_t e) { touch(e); ops.push_back(pv_op(PV_STT, e)); }
   void addt(uint32_t e) { touch(e); ops.push_back(pv_op(PV_ADDT, e)); }
@@ -374,7 +379,7 @@ struct PairBuilder {
     Prog p;
     // one-lane pair products park an intermediate in a spare row (the last one) of the slot's table
     p.nops = (uint32_t)ops.size(); p.nscratch = nscratch + (one_lane ? 1 : 0); p.nconst = 4; p.muls_per_item = macs;
-    p.pair_sqrs = sqrs; p.pair_muls = muls;
+    p.pair_sqrs = sqrs; p.pair_muls = muls; p.pair_dig = dig;
     p.host_ops = std::make_shared<std::vector<VmOp>>(ops);
     int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops); if (rc) return rc;
     rc = get_pair_consts(ctx, mod, &p.d_consts); if (rc) return rc;
@@ -386,6 +391,7 @@ struct PairBuilder {
   bool one_lane;
   double S2, SQ, MU, macs = 0;
   uint32_t nscratch = 2, sqrs = 0, muls = 0;
+  bool dig = false;
   void touch(uint32_t e) { nscratch = std::max(nscratch, 2 * e + 2); }
 };
 
@@ -475,6 +481,13 @@ int run_pvm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, ui
   for (int i = 0; i < next; i++) a.ext[i] = exts[i];
   ctx->mac_counter += (double)count * p.muls_per_item;   // pair programs carry their exact multiply-add count here
   if (!pair_capable(m.G, m.L, m.W)) return fail(ctx, SC_ERR_UNSUPPORTED, "no pair kernel for G=%d L=%d", m.G, m.L);
+  if (p.pair_dig) {      // per-row exponents: the modulus's own instance with PV_MULTDIG (no latency / n = -1 variants of it exist)
+    int rc = launch_pvm_dig_part0(ctx, m.G, m.L, a);
+    if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_dig_part1(ctx, m.G, m.L, a);
+    if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_dig_part2(ctx, m.G, m.L, a);
+    if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no per-row-exponent pair kernel for G=%d L=%d", m.G, m.L);
+    return rc;
+  }
   int G, L; bool neg1;
   pvm_instance(ctx, m, count, &G, &L, &neg1);
   const bool stamp = neg1 && G == 4 && L == 18 && ctx->stamps != nullptr;     // the stamping twin of (4,18,neg1) is sc_clock_probe's diagnostic launch
@@ -1770,6 +1783,128 @@ int sc_modexp_shared_sq(sc_ctx* ctx, int mod_m, int mod_m2, int exp, const uint3
   else rc = run_pvm(ctx, mod_m, *prog, ex3, 3, count);
   if (rc) return rc;
   return pair_assemble(ctx, mod_m, mod_m2, d_w, d_w1, wm, mul_into, out, count);
+}
+
+// ---- sc_modexp_var_sq: prod_j x_j^e_j mod m^2 with exponents per row, products modulo m only -----------------------------------
+// The window that minimises the table build plus the digit products of nb tables of 2^w entries (squarings are ebits whatever w);
+// at most 5 (nb * 32 pair rows of the slot's table).
+static int var_sq_window(int nbases, int ebits) {
+  int best = 1; double bc = 1e30;
+  for (int w = 1; w <= 5; w++) {
+    const double c = nbases * ((double)(1 << w) - 2.0 + std::ceil((double)ebits / w));
+    if (c < bc) { bc = c; best = w; }
+  }
+  return best;
+}
+
+// Interleaved (Shamir) fixed-window schedule of up to three bases with exponents per row: table j holds x_j^0 .. x_j^(2^w - 1) in pair
+// entries T_j .. T_j + 2^w - 1 (x^0 from the word 1 in ext 6), then per window of w exponent bits, top first: w squarings of the
+// shared accumulator and one digit-indexed product per base (PV_MULTDIG on ext 3 + j).  The top window is ebits - (nd - 1) w bits
+// wide, so no exponent bit at or above ebits is read.  Operands x: ext 0 as [nb][count][x_words]; the pair halves go to ext 1, 2.
+static void emit_var_sq_pow(PairBuilder& pb, const Mod& m, int nbases, int x_words, int ebits, int w) {
+  const uint32_t TMP_E = 0, NT = 1u << w;
+  const int nch = (x_words + m.nwords - 1) / m.nwords;
+  pb.loadu(6, 0, 1); pb.mul_const(2);                                    // pair form of 1
+  for (int j = 0; j < nbases; j++) pb.stt(1 + j * NT);
+  for (int j = 0; j < nbases; j++) {
+    const uint32_t T = 1 + j * NT;
+    for (int t = nch - 1; t >= 0; t--) {                                 // x_j embedded (Horner over chunks, as pair_pow_prog)
+      const int nw = std::min(m.nwords, x_words - t * m.nwords);
+      if (t != nch - 1) { pb.mul_const(4); pb.stt(TMP_E); }
+      pb.loadu(0, (uint32_t)(t * m.nwords), (uint32_t)nw, (uint32_t)j);
+      pb.mul_const(2);
+      if (t != nch - 1) pb.addt(TMP_E);
+    }
+    pb.stt(T + 1);
+    for (uint32_t k = 2; k < NT; k++) { pb.mul_tbl(T + 1); pb.stt(T + k); }
+  }
+  const int nd = (ebits + w - 1) / w;
+  pb.loadt_tbl(1);
+  for (int d = nd - 1; d >= 0; d--) {
+    const uint32_t width = (d == nd - 1) ? (uint32_t)(ebits - (nd - 1) * w) : (uint32_t)w;
+    if (d != nd - 1) for (int k = 0; k < w; k++) pb.sqr();
+    for (int j = 0; j < nbases; j++) pb.mul_tbl_digit(3 + j, (uint32_t)(d * w), width, 1 + j * NT);
+  }
+  pb.out(1, 2);
+}
+
+int sc_modexp_var_sq(sc_ctx* ctx, int mod_m, int mod_m2, int nbases, const uint32_t* x, int x_words, const uint32_t* e, int ewords,
+                     int ebits, const uint32_t* mul_into, uint32_t* out, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  if (!valid_mod(ctx, mod_m) || !valid_mod(ctx, mod_m2) || nbases < 1 || nbases > 3 || !x || !e || !out || x_words <= 0 ||
+      ewords <= 0 || ebits < 0 || ebits > 32 * ewords || ebits > (1 << 20) - 64)
+    return fail(ctx, SC_ERR_ARG, "sc_modexp_var_sq: bad argument");
+  mod_m = pair_twin(ctx, mod_m);
+  if (mod_m < 0) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_modexp_var_sq: no pair configuration fits this modulus");
+  {
+    const Mod& m0 = ctx->mods[mod_m];
+    const Mod& m2 = ctx->mods[mod_m2];
+    if (!((m0.G == 2 && m0.L == 18) || (m0.G == 4 && m0.L == 18) || (m0.G == 8 && m0.L == 14)))
+      return fail(ctx, SC_ERR_UNSUPPORTED, "sc_modexp_var_sq: no per-row-exponent pair kernel for G=%d L=%d", m0.G, m0.L);
+    Big sq = big_mul(m0.n, m0.n);
+    sq.resize(std::max(sq.size(), m2.n.size()), 0);
+    Big other = m2.n; other.resize(sq.size(), 0);
+    if (big_cmp(sq, other) != 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_var_sq: mod_m2 is not the square of mod_m");
+    if (x_words > 4 * m0.nwords) return fail(ctx, SC_ERR_ARG, "sc_modexp_var_sq: operand wider than 4 chunks");
+  }
+  if (!ctx->d_one) { const uint32_t one = 1; int rc = upload(ctx, &one, 4, (void**)&ctx->d_one); if (rc) return rc; }
+  const int w = var_sq_window(nbases, ebits);
+  const int wm = ctx->mods[mod_m].nwords + 1;
+  uint32_t* d_w;
+  int rc = tmp_buf(ctx, TMP_PAIR, (size_t)count * wm * 4 * 2, (void**)&d_w); if (rc) return rc;
+  uint32_t* d_w1 = d_w + (size_t)count * wm;
+  const std::string key = "pvsq:" + std::to_string(mod_m) + ":" + std::to_string(nbases) + ":" + std::to_string(ebits) + ":" +
+                          std::to_string(w) + ":" + std::to_string(x_words);
+  const Prog* prog;
+  rc = cached_prog(ctx, key, mod_m, [&](PairBuilder& pb) { emit_var_sq_pow(pb, ctx->mods[mod_m], nbases, x_words, ebits, w); },
+                   &prog, PairBuilder(ctx->mods[mod_m])); if (rc) return rc;
+  VmExt ex[7] = {mk_ext(x, x_words, x_words), mk_ext(d_w, wm, wm), mk_ext(d_w1, wm, wm), mk_ext(e, ewords, ewords),
+                 mk_ext(e, ewords, ewords), mk_ext(e, ewords, ewords), mk_ext(ctx->d_one, 0, 1)};
+  for (int j = 1; j < nbases; j++) ex[3 + j] = mk_ext(e + (size_t)j * count * ewords, ewords, ewords);
+  rc = run_pvm(ctx, mod_m, *prog, ex, 7, count); if (rc) return rc;
+  return pair_assemble(ctx, mod_m, mod_m2, d_w, d_w1, wm, mul_into, out, count);
+}
+
+// ---- secure selection: the plaintext-word halves of the two players (k_select_prep / k_select_split) -------------------------------
+static int select_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int nfields, const int* widths, SelLayout* lay) {
+  if (kappa < 1 || kappa > 62 || nfields < 1 || nfields > SEL_MAX_FIELDS || !widths) return fail(ctx, SC_ERR_ARG, "%s: bad layout", who);
+  lay->s = kappa + 1; lay->nf = nfields;
+  int off = lay->s;
+  for (int j = 0; j < nfields; j++) {
+    if (widths[j] < 1 || widths[j] > 4096) return fail(ctx, SC_ERR_ARG, "%s: bad field width %d", who, widths[j]);
+    lay->width[j] = widths[j]; lay->fbits[j] = widths[j] + kappa + 2; lay->off[j] = off;
+    if (lay->s + lay->fbits[j] >= nbits_n - 1) return fail(ctx, SC_ERR_ARG, "%s: the product of field %d does not fit below N", who, j);
+    off += lay->fbits[j];
+  }
+  lay->end = off;
+  if (off >= nbits_n - 1) return fail(ctx, SC_ERR_ARG, "%s: the packed fields (%d bits) do not fit below N (%d bits)", who, off, nbits_n);
+  return SC_OK;
+}
+
+int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* r_a,
+                   int aw, const uint32_t* r_b, int bw, int ew, uint32_t* R, uint32_t* e, uint32_t* rab, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  if (!ctx || !n_hptr || nw <= 0 || !r_a || !r_b || !R || !e || !rab || aw < 1 || aw > 2 || bw < 1 || ew < 1)
+    return fail(ctx, SC_ERR_ARG, "sc_select_prep: bad argument");
+  SelLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = select_layout(ctx, "sc_select_prep", big_bits(n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  if (bw > nw) return fail(ctx, SC_ERR_ARG, "sc_select_prep: r_b rows of %d words are wider than N (%d words)", bw, nw);
+  for (int j = 0; j < nfields; j++)
+    if (32 * ew < lay.fbits[j]) return fail(ctx, SC_ERR_ARG, "sc_select_prep: exponent rows of %d words are too narrow", ew);
+  if (launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, nw, ew, count, R, e, rab)) return fail(ctx, SC_ERR_HIP, "sc_select_prep: launch failed");
+  return SC_OK;
+}
+
+int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* p,
+                    uint32_t* prod, uint32_t* bad, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  if (!ctx || !n_hptr || nw <= 0 || !p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_select_split: bad argument");
+  SelLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = select_layout(ctx, "sc_select_split", big_bits(n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  if (launch_select_split(ctx->stream, p, nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_select_split: launch failed");
+  return SC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -47,6 +47,8 @@ enum PvOpcode : uint32_t {
   PV_LOADT = 6,   // pair = scratch pair entry w1
   PV_ADDT = 7,    // pair += scratch pair entry w1 (component-wise, lazy)
   PV_OUT = 8,     // leave the pair form and store: ACC0 -> ext[w1], ACC1 -> ext[w2] as exact words (not reduced mod n)
+  PV_MULTDIG = 9, // pair *= scratch pair entry w2 + digit, digit = `width` bits at `bitpos` of the item's row in ext (w1 = ext | bitpos<<4 |
+                  //   width<<24, as AK_TBLDIG): per-row exponents.  Only in the k_pvm<.., DIG = true> instances
 };
 
 enum VmAKind : uint32_t {
@@ -76,6 +78,13 @@ struct VmExt {
 };
 
 struct RngKey { uint32_t k[8]; };   // ChaCha20 key of a context's generator (sc_rng.h)
+
+// Field layout of a secure selection's packed plaintext (k_select_prep / k_select_split, sc_kernel_plain.h)
+constexpr int SEL_MAX_FIELDS = 4;
+struct SelLayout {
+  int s, nf, end;                  // end = off[nf - 1] + fbits[nf - 1]: no bit at or above it is set in a well-formed P
+  int off[SEL_MAX_FIELDS], fbits[SEL_MAX_FIELDS], width[SEL_MAX_FIELDS];
+};
 
 constexpr int VM_MAX_EXT = 8;
 constexpr int VM_MAX_CONST = 8;  // including R^2 and R

@@ -344,6 +344,66 @@ class Engine:
                                                  self._ptr(mul_into), self._ptr(out), count))
         return out
 
+    def modexp_var_sq(self, mod_m: Modulus, mod_m2: Modulus, x: torch.Tensor, e: torch.Tensor, ebits: int,
+                      mul_into: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """prod_j x[j]^e[j] [* mul_into] mod m^2 with exponents per row (sc_modexp_var_sq): x [nb][count][x_words], e [nb][count][ewords],
+        nb = 1 .. 3, exponent bits at or above `ebits` ignored.  Where the modulus has no per-row pair kernel (SC_ERR_UNSUPPORTED) the
+        same residues come from sc_modexp_var modulo m^2 and sc_modmul."""
+        if x.dim() != 3 or e.dim() != 3 or x.shape[0] != e.shape[0] or x.shape[1] != e.shape[1]:
+            raise ValueError("x, e: expected [nbases][count][words] arrays of the same nbases and count")
+        nb, count = x.shape[0], x.shape[1]
+        self._arr(x, "x", nb * count)
+        self._arr(e, "e", nb * count)
+        self._arr(mul_into, "mul_into", count, mod_m2.nwords, optional=True)
+        out = self._out(out, count, mod_m2.nwords)
+        self._sync_stream()
+        rc = self.lib.sc_modexp_var_sq(self.ctx, mod_m.id, mod_m2.id, nb, self._ptr(x), x.shape[-1], self._ptr(e), e.shape[-1], ebits,
+                                       self._ptr(mul_into), self._ptr(out), count)
+        if rc != -4:
+            self._check(rc)
+            return out
+        if x.shape[-1] != mod_m2.nwords:
+            raise ValueError(f"x: {x.shape[-1]} words per item; without the pair kernel the operands must be residues of {mod_m2.nwords} words")
+        acc = mul_into
+        for j in range(nb if ebits > 0 else 0):
+            t = self.modexp_var(mod_m2, x[j], e[j], ebits)
+            acc = t if acc is None else self.modmul(mod_m2, acc, t)
+        if acc is None:
+            acc = self.upload([1] * count, mod_m2.nwords)
+        out.copy_(acc)
+        return out
+
+    def select_prep(self, n: int, kappa: int, widths: list[int], r_a: torch.Tensor, r_b: torch.Tensor, ew: int):
+        """The initiator's plaintext values of a selection (sc_select_prep): R [count][nw], e [nf][count][ew], rab [nf][count][nw]."""
+        nf, count = len(widths), r_a.shape[0]
+        self._arr(r_a, "r_a", count)
+        self._arr(r_b, "r_b", nf * count)
+        if r_b.dim() != 3 or r_b.shape[0] != nf:
+            raise ValueError("r_b: expected [nfields][count][words]")
+        nw = (n.bit_length() + 31) // 32
+        _, pn = self._host_n_words(n, nw)
+        wa = np.array(widths, dtype=np.int32)
+        R, rab = self.empty(count, nw), torch.empty((nf, count, nw), dtype=torch.int32, device=self.device)
+        e = torch.empty((nf, count, ew), dtype=torch.int32, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_select_prep(self.ctx, pn, nw, kappa, nf, wa.ctypes.data_as(C.c_void_p), self._ptr(r_a), r_a.shape[-1],
+                                            self._ptr(r_b), r_b.shape[-1], ew, self._ptr(R), self._ptr(e), self._ptr(rab), count))
+        return R, e, rab
+
+    def select_split(self, n: int, kappa: int, widths: list[int], p: torch.Tensor):
+        """The key holder's products a * b_j of the fields of the decrypted P (sc_select_split): ([nf][count][nw], bad flag int32 [1])."""
+        count, nf = self._items(p), len(widths)
+        nw = (n.bit_length() + 31) // 32
+        self._arr(p, "p", count, nw)
+        _, pn = self._host_n_words(n, nw)
+        wa = np.array(widths, dtype=np.int32)
+        prod = torch.empty((nf, count, nw), dtype=torch.int32, device=self.device)
+        bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_select_split(self.ctx, pn, nw, kappa, nf, wa.ctypes.data_as(C.c_void_p), self._ptr(p), self._ptr(prod),
+                                             self._ptr(bad), count))
+        return prod, bad
+
     def modexp_shared_isone(self, mod: Modulus, x: torch.Tensor, e: int) -> torch.Tensor:
         count = self._items(x)
         self._arr(x, "x", count)

@@ -306,6 +306,24 @@ class Initiator:
         from .batch import draw_alice, split_draws
         from .distributed import shard_bounds
 
+        sid = await self._open_batch_session(x_enc, y_enc, engine)
+        comm, count = self.communicator, x_enc.shape[0]
+        chunks = max(1, min(int(chunks), count))
+        if chunks == 1:
+            return await self._batch_session(f"session_{sid}", x_enc, y_enc, draws, source, generator, None)
+        bounds = [shard_bounds(count, i, chunks) for i in range(chunks)]
+        await comm.send(self.other_party, wire.pack_plan([b - a for a, b in bounds]), msg_id=f"step_1_batch_session_{sid}")
+        parts = [None] * chunks if draws is None else split_draws(draws, bounds)
+        out = torch.empty_like(x_enc)
+        await asyncio.gather(*(self._batch_session(f"session_{sid}_chunk_{i}", x_enc[a:b], y_enc[a:b], parts[i], source, generator, out[a:b])
+                               for i, (a, b) in enumerate(bounds)))
+        return out
+
+    async def _open_batch_session(self, x_enc: torch.Tensor, y_enc: torch.Tensor, engine) -> int:
+        """The start of a batch session: the key holder's public schemes (message `schemes_batch_session_{sid}`) checked against
+        those already held, and the shapes of x_enc, y_enc.  Returns the session id."""
+        from . import wire
+
         if self.communicator is None:
             raise ValueError("Communicator not properly initialized.")
         check_l(self.l_maximum_bit_length)
@@ -325,19 +343,12 @@ class Initiator:
         count = x_enc.shape[0]
         wire.expect_array(x_enc, (count, 2 * pai.mod_n.nwords), "x_enc")
         wire.expect_array(y_enc, (count, 2 * pai.mod_n.nwords), "y_enc")
-        chunks = max(1, min(int(chunks), count))
-        if chunks == 1:
-            return await self._batch_session(f"session_{sid}", x_enc, y_enc, draws, source, generator, None)
-        bounds = [shard_bounds(count, i, chunks) for i in range(chunks)]
-        await comm.send(self.other_party, wire.pack_plan([b - a for a, b in bounds]), msg_id=f"step_1_batch_session_{sid}")
-        parts = [None] * chunks if draws is None else split_draws(draws, bounds)
-        out = torch.empty_like(x_enc)
-        await asyncio.gather(*(self._batch_session(f"session_{sid}_chunk_{i}", x_enc[a:b], y_enc[a:b], parts[i], source, generator, out[a:b])
-                               for i, (a, b) in enumerate(bounds)))
-        return out
+        return sid
 
-    async def _batch_session(self, tag: str, x_enc: torch.Tensor, y_enc: torch.Tensor, draws, source: str, generator, out) -> torch.Tensor:
-        """One (sub-)session of the batched protocol: Alice's steps around the four message exchanges, message ids `.._{tag}`."""
+    async def _batch_session(self, tag: str, x_enc: torch.Tensor, y_enc: torch.Tensor, draws, source: str, generator, out,
+                             keep: dict | None = None) -> torch.Tensor:
+        """One (sub-)session of the batched protocol: Alice's steps around the four message exchanges, message ids `.._{tag}`.
+        keep: receives the sent [[z + r]] ("z_enc", on the device) and r ("r") for a selection that follows (selection.py)."""
         from . import wire
         from .batch import draw_alice
 
@@ -350,6 +361,8 @@ class Initiator:
         # (wire.reserve: no device-to-host copy afterwards); a device transport gets the arrays themselves
         msg = wire.reserve(comm, dev, (count, 2 * nw_p))
         z_enc, plain = Initiator.step_1_batch(x_enc, y_enc, l, pai, draws.r, draws.rho_z, out=None if msg is None else msg.arrays[0])
+        if keep is not None:         # (a byte transport's [[z]] lives in the pinned message: the copy is ordered after its launch)
+            keep["z_enc"], keep["r"] = (z_enc if z_enc.device == dev else z_enc.to(dev)), draws.r
         await comm.send(self.other_party, wire.outgoing(comm, z_enc) if msg is None else await msg.finish(), msg_id=f"step_1_batch_{tag}")
         got = wire.incoming(await comm.recv(self.other_party, msg_id=f"step_4b_batch_{tag}"), dev, expect=None, planes_of_one=True)
         if len(got) == 1:            # [d] and the planes [beta_i] as ONE array, the way the key holder's launch stored them
@@ -376,6 +389,37 @@ class Initiator:
         else:
             raise ValueError(f"batch message carries {len(got)} arrays, expected three ciphertext blocks")
         return Initiator.step_6_7_batch(draws.delta_a, delta_b_enc, zeta_1, zeta_2, plain, l, pai, out)   # one inversion pass
+
+    # ---- secure selection (selection.py): the comparison session, then one selection exchange per round
+    async def perform_secure_minimum_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor, draws=None, select_draws=None, kappa: int = 40,
+                                           source: str = "device", engine=None, generator=None, chunks: int = 1):
+        """([[min(x, y)]], [[x <= y]]) for B pairs: perform_secure_comparison_batch's messages, then `select_1_batch_{tag}` (P) and
+        `select_2_batch_{tag}` (the key holder's products).  chunks > 1 is not supported (ValueError)."""
+        from .selection import alice_minmax
+
+        return await alice_minmax(self, x_enc, y_enc, draws, select_draws, kappa, source, engine, generator, chunks, want_max=False)
+
+    async def perform_secure_maximum_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor, draws=None, select_draws=None, kappa: int = 40,
+                                           source: str = "device", engine=None, generator=None, chunks: int = 1):
+        """([[max(x, y)]], [[x <= y]]); same messages as perform_secure_minimum_batch."""
+        from .selection import alice_minmax
+
+        return await alice_minmax(self, x_enc, y_enc, draws, select_draws, kappa, source, engine, generator, chunks, want_max=True)
+
+    async def perform_secure_argmin_batch(self, v_enc: torch.Tensor, kappa: int = 40, source: str = "device", engine=None, generator=None,
+                                          chunks: int = 1):
+        """([[min_i v_i]], [[argmin_i v_i]]) over v_enc [B][k][2nw], ties to the lowest index: ceil(log2 k) rounds of one comparison
+        session and one selection exchange (message ids `.._session_{sid}_round_{i}`)."""
+        from .selection import alice_argext
+
+        return await alice_argext(self, v_enc, kappa, source, engine, generator, chunks, want_max=False)
+
+    async def perform_secure_argmax_batch(self, v_enc: torch.Tensor, kappa: int = 40, source: str = "device", engine=None, generator=None,
+                                          chunks: int = 1):
+        """([[max_i v_i]], [[argmax_i v_i]]), ties to the lowest index."""
+        from .selection import alice_argext
+
+        return await alice_argext(self, v_enc, kappa, source, engine, generator, chunks, want_max=True)
 
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""

@@ -245,14 +245,8 @@ class KeyHolder:
         from . import wire
         from .batch import split_draws
 
-        if self.communicator is None:
-            raise ValueError("Communicator not properly initialized.")
-        check_l(self.l_maximum_bit_length)
+        sid = await self._open_batch_session()
         comm = self.communicator
-        self.session_id += 1
-        sid = self.session_id
-        pai, dgk = self.scheme_paillier, self.scheme_dgk
-        await comm.send(self.other_party, wire.pack_public_schemes(pai, dgk), msg_id=f"schemes_batch_session_{sid}")
         first = await comm.recv(self.other_party, msg_id=f"step_1_batch_session_{sid}")
         sizes = wire.plan_of(first)
         if sizes is None:
@@ -270,9 +264,47 @@ class KeyHolder:
         await asyncio.gather(*(self._batch_session(f"session_{sid}_chunk_{i}", None, parts[i], source, generator, expect_count=n)
                                for i, n in enumerate(sizes)))
 
-    async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> None:
+    async def _open_batch_session(self) -> int:
+        """The start of a batch session: the public schemes to the initiator (`schemes_batch_session_{sid}`).  Returns the session id."""
+        from . import wire
+
+        if self.communicator is None:
+            raise ValueError("Communicator not properly initialized.")
+        check_l(self.l_maximum_bit_length)
+        self.session_id += 1
+        sid = self.session_id
+        await self.communicator.send(self.other_party, wire.pack_public_schemes(self.scheme_paillier, self.scheme_dgk),
+                                     msg_id=f"schemes_batch_session_{sid}")
+        return sid
+
+    # ---- secure selection (selection.py): the key holder's side of Initiator.perform_secure_{minimum,maximum,argmin,argmax}_batch
+    async def perform_secure_minimum_batch(self, draws=None, select_draws=None, kappa: int = 40, source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_minimum_batch: the comparison session, then one selection exchange."""
+        from .selection import bob_rounds
+
+        await bob_rounds(self, 1, draws, select_draws, kappa, source, generator, ())
+
+    async def perform_secure_maximum_batch(self, draws=None, select_draws=None, kappa: int = 40, source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_maximum_batch (the same steps as the minimum's)."""
+        from .selection import bob_rounds
+
+        await bob_rounds(self, 1, draws, select_draws, kappa, source, generator, ())
+
+    async def perform_secure_argmin_batch(self, k: int, kappa: int = 40, source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_argmin_batch over k values per row: ceil(log2 k) rounds."""
+        from .selection import bob_rounds, index_bits, tournament_rounds
+
+        await bob_rounds(self, tournament_rounds(k), None, None, kappa, source, generator, (index_bits(k),))
+
+    async def perform_secure_argmax_batch(self, k: int, kappa: int = 40, source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_argmax_batch (the same steps as the argmin's)."""
+        from .selection import bob_rounds, index_bits, tournament_rounds
+
+        await bob_rounds(self, tournament_rounds(k), None, None, kappa, source, generator, (index_bits(k),))
+
+    async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
-        message when it has been received already."""
+        message when it has been received already.  Returns the session's batch size."""
         from . import wire
         from ._views import cat_rows
         from .batch import draw_bob
@@ -302,6 +334,7 @@ class KeyHolder:
             out=None if msg is None else msg.arrays[0].reshape(3 * count, 2 * pai.mod_n.nwords))
         await comm.send(self.other_party, wire.outgoing(comm, zeta_1_enc, zeta_2_enc, delta_b_enc) if msg is None else await msg.finish(),
                         msg_id=f"step_5_batch_{tag}")
+        return count
 
     async def make_and_send_encryption_schemes(self, session_id: int = 1, key_length_paillier: int = 2048,
                                                v_bits_dgk: int = 160, n_bits_dgk: int = 2048) -> None:

@@ -490,6 +490,13 @@ class Paillier(_Scheme):
     def add_batch(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         return self.engine.modmul(self.mod_n2, a, b)
 
+    def scalar_mul_batch(self, c: torch.Tensor, k: torch.Tensor, ebits: int | None = None) -> torch.Tensor:
+        """[[k m]] = c^k mod N^2 for ciphertexts c [count][2nw] and non-negative scalars k [count][kw] (one per row): the batched twin
+        of `ct * k`, one launch of the per-row pair exponentiation (sc_modexp_var_sq).  ebits: bits of the scalars (default 32 kw)."""
+        if c.dim() != 2 or k.dim() != 2 or c.shape[0] != k.shape[0]:
+            raise ValueError("c, k: expected [count][words] arrays of the same count")
+        return self.engine.modexp_var_sq(self.mod_n, self.mod_n2, c.unsqueeze(0), k.unsqueeze(0), 32 * k.shape[-1] if ebits is None else ebits)
+
     def neg_batch(self, a: torch.Tensor) -> torch.Tensor:
         return self.engine.modinv(self.mod_n2, a)
 

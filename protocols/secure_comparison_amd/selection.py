@@ -1,0 +1,397 @@
+"""Batched secure selection on top of the comparison: [[min(x, y)]], [[max(x, y)]], and argmin / argmax over k values per row.
+
+One extra round trip after the comparison turns [[delta]] = [[x <= y]] into the selected ciphertext ("Secure
+selection").  For a selector sigma in {0, 1} and columns j with [[b_j]] and [[d_j]], d_j = a_j - b_j + 2^w_j:
+
+1. Alice packs P = [[sigma]] * prod_j [[d_j]]^(2^off_j) * (1 + R N) * rho^N, plaintext (sigma + r_a) + sum_j 2^off_j (d_j + r_b_j).
+2. Bob decrypts P once, splits the fields a = sigma + r_a and b_j = d_j + r_b_j and returns the fresh encryptions [[a b_j]].
+3. Alice unblinds: [[b_j + sigma (a_j - b_j)]] = [[b_j]] [[a b_j]] T_j^-1 with T_j = [[sigma]]^(r_b_j + 2^w_j) [[d_j]]^r_a (1 + r_a r_b_j N).
+
+Everything stays on the device; the exponentiations with per-row exponents run on the pair interpreter (sc_modexp_var_sq).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+
+from .batch import BatchDraws, BatchTrace, draw_alice, draw_bob, secure_comparison_batch
+from .flags import check_l
+from .schemes import DGK, Paillier
+
+MAX_FIELDS = 4      # columns of one selection (csrc/sc_vm.h SEL_MAX_FIELDS)
+
+
+@dataclass(frozen=True)
+class SelectLayout:
+    """Field layout of the packed plaintext of P for a value of l bits and payload columns of payload_bits[i] bits, under a key of
+    nbits bits: a = sigma + r_a in [0, s), s = kappa + 1, then column j (width w_j: d_j < 2^(w_j + 1)) in w_j + kappa + 2 bits.
+    Raises ValueError when the fields, or one product a * b_j, would not fit below N."""
+
+    l: int
+    kappa: int
+    payload_bits: tuple = ()
+    nbits: int = 2048
+
+    def __post_init__(self) -> None:
+        object.__setattr__(self, "payload_bits", tuple(int(b) for b in self.payload_bits))
+        if not 1 <= self.kappa <= 62:
+            raise ValueError(f"kappa = {self.kappa}: expected 1 <= kappa <= 62")
+        if self.l < 1 or any(b < 1 for b in self.payload_bits):
+            raise ValueError("column widths must be >= 1")
+        if len(self.widths) > MAX_FIELDS:
+            raise ValueError(f"{len(self.widths)} columns: at most {MAX_FIELDS}")
+        for j, f in enumerate(self.fbits):
+            if self.s + f >= self.nbits - 1:
+                raise ValueError(f"column {j}: the product a * b ({self.s + f} bits) does not fit below a {self.nbits}-bit N")
+        if self.end >= self.nbits - 1:
+            raise ValueError(f"the packed fields ({self.end} bits) do not fit below a {self.nbits}-bit N (kappa = {self.kappa})")
+
+    @property
+    def widths(self) -> list[int]:
+        return [self.l, *self.payload_bits]
+
+    @property
+    def s(self) -> int:
+        return self.kappa + 1
+
+    @property
+    def fbits(self) -> list[int]:
+        return [w + self.kappa + 2 for w in self.widths]
+
+    @property
+    def offsets(self) -> list[int]:
+        off, out = self.s, []
+        for f in self.fbits:
+            out.append(off)
+            off += f
+        return out
+
+    @property
+    def end(self) -> int:
+        return self.s + sum(self.fbits)
+
+    @property
+    def t_bits(self) -> int:
+        """Bits of the exponents of T: r_b_j + 2^w_j < 2^(w_j + kappa + 2), r_a < 2^kappa."""
+        return max(self.fbits)
+
+
+@dataclass
+class SelectDraws:
+    """The random inputs of one selection batch: Alice's r_a [B][aw] (< 2^kappa), r_b [nf][B][bw] (column j < 2^(w_j + 1 + kappa)) and
+    rho_p [B][nw] (P's randomizer); Bob's rho_products [nf][B][nw] (the randomizers of his returned products).  Either side None."""
+
+    r_a: torch.Tensor | None
+    r_b: torch.Tensor | None
+    rho_p: torch.Tensor | None
+    rho_products: torch.Tensor | None
+
+
+def draw_select(count: int, layout: SelectLayout, paillier: Paillier, source: str = "device", generator=None,
+                alice: bool = True, bob: bool = True) -> SelectDraws:
+    """Both players' (or one player's) selection draws for `count` rows, on the device or from a seeded torch generator."""
+    from .randomness import random_bits, uniform_below
+
+    e, n = paillier.engine, paillier.public_key.n
+    nf = len(layout.widths)
+    r_a = r_b = rho_p = rho_q = None
+    if alice:
+        r_a = random_bits(layout.kappa, (count,), e, source, generator)
+        bw = (max(layout.fbits) + 31) // 32
+        cols = []
+        for w in layout.widths:
+            c = random_bits(w + 1 + layout.kappa, (count,), e, source, generator)
+            cols.append(torch.nn.functional.pad(c, (0, bw - c.shape[-1])))
+        r_b = torch.stack(cols).contiguous()
+        rho_p = uniform_below(n, count, e, source, generator, nonzero=True)
+    if bob:
+        rho_q = uniform_below(n, nf * count, e, source, generator, nonzero=True).reshape(nf, count, -1)
+    return SelectDraws(r_a=r_a, r_b=r_b, rho_p=rho_p, rho_products=rho_q)
+
+
+def _pow2_shared(paillier: Paillier, x: torch.Tensor, bits: int, mul_into: torch.Tensor) -> torch.Tensor:
+    """x^(2^bits) * mul_into mod N^2 (sc_modexp_shared_sq; sc_modexp_shared modulo N^2 where the pair arithmetic does not fit)."""
+    e = paillier.engine
+    if e.supports_sq(paillier.mod_n):
+        return e.modexp_shared_sq(paillier.mod_n, paillier.mod_n2, x, 1 << bits, mul_into=mul_into)
+    return e.modexp_shared(paillier.mod_n2, x, 1 << bits, mul_into=mul_into)
+
+
+def _pad_words(t: torch.Tensor, words: int) -> torch.Tensor:
+    return t if t.shape[-1] == words else torch.nn.functional.pad(t, (0, words - t.shape[-1])).contiguous()
+
+
+# ---- the three steps --------------------------------------------------------------------------------------------------------------
+def select_pack(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, draws: SelectDraws, paillier: Paillier):
+    """Alice, step 1: P [B][2nw] from [[sigma]] [B][2nw] and [[d_j]] [nf][B][2nw]; returns (P, (e, rab)) -- the latter is what
+    select_finish needs."""
+    e = paillier.engine
+    nf, count = len(layout.widths), sigma_enc.shape[0]
+    if d_enc.dim() != 3 or d_enc.shape[0] != nf or d_enc.shape[1] != count:
+        raise ValueError(f"d_enc: expected [{nf}][{count}][words]")
+    ew = (layout.t_bits + 31) // 32
+    R, et, rab = e.select_prep(paillier.public_key.n, layout.kappa, layout.widths, draws.r_a, draws.r_b, ew)
+    m = paillier.add_batch(sigma_enc, paillier.encrypt_raw_batch(R))            # [[sigma + R]]
+    m = paillier.randomize_batch(m, draws.rho_p)                                 # * rho^N: fresh randomness Bob cannot trace
+    # prod_j [[d_j]]^(2^off_j): exponents shared by the batch, so Horner from the top column with squarings only
+    offs = layout.offsets
+    t = d_enc[nf - 1]
+    for j in range(nf - 1, -1, -1):
+        t = _pow2_shared(paillier, t, offs[j] - (offs[j - 1] if j > 0 else 0), d_enc[j - 1] if j > 0 else m)
+    return t, (et, rab)
+
+
+def select_mult(layout: SelectLayout, P: torch.Tensor, paillier: Paillier, rho_products: torch.Tensor) -> torch.Tensor:
+    """Bob, step 2: one CRT decryption of P, the field products a * b_j, encrypted and freshly randomized: [nf][B][2nw].
+    ValueError when a decrypted row does not fit the announced layout (the players disagree on kappa or the widths)."""
+    e = paillier.engine
+    nf, count = len(layout.widths), P.shape[0]
+    p = paillier.decrypt_raw_batch(P)
+    prod, bad = e.select_split(paillier.public_key.n, layout.kappa, layout.widths, p)
+    nw2 = paillier.mod_n2.nwords
+    c = paillier.randomize_batch(paillier.encrypt_raw_batch(prod.reshape(nf * count, -1)), rho_products.reshape(nf * count, -1))
+    if int(bad.item()):
+        raise ValueError("select: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)")
+    return c.reshape(nf, count, nw2)
+
+
+def select_finish(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor, products: torch.Tensor,
+                  plain, draws: SelectDraws, paillier: Paillier) -> torch.Tensor:
+    """Alice, step 3: [[b_j + sigma (a_j - b_j)]] [nf][B][2nw] from Bob's products."""
+    e = paillier.engine
+    et, rab = plain
+    nf, count = len(layout.widths), sigma_enc.shape[0]
+    nw2 = paillier.mod_n2.nwords
+    ew = et.shape[-1]
+    x = torch.stack([sigma_enc.unsqueeze(0).expand(nf, count, nw2).reshape(nf * count, nw2), d_enc.reshape(nf * count, nw2)])
+    ex = torch.stack([et.reshape(nf * count, ew), _pad_words(draws.r_a, ew).unsqueeze(0).expand(nf, count, ew).reshape(nf * count, ew)])
+    T = e.modexp_var_sq(paillier.mod_n, paillier.mod_n2, x.contiguous(), ex.contiguous(), layout.t_bits,
+                        mul_into=paillier.encrypt_raw_batch(rab.reshape(nf * count, -1)))
+    t_inv = e.modinv(paillier.mod_n2, T)
+    out = paillier.add_batch(paillier.add_batch(b_enc.reshape(nf * count, nw2), products.reshape(nf * count, nw2)), t_inv)
+    return out.reshape(nf, count, nw2)
+
+
+def select_batch(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor, alice_paillier: Paillier,
+                 bob_paillier: Paillier, draws: SelectDraws) -> torch.Tensor:
+    """Both players' halves of one selection batch in one process: [[b_j + sigma (a_j - b_j)]] [nf][B][2nw]."""
+    P, plain = select_pack(layout, sigma_enc, d_enc, draws, alice_paillier)
+    products = select_mult(layout, P, bob_paillier, draws.rho_products)
+    return select_finish(layout, sigma_enc, d_enc, b_enc, products, plain, draws, alice_paillier)
+
+
+# ---- min / max ---------------------------------------------------------------------------------------------------------------------
+def _comparison_draws(count: int, l: int, ap: Paillier, ad: DGK, bp: Paillier, bd: DGK) -> BatchDraws:
+    a, b = draw_alice(count, l, ap, ad), draw_bob(count, l, bp, bd)
+    return BatchDraws(r=a.r, delta_a=a.delta_a, rhos=a.rhos, permutation=a.permutation, rho_z=a.rho_z, r_bob_dgk=b.r_bob_dgk,
+                      r_alice_dgk=a.r_alice_dgk, rho_zeta_1=b.rho_zeta_1, rho_zeta_2=b.rho_zeta_2, rho_delta_b=b.rho_delta_b)
+
+
+def _compare(x_enc, y_enc, l, ap, ad, bp, bd, draws):
+    """[[x <= y]] and Alice's [[d]] = [[y - x + 2^l]] = [[z + r]] (1 - r N) from step 1 (z = y - x + 2^l): no inversion."""
+    draws = draws if draws is not None else _comparison_draws(x_enc.shape[0], l, ap, ad, bp, bd)
+    trace = BatchTrace()
+    delta = secure_comparison_batch(x_enc, y_enc, l, ap, ad, bp, bd, draws, trace=trace)
+    d = ap.add_batch(trace.z_enc, ap.encrypt_raw_neg_batch(draws.r))
+    return delta, d
+
+
+def _one_minus(paillier: Paillier, c: torch.Tensor) -> torch.Tensor:
+    """[[1 - c]] = g [[c]]^-1 (one batched inversion)."""
+    return paillier.engine.modmul_const(paillier.mod_n2, paillier.neg_batch(c), paillier.public_key.n + 1)
+
+
+def _minmax(x_enc, y_enc, l, ap, ad, bp, bd, draws, select_draws, kappa, want_max):
+    check_l(l)
+    layout = SelectLayout(l, kappa, (), ap.public_key.n.bit_length())
+    delta, d = _compare(x_enc, y_enc, l, ap, ad, bp, bd, draws)
+    sigma = delta if want_max else _one_minus(ap, delta)            # max = x + delta (y - x), min = x + (1 - delta)(y - x)
+    sd = select_draws if select_draws is not None else draw_select(x_enc.shape[0], layout, ap)
+    out = select_batch(layout, sigma, d.unsqueeze(0), x_enc.unsqueeze(0), ap, bp, sd)
+    return out[0], delta
+
+
+def secure_minimum_batch(x_enc: torch.Tensor, y_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK,
+                         bob_paillier: Paillier, bob_dgk: DGK, draws: BatchDraws | None = None,
+                         select_draws: SelectDraws | None = None, kappa: int = 40):
+    """([[min(x, y)]], [[x <= y]]) for B pairs of Paillier ciphertexts [B][2nw] under Bob's key, 0 <= x, y < 2^l."""
+    return _minmax(x_enc, y_enc, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, draws, select_draws, kappa, False)
+
+
+def secure_maximum_batch(x_enc: torch.Tensor, y_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK,
+                         bob_paillier: Paillier, bob_dgk: DGK, draws: BatchDraws | None = None,
+                         select_draws: SelectDraws | None = None, kappa: int = 40):
+    """([[max(x, y)]], [[x <= y]]): the same comparison and selection; the minimum selects with [[1 - delta]] instead (one
+    extra batched inversion)."""
+    return _minmax(x_enc, y_enc, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, draws, select_draws, kappa, True)
+
+
+# ---- argmin / argmax -----------------------------------------------------------------------------------------------------------------
+def index_bits(k: int) -> int:
+    """Width of the index column: indices 0 .. k - 1 are below 2^index_bits(k)."""
+    return max(1, (k - 1).bit_length())
+
+
+def tournament_rounds(k: int) -> int:
+    """Rounds of the argmin / argmax tournament over k values: ceil(log2 k)."""
+    return (k - 1).bit_length()
+
+
+def _arg_inputs(ap, lv, li, rv, ri, delta, d_v, k, want_max):
+    """The selection inputs of one tournament round from its comparison.  min compared (L, R): delta = [L <= R], d = R - L + 2^l,
+    winner = L + (1 - delta)(R - L).  max compared (R, L): delta' = [R <= L], d = L - R + 2^l, winner = R + delta' (L - R).  Both
+    keep the left operand on ties.  Returns (sigma, [[d]] [2][P][2nw], [[b]] [2][P][2nw])."""
+    n, count, wi = ap.public_key.n, lv.shape[0], index_bits(k)
+    if not want_max:            # [[1 - delta]] and the index column's [[L.i]]^-1 share one batched inversion
+        inv = ap.neg_batch(torch.cat([delta, li]))
+        sigma = ap.engine.modmul_const(ap.mod_n2, inv[:count], n + 1)
+        d_i = ap.engine.modmul_const(ap.mod_n2, ap.add_batch(ri, inv[count:]), 1 + (1 << wi) * n)
+        return sigma, torch.stack([d_v, d_i]), torch.stack([lv, li])
+    d_i = ap.engine.modmul_const(ap.mod_n2, ap.add_batch(li, ap.neg_batch(ri)), 1 + (1 << wi) * n)
+    return delta, torch.stack([d_v, d_i]), torch.stack([rv, ri])
+
+
+def _arg_start(v_enc, l, ap, kappa):
+    check_l(l)
+    if v_enc.dim() != 3:
+        raise ValueError("v_enc: expected [B][k][2nw]")
+    B, k, _ = v_enc.shape
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    layout = SelectLayout(l, kappa, (index_bits(k),), ap.public_key.n.bit_length())    # the layout check before any launch
+    vals = [v_enc[:, i].contiguous() for i in range(k)]
+    idx = [ap.encrypt_raw_batch(ap.engine.upload([i] * B, 1)) for i in range(k)]         # trivial encryptions 1 + i N
+    return layout, B, k, vals, idx
+
+
+def _pairs(vals, idx):
+    """The round's pairs (2t, 2t + 1) of every row as [h B][2nw] arrays: (h, left values, left indices, right values, right indices)."""
+    h = len(vals) // 2
+    cat = lambda xs: torch.cat(xs).contiguous()  # noqa: E731
+    return h, cat(vals[0:2 * h:2]), cat(idx[0:2 * h:2]), cat(vals[1:2 * h:2]), cat(idx[1:2 * h:2])
+
+
+def _unpair(wv, wi, vals, idx, h, B):
+    nv = [wv[t * B:(t + 1) * B] for t in range(h)]
+    ni = [wi[t * B:(t + 1) * B] for t in range(h)]
+    if len(vals) % 2:                       # the odd element carries over to the next round
+        nv.append(vals[-1])
+        ni.append(idx[-1])
+    return nv, ni
+
+
+def _argext(v_enc, l, ap, ad, bp, bd, kappa, want_max):
+    layout, B, k, vals, idx = _arg_start(v_enc, l, ap, kappa)
+    while len(vals) > 1:
+        h, lv, li, rv, ri = _pairs(vals, idx)
+        delta, d_v = _compare(rv, lv, l, ap, ad, bp, bd, None) if want_max else _compare(lv, rv, l, ap, ad, bp, bd, None)
+        sigma, d, b = _arg_inputs(ap, lv, li, rv, ri, delta, d_v, k, want_max)
+        out = select_batch(layout, sigma, d, b, ap, bp, draw_select(lv.shape[0], layout, ap))
+        vals, idx = _unpair(out[0], out[1], vals, idx, h, B)
+    return vals[0].contiguous(), idx[0].contiguous()
+
+
+def secure_argmin_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
+                        kappa: int = 40):
+    """([[min_i v_i]], [[argmin_i v_i]]) over k values per row, v_enc [B][k][2nw]; ties go to the lowest index.  A tournament of
+    ceil(log2 k) rounds, each one comparison batch and one two-column selection batch over the row's pairs."""
+    return _argext(v_enc, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, kappa, False)
+
+
+def secure_argmax_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
+                        kappa: int = 40):
+    """([[max_i v_i]], [[argmax_i v_i]]); ties go to the lowest index."""
+    return _argext(v_enc, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, kappa, True)
+
+
+# ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{minimum,maximum,argmin,argmax}_batch) -----------------
+# Each round is one batched comparison session (Initiator._batch_session, its messages unchanged) followed by one selection exchange:
+# `select_1_batch_{tag}` carries the layout (kappa and the column widths, int32) and P, `select_2_batch_{tag}` the key holder's
+# products.  The key holder checks the announced layout against his own kappa, l and payload widths before he decrypts, so players
+# that disagree fail loudly in either direction (sc_select_split's flag alone catches only a layout wider than the key holder's).
+async def _alice_compare(ini, tag, x_enc, y_enc, draws, source, generator):
+    keep = {}
+    delta = await ini._batch_session(tag, x_enc, y_enc, draws, source, generator, None, keep=keep)
+    pai = ini.scheme_paillier
+    return delta, pai.add_batch(keep["z_enc"], pai.encrypt_raw_neg_batch(keep["r"]))
+
+
+async def _alice_select(ini, tag, layout, sigma, d, b, sd, source, generator):
+    from . import wire
+
+    comm, pai = ini.communicator, ini.scheme_paillier
+    nf, count, dev = len(layout.widths), sigma.shape[0], sigma.device
+    sd = sd if sd is not None else draw_select(count, layout, pai, source, generator, bob=False)
+    P, plain = select_pack(layout, sigma, d, sd, pai)
+    head = torch.tensor([layout.kappa, *layout.widths], dtype=torch.int32, device=dev)
+    await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"select_1_batch_{tag}")
+    (prods,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"select_2_batch_{tag}"), dev, expect=1)
+    prods = wire.expect_array(prods, (nf, count, pai.mod_n2.nwords), "[[a b_j]]")
+    return select_finish(layout, sigma, d, b, prods, plain, sd, pai)
+
+
+def _no_chunks(chunks):
+    if int(chunks) != 1:
+        raise ValueError("secure selection: chunks > 1 is not supported")
+
+
+async def alice_minmax(ini, x_enc, y_enc, draws, select_draws, kappa, source, engine, generator, chunks, want_max):
+    from .batch import draw_alice
+
+    _no_chunks(chunks)
+    sid = await ini._open_batch_session(x_enc, y_enc, engine)
+    pai, dgk, l = ini.scheme_paillier, ini.scheme_dgk, ini.l_maximum_bit_length
+    layout = SelectLayout(l, kappa, (), pai.public_key.n.bit_length())
+    if draws is None:
+        draws = draw_alice(x_enc.shape[0], l, pai, dgk, source, generator)
+    tag = f"session_{sid}"
+    delta, d = await _alice_compare(ini, tag, x_enc, y_enc, draws, source, generator)
+    sigma = delta if want_max else _one_minus(pai, delta)
+    out = await _alice_select(ini, tag, layout, sigma, d.unsqueeze(0), x_enc.unsqueeze(0), select_draws, source, generator)
+    return out[0], delta
+
+
+async def alice_argext(ini, v_enc, kappa, source, engine, generator, chunks, want_max):
+    _no_chunks(chunks)
+    if v_enc.dim() != 3:
+        raise ValueError("v_enc: expected [B][k][2nw]")
+    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
+    pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
+    layout, B, k, vals, idx = _arg_start(v_enc, l, pai, kappa)
+    rnd = 0
+    while len(vals) > 1:
+        tag = f"session_{sid}_round_{rnd}"
+        h, lv, li, rv, ri = _pairs(vals, idx)
+        x, y = (rv, lv) if want_max else (lv, rv)
+        delta, d_v = await _alice_compare(ini, tag, x, y, None, source, generator)
+        sigma, d, b = _arg_inputs(pai, lv, li, rv, ri, delta, d_v, k, want_max)
+        out = await _alice_select(ini, tag, layout, sigma, d, b, None, source, generator)
+        vals, idx = _unpair(out[0], out[1], vals, idx, h, B)
+        rnd += 1
+    return vals[0].contiguous(), idx[0].contiguous()
+
+
+async def bob_rounds(kh, rounds, draws, select_draws, kappa, source, generator, payload_bits):
+    """The key holder's side: `rounds` times (comparison session, selection exchange); he expects the layout (kappa, l, payload_bits)."""
+    from . import wire
+
+    sid = await kh._open_batch_session()
+    comm, pai, l = kh.communicator, kh.scheme_paillier, kh.l_maximum_bit_length
+    layout = SelectLayout(l, kappa, tuple(payload_bits), pai.public_key.n.bit_length())
+    dev = pai.engine.device
+    for rnd in range(rounds):
+        tag = f"session_{sid}" if not payload_bits else f"session_{sid}_round_{rnd}"
+        count = await kh._batch_session(tag, None, draws, source, generator)
+        head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"select_1_batch_{tag}"), dev, expect=2)
+        if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] > 1 + MAX_FIELDS:
+            raise ValueError("select: malformed layout announcement")
+        announced = [int(v) for v in head.cpu().tolist()]
+        if announced != [layout.kappa, *layout.widths]:
+            raise ValueError(f"select: the initiator announces kappa and widths {announced}, this key holder expects "
+                             f"{[layout.kappa, *layout.widths]}")
+        P = wire.expect_array(P, (count, pai.mod_n2.nwords), "P")
+        rho = (select_draws.rho_products if select_draws is not None
+               else draw_select(count, layout, pai, source, generator, alice=False).rho_products)
+        prods = select_mult(layout, P, pai, rho)
+        await comm.send(kh.other_party, wire.outgoing(comm, prods), msg_id=f"select_2_batch_{tag}")
