@@ -198,6 +198,14 @@ int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int n
  * (selection.py announces it in the message that carries P). */
 int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr,
                     const uint32_t* p_dptr, uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
+/* sc_select_finish_cx (initiator, the compare-exchange of a secure sort): from a selection with sigma = delta,
+ * base F and d = G - F + 2^w, both outputs hi = F ab^2 u_inv and lo = G t^2 u_inv modulo mod (N^2), where u_inv = (t ab)^-1.
+ * t, ab, u_inv, f, g: [nfields][count][words(mod)], nfields 1 .. 4.  lo_index / hi_index (both or neither): uint64 [nfields][count],
+ * the row of out [out_rows][words(mod)] that the lo / hi output of each column and item goes to; rows >= out_rows are not written.
+ * Both null: out is [2][nfields][count][words(mod)] = (lo, hi), out_rows >= 2 nfields count. */
+int sc_select_finish_cx(sc_ctx* ctx, int mod, int nfields, const uint32_t* t_dptr, const uint32_t* ab_dptr, const uint32_t* u_inv_dptr,
+                        const uint32_t* f_dptr, const uint32_t* g_dptr, const uint64_t* lo_index_dptr /* nullable */,
+                        const uint64_t* hi_index_dptr /* nullable */, uint32_t* out_dptr, uint64_t out_rows, uint64_t count);
 
 /* ---- fused Initiator steps 4c-4h (SC/initiator.py:272-485) --------------------------------------- */
 /* Inputs, all bit-major: beta[l][count][nw], beta_inv[l][count][nw], d[count][nw], d_inv[count][nw]

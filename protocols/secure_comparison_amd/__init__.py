@@ -5,8 +5,10 @@ from .initiator import AlicePlain, Initiator
 from .keyholder import BobPlain, KeyHolder
 from .schemes import DGK, DGKCiphertext, Paillier, PaillierCiphertext
 from .selection import secure_argmax_batch, secure_argmin_batch, secure_maximum_batch, secure_minimum_batch
+from .sorting import secure_sort_batch
 from .utils import from_bits, to_bits
 
 __all__ = ["Communicator", "InMemoryCommunicator", "StreamCommunicator", "Initiator", "KeyHolder", "from_bits", "to_bits", "Paillier", "PaillierCiphertext", "DGK",
-           "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch"]
+           "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch",
+           "secure_sort_batch"]
 __version__ = "0.1.0"

@@ -1907,6 +1907,42 @@ int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int 
   return SC_OK;
 }
 
+// ---- compare-exchange finish of a secure sort: both outputs of every column from one shared inversion ----------
+// The nf columns run as flat items (nf * count of them), so the program does not depend on nf and an index row entry is read at the
+// item's flat number.  Per item, with V = U^-1 R^3 (one product, shared by both outputs): hi = F ab ab V / R^3 = F ab^2 U^-1 and
+// lo = G T T V / R^3 = G T^2 U^-1 -- seven Montgomery products on operands loaded once.
+int sc_select_finish_cx(sc_ctx* ctx, int mod, int nfields, const uint32_t* t, const uint32_t* ab, const uint32_t* u_inv, const uint32_t* f,
+                        const uint32_t* g, const uint64_t* lo_index, const uint64_t* hi_index, uint32_t* out, uint64_t out_rows,
+                        uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  if (!valid_mod(ctx, mod) || nfields < 1 || nfields > SEL_MAX_FIELDS || !t || !ab || !u_inv || !f || !g || !out ||
+      (!lo_index) != (!hi_index))
+    return fail(ctx, SC_ERR_ARG, "sc_select_finish_cx: bad argument");
+  const uint64_t items = (uint64_t)nfields * count;
+  const bool indexed = lo_index != nullptr;
+  if (!indexed && out_rows < 2 * items)
+    return fail(ctx, SC_ERR_ARG, "sc_select_finish_cx: out holds %llu rows, the contiguous [2][nf][count] form needs %llu",
+                (unsigned long long)out_rows, (unsigned long long)(2 * items));
+  const Mod& m = ctx->mods[mod];
+  int cid;
+  {
+    Big one(m.nwords, 0); one[0] = 1;
+    int rc = sc_const_create_cached(ctx, mod, big_shl_mod(one, m.n, 3 * m.W * m.S), &cid); if (rc) return rc;   // R^3 mod n
+  }
+  const Prog* p;
+  int rc = cached_prog(ctx, "cxfin:" + std::to_string(mod) + ":" + std::to_string(indexed ? 1 : 0), mod, [&](Builder& bd) {
+    bd.loadw(2); bd.mul_const(bd.use_const(cid)); bd.stt(0);        // V = U^-1 R^3
+    bd.loadw(3); bd.mul_extw(1); bd.mul_extw(1); bd.mul_tbl(0);     // hi = F ab^2 U^-1
+    if (indexed) bd.storew_at(5, 7); else bd.storew(5, 1);
+    bd.loadw(4); bd.mul_extw(0); bd.mul_extw(0); bd.mul_tbl(0);     // lo = G T^2 U^-1
+    if (indexed) bd.storew_at(5, 6); else bd.storew(5, 0);
+  }, &p); if (rc) return rc;
+  const uint32_t nw = m.nwords;
+  VmExt ex[8] = {mk_ext(t, nw, nw), mk_ext(ab, nw, nw), mk_ext(u_inv, nw, nw), mk_ext(f, nw, nw), mk_ext(g, nw, nw),
+                 mk_ext(out, nw, nw, out_rows), mk_ext(lo_index, 0, 0), mk_ext(hi_index, 0, 0)};   // rows >= out_rows are not written
+  return run_vm(ctx, mod, *p, ex, 8, items);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Multi-GPU: comparisons are independent, so the only exchange is the reassembly of per-rank result blocks -- one
 // RCCL all-gather over xGMI on the context's stream.  RCCL is bound at run time (dlopen): a single-GPU user never loads it, and

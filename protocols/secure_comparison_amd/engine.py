@@ -404,6 +404,38 @@ class Engine:
                                              self._ptr(bad), count))
         return prod, bad
 
+    def select_finish_cx(self, mod: Modulus, t: torch.Tensor, ab: torch.Tensor, u_inv: torch.Tensor, f: torch.Tensor, g: torch.Tensor,
+                         lo_index: torch.Tensor | None = None, hi_index: torch.Tensor | None = None,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+        """Both outputs of a compare-exchange (sc_select_finish_cx): hi = F ab^2 U^-1 and lo = G T^2 U^-1 mod m for every column and
+        row, f / g [nf][count][words], t / ab / u_inv nf * count rows.  Without index rows: out [2][nf][count][words] = (lo, hi).  With
+        lo_index / hi_index (int64 [nf][count]): the outputs of column j, item i go to rows lo_index[j][i] / hi_index[j][i] of `out`
+        (required, any contiguous array of rows of `words` words); rows at or past its end are not written."""
+        if not isinstance(f, torch.Tensor) or f.dim() != 3:
+            raise ValueError("f: expected [nfields][count][words]")
+        nf, count = f.shape[0], f.shape[1]
+        for name, x in (("t", t), ("ab", ab), ("u_inv", u_inv), ("f", f), ("g", g)):
+            self._arr(x, name, nf * count, mod.nwords)
+        if (lo_index is None) != (hi_index is None):
+            raise ValueError("lo_index, hi_index: give both or neither")
+        if lo_index is None:
+            out = self._result(out, (2, nf, count, mod.nwords))
+        else:
+            for name, x in (("lo_index", lo_index), ("hi_index", hi_index)):
+                self._arr(x, name, dtype=torch.int64)
+                if x.numel() != nf * count:
+                    raise ValueError(f"{name}: {x.numel()} items, expected {nf * count}")
+            if out is None:
+                raise ValueError("out: required with index rows")
+            self._arr(out, "out", words=mod.nwords)
+        if count == 0:
+            return out
+        self._sync_stream()
+        self._check(self.lib.sc_select_finish_cx(self.ctx, mod.id, nf, self._ptr(t), self._ptr(ab), self._ptr(u_inv), self._ptr(f),
+                                                 self._ptr(g), self._ptr(lo_index), self._ptr(hi_index), self._ptr(out),
+                                                 out.numel() // mod.nwords, count))
+        return out
+
     def modexp_shared_isone(self, mod: Modulus, x: torch.Tensor, e: int) -> torch.Tensor:
         count = self._items(x)
         self._arr(x, "x", count)

@@ -421,6 +421,17 @@ class Initiator:
 
         return await alice_argext(self, v_enc, kappa, source, engine, generator, chunks, want_max=True)
 
+    async def perform_secure_sort_batch(self, v_enc: torch.Tensor, payload: torch.Tensor | None = None, payload_bits=(),
+                                        descending: bool = False, return_indices: bool = False, kappa: int = 40, source: str = "device",
+                                        engine=None, generator=None, chunks: int = 1, max_rows: int = 65536):
+        """(sorted [B][k][2nw], payload [np][B][k][2nw] or None, indices [B][k][2nw] or None), as sorting.secure_sort_batch: the header
+        `sort_0_session_{sid}`, then per sub-batch of the network one comparison session and one selection exchange (message ids
+        `.._session_{sid}_sort_{i}`).  chunks > 1 is not supported (ValueError)."""
+        from .sorting import alice_sort
+
+        return await alice_sort(self, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks,
+                                max_rows)
+
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""
         if self.communicator is None:

@@ -302,6 +302,14 @@ class KeyHolder:
 
         await bob_rounds(self, tournament_rounds(k), None, None, kappa, source, generator, (index_bits(k),))
 
+    async def perform_secure_sort_batch(self, k: int, payload_bits=(), return_indices: bool = False, kappa: int = 40, source: str = "device",
+                                        generator=None, max_rows: int = 65536) -> None:
+        """Bob's side of Initiator.perform_secure_sort_batch over k values per row: the initiator's header must announce this k,
+        max_rows, kappa and these column widths; the schedule follows from it (sorting.sort_schedule)."""
+        from .sorting import bob_sort
+
+        await bob_sort(self, k, payload_bits, return_indices, kappa, source, generator, max_rows)
+
     async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
         message when it has been received already.  Returns the session's batch size."""

@@ -156,9 +156,8 @@ def select_mult(layout: SelectLayout, P: torch.Tensor, paillier: Paillier, rho_p
     return c.reshape(nf, count, nw2)
 
 
-def select_finish(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor, products: torch.Tensor,
-                  plain, draws: SelectDraws, paillier: Paillier) -> torch.Tensor:
-    """Alice, step 3: [[b_j + sigma (a_j - b_j)]] [nf][B][2nw] from Bob's products."""
+def select_t(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, plain, draws: SelectDraws, paillier: Paillier) -> torch.Tensor:
+    """T_j = [[sigma]]^(r_b_j + 2^w_j) [[d_j]]^r_a (1 + r_a r_b_j N) [nf * B][2nw] (step 3's unblinding factor)."""
     e = paillier.engine
     et, rab = plain
     nf, count = len(layout.widths), sigma_enc.shape[0]
@@ -166,9 +165,17 @@ def select_finish(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Te
     ew = et.shape[-1]
     x = torch.stack([sigma_enc.unsqueeze(0).expand(nf, count, nw2).reshape(nf * count, nw2), d_enc.reshape(nf * count, nw2)])
     ex = torch.stack([et.reshape(nf * count, ew), _pad_words(draws.r_a, ew).unsqueeze(0).expand(nf, count, ew).reshape(nf * count, ew)])
-    T = e.modexp_var_sq(paillier.mod_n, paillier.mod_n2, x.contiguous(), ex.contiguous(), layout.t_bits,
-                        mul_into=paillier.encrypt_raw_batch(rab.reshape(nf * count, -1)))
-    t_inv = e.modinv(paillier.mod_n2, T)
+    return e.modexp_var_sq(paillier.mod_n, paillier.mod_n2, x.contiguous(), ex.contiguous(), layout.t_bits,
+                           mul_into=paillier.encrypt_raw_batch(rab.reshape(nf * count, -1)))
+
+
+def select_finish(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor, products: torch.Tensor,
+                  plain, draws: SelectDraws, paillier: Paillier) -> torch.Tensor:
+    """Alice, step 3: [[b_j + sigma (a_j - b_j)]] [nf][B][2nw] from Bob's products."""
+    nf, count = len(layout.widths), sigma_enc.shape[0]
+    nw2 = paillier.mod_n2.nwords
+    T = select_t(layout, sigma_enc, d_enc, plain, draws, paillier)
+    t_inv = paillier.engine.modinv(paillier.mod_n2, T)
     out = paillier.add_batch(paillier.add_batch(b_enc.reshape(nf * count, nw2), products.reshape(nf * count, nw2)), t_inv)
     return out.reshape(nf, count, nw2)
 
@@ -317,7 +324,9 @@ async def _alice_compare(ini, tag, x_enc, y_enc, draws, source, generator):
     return delta, pai.add_batch(keep["z_enc"], pai.encrypt_raw_neg_batch(keep["r"]))
 
 
-async def _alice_select(ini, tag, layout, sigma, d, b, sd, source, generator):
+async def _alice_exchange(ini, tag, layout, sigma, d, sd, source, generator):
+    """Alice's selection exchange up to Bob's products: (products [nf][B][2nw], plain, draws) for select_finish or the sort's
+    compare-exchange finish."""
     from . import wire
 
     comm, pai = ini.communicator, ini.scheme_paillier
@@ -328,7 +337,12 @@ async def _alice_select(ini, tag, layout, sigma, d, b, sd, source, generator):
     await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"select_1_batch_{tag}")
     (prods,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"select_2_batch_{tag}"), dev, expect=1)
     prods = wire.expect_array(prods, (nf, count, pai.mod_n2.nwords), "[[a b_j]]")
-    return select_finish(layout, sigma, d, b, prods, plain, sd, pai)
+    return prods, plain, sd
+
+
+async def _alice_select(ini, tag, layout, sigma, d, b, sd, source, generator):
+    prods, plain, sd = await _alice_exchange(ini, tag, layout, sigma, d, sd, source, generator)
+    return select_finish(layout, sigma, d, b, prods, plain, sd, ini.scheme_paillier)
 
 
 def _no_chunks(chunks):
@@ -372,26 +386,31 @@ async def alice_argext(ini, v_enc, kappa, source, engine, generator, chunks, wan
     return vals[0].contiguous(), idx[0].contiguous()
 
 
-async def bob_rounds(kh, rounds, draws, select_draws, kappa, source, generator, payload_bits):
-    """The key holder's side: `rounds` times (comparison session, selection exchange); he expects the layout (kappa, l, payload_bits)."""
+async def _bob_select(kh, tag, layout, count, select_draws, source, generator):
+    """The key holder's selection exchange after a comparison session of `count` rows: the layout check, then his products."""
     from . import wire
 
+    comm, pai = kh.communicator, kh.scheme_paillier
+    head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"select_1_batch_{tag}"), pai.engine.device, expect=2)
+    if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] > 1 + MAX_FIELDS:
+        raise ValueError("select: malformed layout announcement")
+    announced = [int(v) for v in head.cpu().tolist()]
+    if announced != [layout.kappa, *layout.widths]:
+        raise ValueError(f"select: the initiator announces kappa and widths {announced}, this key holder expects "
+                         f"{[layout.kappa, *layout.widths]}")
+    P = wire.expect_array(P, (count, pai.mod_n2.nwords), "P")
+    rho = (select_draws.rho_products if select_draws is not None
+           else draw_select(count, layout, pai, source, generator, alice=False).rho_products)
+    prods = select_mult(layout, P, pai, rho)
+    await comm.send(kh.other_party, wire.outgoing(comm, prods), msg_id=f"select_2_batch_{tag}")
+
+
+async def bob_rounds(kh, rounds, draws, select_draws, kappa, source, generator, payload_bits):
+    """The key holder's side: `rounds` times (comparison session, selection exchange); he expects the layout (kappa, l, payload_bits)."""
     sid = await kh._open_batch_session()
-    comm, pai, l = kh.communicator, kh.scheme_paillier, kh.l_maximum_bit_length
+    pai, l = kh.scheme_paillier, kh.l_maximum_bit_length
     layout = SelectLayout(l, kappa, tuple(payload_bits), pai.public_key.n.bit_length())
-    dev = pai.engine.device
     for rnd in range(rounds):
         tag = f"session_{sid}" if not payload_bits else f"session_{sid}_round_{rnd}"
         count = await kh._batch_session(tag, None, draws, source, generator)
-        head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"select_1_batch_{tag}"), dev, expect=2)
-        if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] > 1 + MAX_FIELDS:
-            raise ValueError("select: malformed layout announcement")
-        announced = [int(v) for v in head.cpu().tolist()]
-        if announced != [layout.kappa, *layout.widths]:
-            raise ValueError(f"select: the initiator announces kappa and widths {announced}, this key holder expects "
-                             f"{[layout.kappa, *layout.widths]}")
-        P = wire.expect_array(P, (count, pai.mod_n2.nwords), "P")
-        rho = (select_draws.rho_products if select_draws is not None
-               else draw_select(count, layout, pai, source, generator, alice=False).rho_products)
-        prods = select_mult(layout, P, pai, rho)
-        await comm.send(kh.other_party, wire.outgoing(comm, prods), msg_id=f"select_2_batch_{tag}")
+        await _bob_select(kh, tag, layout, count, select_draws, source, generator)
