@@ -44,7 +44,8 @@ enum sc_status {
   SC_ERR_ARG = -1,          /* bad argument (AssertionError / ValueError at the Python layer) */
   SC_ERR_HIP = -2,          /* HIP runtime error */
   SC_ERR_NOT_INVERTIBLE = -3, /* an element has no modular inverse (gmpy2/pow raise in the reference) */
-  SC_ERR_UNSUPPORTED = -4   /* modulus too large for the compiled configurations */
+  SC_ERR_UNSUPPORTED = -4,  /* modulus too large for the compiled configurations */
+  SC_ERR_LAYOUT = -5        /* sc_keyholder_select_mult: a decrypted P exceeds the announced field layout (ValueError in Python) */
 };
 
 /* ---- context ------------------------------------------------------------------------------------ */
@@ -58,7 +59,8 @@ const char* sc_last_error(sc_ctx* ctx);
 int64_t sc_last_bad_index(sc_ctx* ctx);
 /* Bumped whenever an entry point is added, removed or changes meaning; the binding checks it (round 3: 3; round 4: 4 -- the header
  * split into sc_amd.h / sc_amd_dev.h, SC_STEP_DEFER_CHECKS and sc_ctx_check removed, sc_clock_probe and sc_ctx_policy added; round 5: 5
- * -- sc_ctx_set_pair_policy and sc_ctx_stats added in sc_amd_dev.h). */
+ * -- sc_ctx_set_pair_policy and sc_ctx_stats added in sc_amd_dev.h).  Still 5 with the selection entries (sc_initiator_select_d ..
+ * sc_initiator_cx_finish, SC_ERR_LAYOUT): they are additions, nothing that was there changed. */
 #define SC_ABI_VERSION 5
 int sc_abi_version(void);
 /* device memory helpers for callers that do not bring their own allocator */
@@ -167,6 +169,62 @@ int sc_keyholder_step4j_5(sc_ctx* ctx, int paillier_key, int dgk_key, int l, con
 int sc_initiator_step67(sc_ctx* ctx, int paillier_key, const uint64_t* delta_a_dptr, const uint32_t* delta_b_enc_dptr,
                         const uint32_t* zeta1_enc_dptr, const uint32_t* zeta2_enc_dptr, const uint64_t* rsmall_dptr,
                         const uint32_t* rshift_dptr, int flags, uint32_t* out_dptr, uint64_t count);
+
+/* ---- secure selection and compare-exchange: what selection.py / sorting.py do per step, one call each ------ */
+/* After a comparison [[delta]] = [[x <= y]] one more round trip selects between encrypted columns: for a selector [[sigma]], sigma in
+ * {0, 1}, and columns j < nfields with bases [[b_j]] and differences [[d_j]], d_j = a_j - b_j + 2^w_j, the result is
+ * [[b_j + sigma (a_j - b_j)]].  A minimum is (five comparison calls,) select_d, one_minus, select_pack | keyholder_select_mult |
+ * select_finish; a compare-exchange of a sort is select_d, cx_differences, select_pack | keyholder_select_mult | cx_finish
+ * ("Selection and sort from C").  LAYOUT: (kappa, nfields, widths_hptr) as sc_select_prep takes it -- 1 <= kappa <= 62
+ * statistical blinding bits, 1 <= nfields <= 4 columns, widths_hptr[j] = w_j >= 1 (column 0 is the compared value: w_0 = l).  Every
+ * entry checks it against the key before anything is launched (SC_ERR_ARG, sc_last_error names the column): the packed fields
+ * s + sum_j (w_j + kappa + 2), s = kappa + 1, and every product of s + w_j + kappa + 2 bits must stay below bits(N) - 1.  All
+ * ciphertext arrays are [..][count][2 nwords] modulo N^2.  Scratch comes from the context; the work runs on its stream.  Every
+ * Paillier key of sc_paillier_key_create is served: where the modulus has no pair kernel with per-row exponents the entries compose
+ * the same residues from exponentiations modulo N^2 themselves (no SC_ERR_UNSUPPORTED for that reason). */
+/* Initiator.  [[d]] = [[y - x + 2^l]] = [[z]] (1 - r N) from step 1's z_out and its draw r [count][nwords]: no inversion. */
+int sc_initiator_select_d(sc_ctx* ctx, int paillier_key, const uint32_t* z_enc_dptr, const uint32_t* r_dptr, uint32_t* d_out_dptr,
+                          uint64_t count);
+/* [[1 - c]] = (N + 1) [[c]]^-1: the selector of a minimum from [[x <= y]] (8b).  One batched inversion: synchronous like
+ * sc_initiator_step67; SC_ERR_NOT_INVERTIBLE names the element through sc_last_bad_index.  out must not overlap c. */
+int sc_paillier_one_minus(sc_ctx* ctx, int paillier_key, const uint32_t* c_dptr, uint32_t* out_dptr, uint64_t count);
+/* Initiator, compare-exchange (8c): [[d_j]] = [[G_j]] [[F_j]]^-1 (1 + 2^w_j N) for the columns j >= 1; column 0 of d_out is a copy of
+ * d_key (the comparison's own [[d]], sc_initiator_select_d).  f_enc / g_enc / d_out: [nfields][count][2 nwords].  One inversion pass
+ * over the columns j >= 1 (synchronous, SC_ERR_NOT_INVERTIBLE as above, the index counts from column 1), then one launch for all
+ * of them.  nfields = 1: the copy alone. */
+int sc_initiator_cx_differences(sc_ctx* ctx, int paillier_key, int kappa, int nfields, const int* widths_hptr, const uint32_t* f_enc_dptr,
+                                const uint32_t* g_enc_dptr, const uint32_t* d_key_dptr, uint32_t* d_out_dptr, uint64_t count);
+/* Initiator, the message P = [[sigma]] prod_j [[d_j]]^(2^off_j) (1 + R N) rho_p^N with R = r_a + sum_j 2^off_j r_b_j, and the two
+ * plaintext arrays the finish needs: e_out[j] = r_b_j + 2^w_j [nfields][count][ew] and rab_out[j] = r_a r_b_j [nfields][count][nwords]
+ * (sc_select_prep's outputs).  r_a: [count][aw], aw <= 2, below 2^kappa; r_b: [nfields][count][bw], column j below 2^(w_j + 1 + kappa);
+ * 32 ew >= max_j (w_j + kappa + 2); rho_p: [count][nwords] in [1, N).  rho_p is NOT nullable (SC_ERR_ARG): without a fresh rho_p^N
+ * the key holder could recognise the ciphertexts he sent earlier inside P. */
+int sc_initiator_select_pack(sc_ctx* ctx, int paillier_key, int kappa, int nfields, const int* widths_hptr, const uint32_t* sigma_enc_dptr,
+                             const uint32_t* d_enc_dptr, const uint32_t* r_a_dptr, int aw, const uint32_t* r_b_dptr, int bw,
+                             const uint32_t* rho_p_dptr, int ew, uint32_t* p_out_dptr, uint32_t* e_out_dptr, uint32_t* rab_out_dptr,
+                             uint64_t count);
+/* Key holder (secret key): CRT decryption of P, the field products a b_j (sc_select_split), their encryptions randomized with
+ * rho_products [nfields][count][nwords]: out [nfields][count][2 nwords].  SC_ERR_LAYOUT when a decrypted row has a bit at or above the
+ * end of the announced layout (the initiator packed a WIDER one; `out` is unspecified then).  A narrower one cannot be seen in P:
+ * compare the two players' (kappa, widths) on the wire as well.  Synchronous (the verdict is read before it returns). */
+int sc_keyholder_select_mult(sc_ctx* ctx, int paillier_key, int kappa, int nfields, const int* widths_hptr, const uint32_t* p_enc_dptr,
+                             const uint32_t* rho_products_dptr, uint32_t* out_dptr, uint64_t count);
+/* Initiator: out[j] = [[b_j + sigma (a_j - b_j)]] = [[b_j]] [[a b_j]] T_j^-1 with T_j = [[sigma]]^(e_j) [[d_j]]^(r_a) (1 + rab_j N),
+ * [nfields][count][2 nwords]; products = the key holder's answer, e / rab = sc_initiator_select_pack's.  One inversion (synchronous,
+ * SC_ERR_NOT_INVERTIBLE as above, flat index j count + i), then one launch. */
+int sc_initiator_select_finish(sc_ctx* ctx, int paillier_key, int kappa, int nfields, const int* widths_hptr, const uint32_t* sigma_enc_dptr,
+                               const uint32_t* d_enc_dptr, const uint32_t* b_enc_dptr, const uint32_t* products_dptr,
+                               const uint32_t* r_a_dptr, int aw, const uint32_t* e_dptr, int ew, const uint32_t* rab_dptr,
+                               uint32_t* out_dptr, uint64_t count);
+/* Initiator, both outputs of a compare-exchange (8c) from the selection with sigma = delta, base F and d = G - F + 2^w: T as above,
+ * U = T [[a b]], one inversion of U, then sc_select_finish_cx's launch: lo = G T^2 U^-1, hi = F ab^2 U^-1.  lo_index / hi_index
+ * (both or neither): uint64 [nfields][count], the row of out [out_rows][2 nwords] each output goes to; rows >= out_rows are not
+ * written.  Both null: out is [2][nfields][count][2 nwords] = (lo, hi) and out_rows >= 2 nfields count. */
+int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key, int kappa, int nfields, const int* widths_hptr, const uint32_t* delta_enc_dptr,
+                           const uint32_t* d_enc_dptr, const uint32_t* f_enc_dptr, const uint32_t* g_enc_dptr, const uint32_t* products_dptr,
+                           const uint32_t* r_a_dptr, int aw, const uint32_t* e_dptr, int ew, const uint32_t* rab_dptr,
+                           const uint64_t* lo_index_dptr /* nullable */, const uint64_t* hi_index_dptr /* nullable */, uint32_t* out_dptr,
+                           uint64_t out_rows, uint64_t count);
 
 /* ---- device-side CSPRNG: the random draws of a batch, generated where they are consumed ---------------- */
 /* The reference draws from Python's `secrets` (SC/initiator.py:223 permutation, :250 r, :420 delta_A, :512 rho_i) and the

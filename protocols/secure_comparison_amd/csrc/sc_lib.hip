@@ -1866,18 +1866,24 @@ int sc_modexp_var_sq(sc_ctx* ctx, int mod_m, int mod_m2, int nbases, const uint3
 }
 
 // ---- secure selection: the plaintext-word halves of the two players (k_select_prep / k_select_split) -------------------------------
+// SelectLayout.__post_init__ (selection.py) on the host -- the one copy of the rule every selection entry checks before it launches
+// anything (sc_select_prep / sc_select_split here, the scheme-level entries of sc_schemes.h); every refusal names its column
 static int select_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int nfields, const int* widths, SelLayout* lay) {
-  if (kappa < 1 || kappa > 62 || nfields < 1 || nfields > SEL_MAX_FIELDS || !widths) return fail(ctx, SC_ERR_ARG, "%s: bad layout", who);
+  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
+  if (!widths || nfields < 1 || nfields > SEL_MAX_FIELDS)
+    return fail(ctx, SC_ERR_ARG, "%s: %d columns: expected 1 .. %d with their widths", who, nfields, SEL_MAX_FIELDS);
   lay->s = kappa + 1; lay->nf = nfields;
   int off = lay->s;
   for (int j = 0; j < nfields; j++) {
-    if (widths[j] < 1 || widths[j] > 4096) return fail(ctx, SC_ERR_ARG, "%s: bad field width %d", who, widths[j]);
+    if (widths[j] < 1 || widths[j] > 4096) return fail(ctx, SC_ERR_ARG, "%s: column %d: width %d: expected 1 .. 4096", who, j, widths[j]);
     lay->width[j] = widths[j]; lay->fbits[j] = widths[j] + kappa + 2; lay->off[j] = off;
-    if (lay->s + lay->fbits[j] >= nbits_n - 1) return fail(ctx, SC_ERR_ARG, "%s: the product of field %d does not fit below N", who, j);
+    if (lay->s + lay->fbits[j] >= nbits_n - 1)
+      return fail(ctx, SC_ERR_ARG, "%s: column %d: the product a * b (%d bits) does not fit below a %d-bit N", who, j, lay->s + lay->fbits[j], nbits_n);
     off += lay->fbits[j];
+    if (off >= nbits_n - 1)
+      return fail(ctx, SC_ERR_ARG, "%s: column %d: the packed fields (%d bits) do not fit below a %d-bit N (kappa = %d)", who, j, off, nbits_n, kappa);
   }
   lay->end = off;
-  if (off >= nbits_n - 1) return fail(ctx, SC_ERR_ARG, "%s: the packed fields (%d bits) do not fit below N (%d bits)", who, off, nbits_n);
   return SC_OK;
 }
 

@@ -89,7 +89,12 @@ struct DgkKey {
 }  // namespace
 
 // (the key tables live in the context; declared here, stored through the pointers below)
-struct sc_scheme_keys { std::vector<PaillierKey> paillier; std::vector<DgkKey> dgk; };
+struct sc_scheme_keys {
+  std::vector<PaillierKey> paillier; std::vector<DgkKey> dgk;
+  std::map<int, int> pow2_exps;      // bits -> the registered exponent 2^bits (the selection's Horner chain)
+  uint32_t* select_verdict = nullptr; // pinned word the key holder's split kernel writes (sc_keyholder_select_mult)
+  ~sc_scheme_keys() { if (select_verdict) (void)hipHostFree(select_verdict); }
+};
 
 namespace {
 
@@ -697,6 +702,287 @@ int sc_initiator_step67(sc_ctx* ctx, int paillier_key_id, const uint64_t* delta_
   VmExt ex[8] = {mk_ext(zeta1_enc, w2, w2), mk_ext(zeta2_enc, w2, w2), mk_ext(inv, w2, w2), mk_ext(delta_b_enc, w2, w2),
                  mk_ext(rsmall, 2, 2), mk_ext(delta_a, 2, 2), mk_ext(rshift, k.nw, k.nw), mk_ext(out, w2, w2)};
   return run_vm(ctx, k.mod_n2, *p, ex, 8, count);
+}
+
+// ---- secure selection and compare-exchange -----------------------------------------------------------------
+// What selection.py / sorting.py used to compose from the primitives, one call per protocol step: the field layout, the Horner chain
+// of shared-exponent squarings, T_j with per-row exponents (pair kernel, or exponentiations modulo N^2 where the modulus has no
+// per-row pair instance), and the two finishes.  Temporaries TMP_SEL_*; the callees' own (TMP_S_A .. TMP_S_D, TMP_PAIR) are not held
+// across their calls.
+enum SelectTmp { TMP_SEL_A = 49, TMP_SEL_B, TMP_SEL_C, TMP_SEL_D, TMP_SEL_E, TMP_SEL_F };
+
+// the layout check of every entry, against the key's N (select_layout, sc_lib.hip: the one copy of the rule)
+static int sel_layout(sc_ctx* ctx, const char* who, const PaillierKey& k, int kappa, int nf, const int* widths, SelLayout* lay) {
+  return select_layout(ctx, who, big_bits(k.n), kappa, nf, widths, lay);
+}
+// one pinned, device-visible word per context for sc_keyholder_select_mult's verdict (freed with the context's other allocations)
+static int select_verdict_word(sc_ctx* ctx, uint32_t** out) {
+  auto* ks = keys_of(ctx);
+  if (!ks->select_verdict) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipHostMalloc((void**)&ks->select_verdict, sizeof(uint32_t), hipHostMallocMapped));
+  }
+  *out = ks->select_verdict;
+  return SC_OK;
+}
+static int sel_t_bits(const SelLayout& lay) { int b = 0; for (int j = 0; j < lay.nf; j++) b = std::max(b, lay.fbits[j]); return b; }
+
+// 1 + v N for v < N (words of N): a residue modulo N^2
+static Big one_plus_vn(const Big& v, const Big& n) {
+  Big r = big_fit(big_mul(big_fit(v, n.size()), n), 2 * n.size());
+  for (size_t i = 0; i < r.size() && ++r[i] == 0; i++) {}
+  return r;
+}
+static Big pow2_words(int bit, size_t words) { Big r(words, 0); r[bit >> 5] = 1u << (bit & 31); return r; }
+
+// x^(2^bits) * mul_into mod N^2 (selection._pow2_shared): the exponent is registered once per context
+static int sel_pow2(sc_ctx* ctx, const PaillierKey& k, int bits, const uint32_t* x, const uint32_t* mul_into, uint32_t* out, uint64_t count) {
+  auto& cache = keys_of(ctx)->pow2_exps;
+  auto it = cache.find(bits);
+  if (it == cache.end()) {
+    int id;
+    int rc = reg_exp(ctx, pow2_words(bits, (size_t)bits / 32 + 1), &id); if (rc) return rc;
+    it = cache.emplace(bits, id).first;
+  }
+  if (k.pairs && sc_mod_supports_sq(ctx, k.mod_n) == 1) return sc_modexp_shared_sq(ctx, k.mod_n, k.mod_n2, it->second, x, 2 * k.nw, mul_into, out, count);
+  return sc_modexp_shared(ctx, k.mod_n2, it->second, x, 2 * k.nw, mul_into, out, count);
+}
+
+// T_j = [[sigma]]^(e_j) [[d_j]]^(r_a) (1 + rab_j N) for the flat items j count + i (selection.select_t): t_out [nf count][2 nw]
+static int sel_t(sc_ctx* ctx, const PaillierKey& k, const SelLayout& lay, const uint32_t* sigma, const uint32_t* d, const uint32_t* r_a, int aw,
+                 const uint32_t* e, int ew, const uint32_t* rab, uint32_t* t_out, uint64_t count) {
+  const int nf = lay.nf, w2 = 2 * k.nw, ebits = sel_t_bits(lay);
+  const uint64_t items = (uint64_t)nf * count;
+  uint32_t *x, *ex, *mi;
+  int rc = tmp_words(ctx, TMP_SEL_A, 2 * items * w2, &x); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, 2 * items * ew, &ex); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, items * w2, &mi); if (rc) return rc;
+  // bases [2][nf count]: sigma for every column, then d; exponents likewise: e, then r_a (zero-extended to ew words) for every column.
+  // These are the copies the Python composition made (torch.stack / expand): sc_modexp_var_sq reads its bases as rows of one array
+  // and an item cannot address "its row modulo count".  A variant of the pair program with one operand per base and a broadcast
+  // period would save about 2 nf count 2nw words of traffic per call; against the exponentiations that is noise, so it is left out.
+  for (int j = 0; j < nf; j++)
+    HIPCHK(ctx, hipMemcpyAsync(x + (size_t)j * count * w2, sigma, (size_t)count * w2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(x + items * w2, d, items * w2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ex, e, items * ew * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  uint32_t* ex_a = ex + items * ew;
+  const int cw = std::min(aw, ew);            // r_a < 2^kappa < 2^(32 ew): words past ew are zero
+  if (cw != ew) HIPCHK(ctx, hipMemsetAsync(ex_a, 0, items * ew * 4, ctx->stream));
+  for (int j = 0; j < nf; j++)
+    HIPCHK(ctx, hipMemcpy2DAsync(ex_a + (size_t)j * count * ew, (size_t)ew * 4, r_a, (size_t)aw * 4, (size_t)cw * 4, count, hipMemcpyDeviceToDevice, ctx->stream));
+  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, rab, k.nw, mi, items); if (rc) return rc;
+  rc = k.pairs ? sc_modexp_var_sq(ctx, k.mod_n, k.mod_n2, 2, x, w2, ex, ew, ebits, mi, t_out, items) : SC_ERR_UNSUPPORTED;
+  if (rc != SC_ERR_UNSUPPORTED) return rc;
+  // no pair kernel with per-row exponents for this modulus: the same residues from exponentiations modulo N^2
+  rc = sc_modexp_var(ctx, k.mod_n2, x, ex, ew, ebits, -1, nullptr, 0, t_out, items); if (rc) return rc;
+  rc = sc_modmul(ctx, k.mod_n2, mi, w2, t_out, w2, mi, items); if (rc) return rc;
+  rc = sc_modexp_var(ctx, k.mod_n2, x + items * w2, ex_a, ew, ebits, -1, nullptr, 0, t_out, items); if (rc) return rc;
+  return sc_modmul(ctx, k.mod_n2, mi, w2, t_out, w2, t_out, items);
+}
+
+static int sel_finish_args(sc_ctx* ctx, const char* who, const PaillierKey* kp, const SelLayout& lay, int aw, int ew, bool ptrs_ok) {
+  if (!kp || !ptrs_ok || aw < 1 || aw > 2 || ew < 1) return fail(ctx, SC_ERR_ARG, "%s: bad argument", who);
+  if (32 * ew < sel_t_bits(lay)) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, sel_t_bits(lay));
+  return SC_OK;
+}
+
+int sc_initiator_select_d(sc_ctx* ctx, int paillier_key_id, const uint32_t* z_enc, const uint32_t* r, uint32_t* d_out, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !z_enc || !r || !d_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_d: bad argument");
+  const PaillierKey k = *kp;
+  const int w2 = 2 * k.nw;
+  const Prog* p;
+  int rc = cached_prog(ctx, "seld:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {
+    const int cn = bd.use_const(k.cst_n);
+    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.neg(); bd.add1();       // [[-r]] = 1 - r N
+    bd.mul_const(0); bd.mul_extw(0);                                      // times [[z]] = [[y - x + 2^l + r]]
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(z_enc, w2, w2), mk_ext(r, k.nw, k.nw), mk_ext(d_out, w2, w2)};
+  return run_vm(ctx, k.mod_n2, *p, ex, 3, count);
+}
+
+int sc_paillier_one_minus(sc_ctx* ctx, int paillier_key_id, const uint32_t* c, uint32_t* out, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !c || !out) return fail(ctx, SC_ERR_ARG, "sc_paillier_one_minus: bad argument");
+  const PaillierKey k = *kp;
+  int cst_g;
+  int rc = reg_const(ctx, k.mod_n2, one_plus_vn(Big(1, 1), k.n), &cst_g); if (rc) return rc;      // g = N + 1
+  rc = sc_modinv(ctx, k.mod_n2, c, out, count, nullptr); if (rc) return rc;
+  return sc_modmul_const(ctx, k.mod_n2, out, cst_g, out, count);
+}
+
+int sc_initiator_cx_differences(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* f_enc,
+                                const uint32_t* g_enc, const uint32_t* d_key, uint32_t* d_out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_differences: bad key");
+  const PaillierKey k = *kp;
+  SelLayout lay;
+  int rc = sel_layout(ctx, "sc_initiator_cx_differences", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  if (!f_enc || !g_enc || !d_key || !d_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_differences: bad argument");
+  const int w2 = 2 * k.nw, np = nfields - 1;
+  const size_t col = (size_t)count * w2;
+  HIPCHK(ctx, hipMemcpyAsync(d_out, d_key, col * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (np == 0) return SC_OK;
+  const uint64_t items = (uint64_t)np * count;
+  uint32_t* finv;
+  rc = tmp_words(ctx, TMP_SEL_A, items * w2, &finv); if (rc) return rc;
+  rc = sc_modinv(ctx, k.mod_n2, f_enc + col, finv, items, nullptr); if (rc) return rc;
+  // One launch over the np * count flat items of the columns j >= 1: G_j F_j^-1 c_j with c_j = 1 + 2^w_j N.  The interpreter takes
+  // nothing from an item's number but the `limit` of an operand (items at or past it read the residue 1), so the item's column picks
+  // its constant through limits: broadcast operand t holds c_(t+1) / c_(t+2) for the items below (t + 1) count, and every item takes
+  // the last column's constant -- a column's factors telescope to its own c_j.  One product per column after an item's own.
+  const Mod& m2 = ctx->mods[k.mod_n2];
+  const Big& n2 = m2.n;
+  int cid_last, cid_ratio[SEL_MAX_FIELDS] = {-1, -1, -1, -1};
+  rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one_plus_vn(pow2_words(lay.width[np], k.n.size()), k.n), n2, m2.W * m2.S), &cid_last);   // c_np R
+  if (rc) return rc;
+  for (int t = 0; t + 1 < np; t++) {          // c_(t+1) / c_(t+2) = 1 + (2^w_(t+1) - 2^w_(t+2)) N  (mod N^2)
+    Big a = pow2_words(lay.width[t + 1], k.n.size()), b = pow2_words(lay.width[t + 2], k.n.size());
+    if (big_cmp(a, b) >= 0) big_sub(a, b); else { big_sub(b, a); a = k.n; big_sub(a, b); }
+    rc = sc_const_create_cached(ctx, k.mod_n2, one_plus_vn(a, k.n), &cid_ratio[t]); if (rc) return rc;
+  }
+  const Prog* p;
+  rc = cached_prog(ctx, "cxdiff:" + std::to_string(k.mod_n2) + ":" + std::to_string(np) + ":" + std::to_string(cid_last), k.mod_n2, [&](Builder& bd) {
+    bd.loadw(0);
+    for (int t = 0; t + 1 < np; t++) bd.mul_extl(3 + t);                  // times c_(t+1) / c_(t+2) below (t + 1) count, else times 1
+    bd.mul_const(bd.use_const(cid_last));                                 // G c_j R
+    bd.mul_extw(1);                                                       // G c_j F^-1
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[5] = {mk_ext(g_enc + col, w2, w2), mk_ext(finv, w2, w2), mk_ext(d_out + col, w2, w2), mk_ext(nullptr, 0, 0), mk_ext(nullptr, 0, 0)};
+  for (int t = 0; t + 1 < np; t++) ex[3 + t] = mk_ext(ctx->consts[cid_ratio[t]].d_limbs, 0, (uint32_t)m2.S, (uint64_t)(t + 1) * count);
+  return run_vm(ctx, k.mod_n2, *p, ex, 5, items);
+}
+
+int sc_initiator_select_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* sigma_enc,
+                             const uint32_t* d_enc, const uint32_t* r_a, int aw, const uint32_t* r_b, int bw, const uint32_t* rho_p, int ew,
+                             uint32_t* p_out, uint32_t* e_out, uint32_t* rab_out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: bad key");
+  const PaillierKey k = *kp;
+  SelLayout lay;
+  int rc = sel_layout(ctx, "sc_initiator_select_pack", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: rho_p is required: P must carry a fresh rho^N");
+  if (!sigma_enc || !d_enc || !r_a || !r_b || !p_out || !e_out || !rab_out || aw < 1 || aw > 2 || bw < 1 || bw > k.nw || ew < 1)
+    return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: bad argument");
+  if (32 * ew < sel_t_bits(lay)) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: exponent rows of %d words are too narrow for %d bits", ew, sel_t_bits(lay));
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw;
+  const size_t col = (size_t)count * w2;
+  uint32_t *R, *m, *acc;
+  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &R); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, col, &m); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, 2 * col, &acc); if (rc) return rc;
+  if (launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_select_pack: launch failed");
+  const Prog* p;
+  rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {
+    const int cn = bd.use_const(k.cst_n);
+    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
+    bd.mul_const(0); bd.mul_extw(0);                                      // [[sigma + R]]
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(sigma_enc, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(m, w2, w2)};
+  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, count); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, paillier_key_id, m, rho_p, m, count); if (rc) return rc;      // * rho_p^N
+  // prod_j [[d_j]]^(2^off_j): the exponents are shared by the batch, so Horner from the top column with squarings only
+  const uint32_t* t = d_enc + (size_t)(nfields - 1) * col;
+  for (int j = nfields - 1; j >= 0; j--) {
+    uint32_t* dst = j == 0 ? p_out : acc + (size_t)(j & 1) * col;
+    rc = sel_pow2(ctx, k, lay.off[j] - (j > 0 ? lay.off[j - 1] : 0), t, j > 0 ? d_enc + (size_t)(j - 1) * col : m, dst, count); if (rc) return rc;
+    t = dst;
+  }
+  return SC_OK;
+}
+
+int sc_keyholder_select_mult(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* p_enc,
+                             const uint32_t* rho_products, uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_select_mult: needs the secret key");
+  const PaillierKey k = *kp;
+  SelLayout lay;
+  int rc = sel_layout(ctx, "sc_keyholder_select_mult", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  if (!p_enc || !rho_products || !out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_select_mult: bad argument");
+  const uint64_t items = (uint64_t)nfields * count;
+  uint32_t *pl, *prod, *c;
+  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &pl); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, items * k.nw, &prod); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, items * 2 * k.nw, &c); if (rc) return rc;
+  // the verdict word lives in pinned host memory the kernel writes itself (like the inversion's verdicts: no copy back) -- a word
+  // of its own, so nothing a callee does with the inversion's status words (status_words may free and regrow them) can touch it
+  uint32_t* bad;
+  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
+  *(volatile uint32_t*)bad = 0;             // (an earlier call has waited for its kernels before it returned)
+  rc = sc_paillier_decrypt(ctx, paillier_key_id, p_enc, pl, count); if (rc) return rc;
+  if (launch_select_split(ctx->stream, pl, k.nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_keyholder_select_mult: launch failed");
+  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, prod, k.nw, c, items); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, paillier_key_id, c, rho_products, out, items); if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (*(volatile uint32_t*)bad)
+    return fail(ctx, SC_ERR_LAYOUT, "select: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)");
+  return SC_OK;
+}
+
+int sc_initiator_select_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* sigma_enc,
+                               const uint32_t* d_enc, const uint32_t* b_enc, const uint32_t* products, const uint32_t* r_a, int aw,
+                               const uint32_t* e, int ew, const uint32_t* rab, uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_finish: bad key");
+  const PaillierKey k = *kp;
+  SelLayout lay;
+  int rc = sel_layout(ctx, "sc_initiator_select_finish", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  rc = sel_finish_args(ctx, "sc_initiator_select_finish", kp, lay, aw, ew, sigma_enc && d_enc && b_enc && products && r_a && e && rab && out); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw;
+  const uint64_t items = (uint64_t)nfields * count;
+  uint32_t *T, *t_inv;
+  rc = tmp_words(ctx, TMP_SEL_D, items * w2, &T); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_E, items * w2, &t_inv); if (rc) return rc;
+  rc = sel_t(ctx, k, lay, sigma_enc, d_enc, r_a, aw, e, ew, rab, T, count); if (rc) return rc;
+  rc = sc_modinv(ctx, k.mod_n2, T, t_inv, items, nullptr); if (rc) return rc;
+  // one launch: b ab T^-1 -- the lift b R^2, then the two Montgomery products
+  const Mod& m2 = ctx->mods[k.mod_n2];
+  int cid;
+  { Big one(m2.nwords, 0); one[0] = 1; rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one, m2.n, 2 * m2.W * m2.S), &cid); if (rc) return rc; }   // R^2 mod N^2
+  const Prog* p;
+  rc = cached_prog(ctx, "selfin:" + std::to_string(k.mod_n2), k.mod_n2, [&](Builder& bd) {
+    bd.loadw(0); bd.mul_const(bd.use_const(cid));                         // b R^2
+    bd.mul_extw(1); bd.mul_extw(2);                                       // b ab T^-1
+    bd.storew(3);
+  }, &p); if (rc) return rc;
+  VmExt ex[4] = {mk_ext(b_enc, w2, w2), mk_ext(products, w2, w2), mk_ext(t_inv, w2, w2), mk_ext(out, w2, w2)};
+  return run_vm(ctx, k.mod_n2, *p, ex, 4, items);
+}
+
+int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* delta_enc,
+                           const uint32_t* d_enc, const uint32_t* f_enc, const uint32_t* g_enc, const uint32_t* products, const uint32_t* r_a,
+                           int aw, const uint32_t* e, int ew, const uint32_t* rab, const uint64_t* lo_index, const uint64_t* hi_index,
+                           uint32_t* out, uint64_t out_rows, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_finish: bad key");
+  const PaillierKey k = *kp;
+  SelLayout lay;
+  int rc = sel_layout(ctx, "sc_initiator_cx_finish", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  rc = sel_finish_args(ctx, "sc_initiator_cx_finish", kp, lay, aw, ew,
+                       delta_enc && d_enc && f_enc && g_enc && products && r_a && e && rab && out && (!lo_index) == (!hi_index)); if (rc) return rc;
+  const uint64_t items = (uint64_t)nfields * count;
+  if (!lo_index && out_rows < 2 * items)
+    return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_finish: out holds %llu rows, the contiguous [2][nf][count] form needs %llu",
+                (unsigned long long)out_rows, (unsigned long long)(2 * items));
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw;
+  uint32_t *T, *U, *u_inv;
+  rc = tmp_words(ctx, TMP_SEL_D, items * w2, &T); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_E, items * w2, &U); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_F, items * w2, &u_inv); if (rc) return rc;
+  rc = sel_t(ctx, k, lay, delta_enc, d_enc, r_a, aw, e, ew, rab, T, count); if (rc) return rc;
+  rc = sc_modmul(ctx, k.mod_n2, T, w2, products, w2, U, items); if (rc) return rc;
+  rc = sc_modinv(ctx, k.mod_n2, U, u_inv, items, nullptr); if (rc) return rc;
+  return sc_select_finish_cx(ctx, k.mod_n2, nfields, T, products, u_inv, f_enc, g_enc, lo_index, hi_index, out, out_rows, count);
 }
 
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {

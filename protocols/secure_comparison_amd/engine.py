@@ -133,7 +133,7 @@ class Engine:
         if rc == 0:
             return
         msg = self.lib.sc_last_error(self.ctx).decode()
-        if rc == -1:
+        if rc in (-1, -5):          # SC_ERR_ARG, SC_ERR_LAYOUT
             raise ValueError(msg)
         if rc == -3:
             raise NotInvertibleError(msg, int(self.lib.sc_last_bad_index(self.ctx)))
@@ -887,6 +887,138 @@ class Engine:
         rc = self.lib.sc_initiator_step67(self.ctx, key.id, self._ptr(delta_a), self._ptr(delta_b_enc), self._ptr(zeta1_enc), self._ptr(zeta2_enc),
                                           self._ptr(rsmall), self._ptr(rshift), 0, self._ptr(out), count)
         self._check(rc)
+        return out
+
+    # ------------------------------------------------------------------ secure selection and compare-exchange (one library call each)
+    @staticmethod
+    def _widths(widths):
+        wa = np.array([int(w) for w in widths], dtype=np.int32)
+        return wa, wa.ctypes.data_as(C.c_void_p)
+
+    def _columns(self, t: torch.Tensor, name: str, nf: int, count: int, words: int | None) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != nf or t.shape[1] != count:
+            raise ValueError(f"{name}: expected [{nf}][{count}][words]")
+        return self._arr(t, name, nf * count, words)
+
+    def initiator_select_d(self, key: PaillierKey, z_enc: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+        """[[d]] = [[z]] (1 - r N) from step 1's [[z]] and r (sc_initiator_select_d)."""
+        count, nw = self._items(z_enc), key.mod_n.nwords
+        self._arr(z_enc, "z_enc", count, 2 * nw)
+        self._arr(r, "r", count, nw)
+        out = self.empty(count, 2 * nw)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_select_d(self.ctx, key.id, self._ptr(z_enc), self._ptr(r), self._ptr(out), count))
+        return out
+
+    def paillier_one_minus(self, key: PaillierKey, c: torch.Tensor) -> torch.Tensor:
+        """[[1 - c]] = (N + 1) [[c]]^-1 (sc_paillier_one_minus; one batched inversion)."""
+        count, nw = self._items(c), key.mod_n.nwords
+        self._arr(c, "c", count, 2 * nw)
+        out = self.empty(count, 2 * nw)
+        self._sync_stream()
+        self._check(self.lib.sc_paillier_one_minus(self.ctx, key.id, self._ptr(c), self._ptr(out), count))
+        return out
+
+    def initiator_cx_differences(self, key: PaillierKey, kappa: int, widths, f_enc: torch.Tensor, g_enc: torch.Tensor,
+                                 d_key: torch.Tensor) -> torch.Tensor:
+        """[[d_j]] [nf][count][2nw] of a compare-exchange: column 0 = d_key, the others [[G_j]] [[F_j]]^-1 (1 + 2^w_j N)
+        (sc_initiator_cx_differences: one inversion pass, one launch)."""
+        nf, nw = len(widths), key.mod_n.nwords
+        count = self._items(d_key)
+        self._columns(f_enc, "f_enc", nf, count, 2 * nw)
+        self._columns(g_enc, "g_enc", nf, count, 2 * nw)
+        self._arr(d_key, "d_key", count, 2 * nw)
+        out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(widths)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_cx_differences(self.ctx, key.id, int(kappa), nf, pw, self._ptr(f_enc), self._ptr(g_enc),
+                                                         self._ptr(d_key), self._ptr(out), count))
+        return out
+
+    def initiator_select_pack(self, key: PaillierKey, kappa: int, widths, sigma_enc: torch.Tensor, d_enc: torch.Tensor, r_a: torch.Tensor,
+                              r_b: torch.Tensor, rho_p: torch.Tensor, ew: int):
+        """The message P [count][2nw] and the finish's plaintext arrays (e [nf][count][ew], rab [nf][count][nw])
+        (sc_initiator_select_pack).  rho_p is required."""
+        nf, nw = len(widths), key.mod_n.nwords
+        count = self._items(sigma_enc)
+        self._arr(sigma_enc, "sigma_enc", count, 2 * nw)
+        self._columns(d_enc, "d_enc", nf, count, 2 * nw)
+        self._arr(r_a, "r_a", count)
+        self._columns(r_b, "r_b", nf, count, None)
+        self._arr(rho_p, "rho_p", count, nw)
+        P = self.empty(count, 2 * nw)
+        e = torch.empty((nf, count, int(ew)), dtype=torch.int32, device=self.device)
+        rab = torch.empty((nf, count, nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(widths)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_select_pack(self.ctx, key.id, int(kappa), nf, pw, self._ptr(sigma_enc), self._ptr(d_enc), self._ptr(r_a),
+                                                      r_a.shape[-1], self._ptr(r_b), r_b.shape[-1], self._ptr(rho_p), int(ew), self._ptr(P),
+                                                      self._ptr(e), self._ptr(rab), count))
+        return P, e, rab
+
+    def keyholder_select_mult(self, key: PaillierKey, kappa: int, widths, P: torch.Tensor, rho_products: torch.Tensor) -> torch.Tensor:
+        """The key holder's randomized [[a b_j]] [nf][count][2nw] from P (sc_keyholder_select_mult); ValueError when a decrypted row
+        exceeds the layout."""
+        nf, nw = len(widths), key.mod_n.nwords
+        count = self._items(P)
+        self._arr(P, "P", count, 2 * nw)
+        self._columns(rho_products, "rho_products", nf, count, nw)
+        out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(widths)
+        self._sync_stream()
+        self._check(self.lib.sc_keyholder_select_mult(self.ctx, key.id, int(kappa), nf, pw, self._ptr(P), self._ptr(rho_products), self._ptr(out), count))
+        return out
+
+    def _finish_args(self, key, widths, sigma_enc, d_enc, products, r_a, e, rab):
+        nf, nw = len(widths), key.mod_n.nwords
+        count = self._items(sigma_enc)
+        self._arr(sigma_enc, "sigma_enc", count, 2 * nw)
+        self._columns(d_enc, "d_enc", nf, count, 2 * nw)
+        self._columns(products, "products", nf, count, 2 * nw)
+        self._arr(r_a, "r_a", count)
+        self._columns(e, "e", nf, count, None)
+        self._columns(rab, "rab", nf, count, nw)
+        return nf, nw, count
+
+    def initiator_select_finish(self, key: PaillierKey, kappa: int, widths, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor,
+                                products: torch.Tensor, r_a: torch.Tensor, e: torch.Tensor, rab: torch.Tensor) -> torch.Tensor:
+        """[[b_j + sigma (a_j - b_j)]] [nf][count][2nw] from the key holder's products (sc_initiator_select_finish)."""
+        nf, nw, count = self._finish_args(key, widths, sigma_enc, d_enc, products, r_a, e, rab)
+        self._columns(b_enc, "b_enc", nf, count, 2 * nw)
+        out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(widths)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_select_finish(self.ctx, key.id, int(kappa), nf, pw, self._ptr(sigma_enc), self._ptr(d_enc), self._ptr(b_enc),
+                                                        self._ptr(products), self._ptr(r_a), r_a.shape[-1], self._ptr(e), e.shape[-1],
+                                                        self._ptr(rab), self._ptr(out), count))
+        return out
+
+    def initiator_cx_finish(self, key: PaillierKey, kappa: int, widths, delta_enc: torch.Tensor, d_enc: torch.Tensor, f_enc: torch.Tensor,
+                            g_enc: torch.Tensor, products: torch.Tensor, r_a: torch.Tensor, e: torch.Tensor, rab: torch.Tensor,
+                            lo_index: torch.Tensor | None = None, hi_index: torch.Tensor | None = None,
+                            out: torch.Tensor | None = None) -> torch.Tensor:
+        """Both outputs of a compare-exchange (sc_initiator_cx_finish); out / lo_index / hi_index as select_finish_cx."""
+        nf, nw, count = self._finish_args(key, widths, delta_enc, d_enc, products, r_a, e, rab)
+        self._columns(f_enc, "f_enc", nf, count, 2 * nw)
+        self._columns(g_enc, "g_enc", nf, count, 2 * nw)
+        if (lo_index is None) != (hi_index is None):
+            raise ValueError("lo_index, hi_index: give both or neither")
+        if lo_index is None:
+            out = self._result(out, (2, nf, count, 2 * nw))
+        else:
+            for name, x in (("lo_index", lo_index), ("hi_index", hi_index)):
+                self._arr(x, name, dtype=torch.int64)
+                if x.numel() != nf * count:
+                    raise ValueError(f"{name}: {x.numel()} items, expected {nf * count}")
+            if out is None:
+                raise ValueError("out: required with index rows")
+            self._arr(out, "out", words=2 * nw)
+        wa, pw = self._widths(widths)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_cx_finish(self.ctx, key.id, int(kappa), nf, pw, self._ptr(delta_enc), self._ptr(d_enc), self._ptr(f_enc),
+                                                    self._ptr(g_enc), self._ptr(products), self._ptr(r_a), r_a.shape[-1], self._ptr(e), e.shape[-1],
+                                                    self._ptr(rab), self._ptr(lo_index), self._ptr(hi_index), self._ptr(out),
+                                                    out.numel() // (2 * nw), count))
         return out
 
     # ------------------------------------------------------------------ device-side CSPRNG (sc_rng_*)

@@ -7,7 +7,9 @@ selection").  For a selector sigma in {0, 1} and columns j with [[b_j]] and [[d_
 2. Bob decrypts P once, splits the fields a = sigma + r_a and b_j = d_j + r_b_j and returns the fresh encryptions [[a b_j]].
 3. Alice unblinds: [[b_j + sigma (a_j - b_j)]] = [[b_j]] [[a b_j]] T_j^-1 with T_j = [[sigma]]^(r_b_j + 2^w_j) [[d_j]]^r_a (1 + r_a r_b_j N).
 
-Everything stays on the device; the exponentiations with per-row exponents run on the pair interpreter (sc_modexp_var_sq).
+Everything stays on the device.  Each step is one scheme-level library call (include/sc_amd.h: sc_initiator_select_d,
+sc_paillier_one_minus, sc_initiator_select_pack, sc_keyholder_select_mult, sc_initiator_select_finish), the same calls a C host makes;
+the exponentiations with per-row exponents run on the pair interpreter (sc_modexp_var_sq) where the modulus has such an instance.
 """
 from __future__ import annotations
 
@@ -110,74 +112,33 @@ def draw_select(count: int, layout: SelectLayout, paillier: Paillier, source: st
     return SelectDraws(r_a=r_a, r_b=r_b, rho_p=rho_p, rho_products=rho_q)
 
 
-def _pow2_shared(paillier: Paillier, x: torch.Tensor, bits: int, mul_into: torch.Tensor) -> torch.Tensor:
-    """x^(2^bits) * mul_into mod N^2 (sc_modexp_shared_sq; sc_modexp_shared modulo N^2 where the pair arithmetic does not fit)."""
-    e = paillier.engine
-    if e.supports_sq(paillier.mod_n):
-        return e.modexp_shared_sq(paillier.mod_n, paillier.mod_n2, x, 1 << bits, mul_into=mul_into)
-    return e.modexp_shared(paillier.mod_n2, x, 1 << bits, mul_into=mul_into)
-
-
-def _pad_words(t: torch.Tensor, words: int) -> torch.Tensor:
-    return t if t.shape[-1] == words else torch.nn.functional.pad(t, (0, words - t.shape[-1])).contiguous()
-
-
 # ---- the three steps --------------------------------------------------------------------------------------------------------------
 def select_pack(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, draws: SelectDraws, paillier: Paillier):
     """Alice, step 1: P [B][2nw] from [[sigma]] [B][2nw] and [[d_j]] [nf][B][2nw]; returns (P, (e, rab)) -- the latter is what
-    select_finish needs."""
-    e = paillier.engine
+    select_finish needs (sc_initiator_select_pack)."""
     nf, count = len(layout.widths), sigma_enc.shape[0]
     if d_enc.dim() != 3 or d_enc.shape[0] != nf or d_enc.shape[1] != count:
         raise ValueError(f"d_enc: expected [{nf}][{count}][words]")
     ew = (layout.t_bits + 31) // 32
-    R, et, rab = e.select_prep(paillier.public_key.n, layout.kappa, layout.widths, draws.r_a, draws.r_b, ew)
-    m = paillier.add_batch(sigma_enc, paillier.encrypt_raw_batch(R))            # [[sigma + R]]
-    m = paillier.randomize_batch(m, draws.rho_p)                                 # * rho^N: fresh randomness Bob cannot trace
-    # prod_j [[d_j]]^(2^off_j): exponents shared by the batch, so Horner from the top column with squarings only
-    offs = layout.offsets
-    t = d_enc[nf - 1]
-    for j in range(nf - 1, -1, -1):
-        t = _pow2_shared(paillier, t, offs[j] - (offs[j - 1] if j > 0 else 0), d_enc[j - 1] if j > 0 else m)
-    return t, (et, rab)
+    P, et, rab = paillier.engine.initiator_select_pack(paillier.key, layout.kappa, layout.widths, sigma_enc, d_enc.contiguous(), draws.r_a,
+                                                       draws.r_b, draws.rho_p, ew)
+    return P, (et, rab)
 
 
 def select_mult(layout: SelectLayout, P: torch.Tensor, paillier: Paillier, rho_products: torch.Tensor) -> torch.Tensor:
-    """Bob, step 2: one CRT decryption of P, the field products a * b_j, encrypted and freshly randomized: [nf][B][2nw].
-    ValueError when a decrypted row does not fit the announced layout (the players disagree on kappa or the widths)."""
-    e = paillier.engine
-    nf, count = len(layout.widths), P.shape[0]
-    p = paillier.decrypt_raw_batch(P)
-    prod, bad = e.select_split(paillier.public_key.n, layout.kappa, layout.widths, p)
-    nw2 = paillier.mod_n2.nwords
-    c = paillier.randomize_batch(paillier.encrypt_raw_batch(prod.reshape(nf * count, -1)), rho_products.reshape(nf * count, -1))
-    if int(bad.item()):
-        raise ValueError("select: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)")
-    return c.reshape(nf, count, nw2)
-
-
-def select_t(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, plain, draws: SelectDraws, paillier: Paillier) -> torch.Tensor:
-    """T_j = [[sigma]]^(r_b_j + 2^w_j) [[d_j]]^r_a (1 + r_a r_b_j N) [nf * B][2nw] (step 3's unblinding factor)."""
-    e = paillier.engine
-    et, rab = plain
-    nf, count = len(layout.widths), sigma_enc.shape[0]
-    nw2 = paillier.mod_n2.nwords
-    ew = et.shape[-1]
-    x = torch.stack([sigma_enc.unsqueeze(0).expand(nf, count, nw2).reshape(nf * count, nw2), d_enc.reshape(nf * count, nw2)])
-    ex = torch.stack([et.reshape(nf * count, ew), _pad_words(draws.r_a, ew).unsqueeze(0).expand(nf, count, ew).reshape(nf * count, ew)])
-    return e.modexp_var_sq(paillier.mod_n, paillier.mod_n2, x.contiguous(), ex.contiguous(), layout.t_bits,
-                           mul_into=paillier.encrypt_raw_batch(rab.reshape(nf * count, -1)))
+    """Bob, step 2: one CRT decryption of P, the field products a * b_j, encrypted and freshly randomized: [nf][B][2nw]
+    (sc_keyholder_select_mult).  ValueError when a decrypted row does not fit the announced layout (the players disagree on kappa
+    or the widths)."""
+    return paillier.engine.keyholder_select_mult(paillier.key, layout.kappa, layout.widths, P, rho_products.contiguous())
 
 
 def select_finish(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor, products: torch.Tensor,
                   plain, draws: SelectDraws, paillier: Paillier) -> torch.Tensor:
-    """Alice, step 3: [[b_j + sigma (a_j - b_j)]] [nf][B][2nw] from Bob's products."""
-    nf, count = len(layout.widths), sigma_enc.shape[0]
-    nw2 = paillier.mod_n2.nwords
-    T = select_t(layout, sigma_enc, d_enc, plain, draws, paillier)
-    t_inv = paillier.engine.modinv(paillier.mod_n2, T)
-    out = paillier.add_batch(paillier.add_batch(b_enc.reshape(nf * count, nw2), products.reshape(nf * count, nw2)), t_inv)
-    return out.reshape(nf, count, nw2)
+    """Alice, step 3: [[b_j + sigma (a_j - b_j)]] [nf][B][2nw] from Bob's products (sc_initiator_select_finish): T_j =
+    [[sigma]]^(r_b_j + 2^w_j) [[d_j]]^r_a (1 + r_a r_b_j N), one inversion, one launch."""
+    et, rab = plain
+    return paillier.engine.initiator_select_finish(paillier.key, layout.kappa, layout.widths, sigma_enc, d_enc.contiguous(), b_enc.contiguous(),
+                                                   products.contiguous(), draws.r_a, et, rab)
 
 
 def select_batch(layout: SelectLayout, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor, alice_paillier: Paillier,
@@ -200,13 +161,12 @@ def _compare(x_enc, y_enc, l, ap, ad, bp, bd, draws):
     draws = draws if draws is not None else _comparison_draws(x_enc.shape[0], l, ap, ad, bp, bd)
     trace = BatchTrace()
     delta = secure_comparison_batch(x_enc, y_enc, l, ap, ad, bp, bd, draws, trace=trace)
-    d = ap.add_batch(trace.z_enc, ap.encrypt_raw_neg_batch(draws.r))
-    return delta, d
+    return delta, ap.engine.initiator_select_d(ap.key, trace.z_enc, draws.r)
 
 
 def _one_minus(paillier: Paillier, c: torch.Tensor) -> torch.Tensor:
-    """[[1 - c]] = g [[c]]^-1 (one batched inversion)."""
-    return paillier.engine.modmul_const(paillier.mod_n2, paillier.neg_batch(c), paillier.public_key.n + 1)
+    """[[1 - c]] = g [[c]]^-1 (one batched inversion; sc_paillier_one_minus)."""
+    return paillier.engine.paillier_one_minus(paillier.key, c)
 
 
 def _minmax(x_enc, y_enc, l, ap, ad, bp, bd, draws, select_draws, kappa, want_max):
@@ -321,7 +281,7 @@ async def _alice_compare(ini, tag, x_enc, y_enc, draws, source, generator):
     keep = {}
     delta = await ini._batch_session(tag, x_enc, y_enc, draws, source, generator, None, keep=keep)
     pai = ini.scheme_paillier
-    return delta, pai.add_batch(keep["z_enc"], pai.encrypt_raw_neg_batch(keep["r"]))
+    return delta, pai.engine.initiator_select_d(pai.key, keep["z_enc"], keep["r"])
 
 
 async def _alice_exchange(ini, tag, layout, sigma, d, sd, source, generator):

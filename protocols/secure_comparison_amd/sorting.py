@@ -19,7 +19,7 @@ from .batch import BatchDraws
 from .flags import check_l
 from .schemes import DGK, Paillier
 from .selection import (MAX_FIELDS, SelectDraws, SelectLayout, _alice_compare, _alice_exchange, _bob_select, _compare, _no_chunks,
-                        draw_select, index_bits, select_mult, select_pack, select_t)
+                        draw_select, index_bits, select_mult, select_pack)
 
 MAX_K = 1024        # values per row
 
@@ -85,28 +85,21 @@ def _sort_steps(buf: torch.Tensor, B: int, k: int, max_rows: int, descending: bo
 # ---- the compare-exchange ----------------------------------------------------------------------------------------------------------
 def cx_differences(paillier: Paillier, layout: SelectLayout, f_enc: torch.Tensor, g_enc: torch.Tensor, d_key: torch.Tensor) -> torch.Tensor:
     """[[d_j]] = [[G_j - F_j + 2^w_j]] [nf][count][2nw]: the key column's is the comparison's own [[d]]; the other columns' are
-    [[G_j]] [[F_j]]^-1 (1 + 2^w_j N), their inverses from one batched inversion."""
-    nf, count, nw2 = f_enc.shape
-    if nf == 1:
-        return d_key.unsqueeze(0)
-    e, n = paillier.engine, paillier.public_key.n
-    q = paillier.add_batch(g_enc[1:].reshape(-1, nw2), paillier.neg_batch(f_enc[1:].reshape(-1, nw2))).reshape(nf - 1, count, nw2)
-    return torch.stack([d_key] + [e.modmul_const(paillier.mod_n2, q[j - 1], 1 + (1 << w) * n)
-                                  for j, w in enumerate(layout.widths) if j > 0]).contiguous()
+    [[G_j]] [[F_j]]^-1 (1 + 2^w_j N), their inverses from one batched inversion and the products from one launch
+    (sc_initiator_cx_differences)."""
+    return paillier.engine.initiator_cx_differences(paillier.key, layout.kappa, layout.widths, f_enc.contiguous(), g_enc.contiguous(),
+                                                    d_key.contiguous())
 
 
 def cx_finish(layout: SelectLayout, delta_enc: torch.Tensor, d_enc: torch.Tensor, f_enc: torch.Tensor, g_enc: torch.Tensor,
               products: torch.Tensor, plain, draws: SelectDraws, paillier: Paillier, out: torch.Tensor | None = None,
               lo_index: torch.Tensor | None = None, hi_index: torch.Tensor | None = None) -> torch.Tensor:
-    """Alice's end of a compare-exchange: T_j as in select_finish, U_j = T_j [[ab_j]] (one product), one inversion of U, then
-    sc_select_finish_cx.  Without index rows the result is [2][nf][count][2nw] = (lo, hi); with them, lo / hi of column j, item i
-    go to row lo_index[j][i] / hi_index[j][i] of `out` seen as rows of 2nw words."""
-    e, mod = paillier.engine, paillier.mod_n2
-    nf, count, nw2 = f_enc.shape
-    T = select_t(layout, delta_enc, d_enc, plain, draws, paillier)
-    ab = products.reshape(nf * count, nw2)
-    u_inv = e.modinv(mod, e.modmul(mod, T, ab))
-    return e.select_finish_cx(mod, T, ab, u_inv, f_enc, g_enc, lo_index, hi_index, out)
+    """Alice's end of a compare-exchange (sc_initiator_cx_finish): T_j as in select_finish, U_j = T_j [[ab_j]] (one product), one
+    inversion of U, then sc_select_finish_cx's launch.  Without index rows the result is [2][nf][count][2nw] = (lo, hi); with them, lo /
+    hi of column j, item i go to row lo_index[j][i] / hi_index[j][i] of `out` seen as rows of 2nw words."""
+    et, rab = plain
+    return paillier.engine.initiator_cx_finish(paillier.key, layout.kappa, layout.widths, delta_enc, d_enc.contiguous(), f_enc.contiguous(),
+                                               g_enc.contiguous(), products.contiguous(), draws.r_a, et, rab, lo_index, hi_index, out)
 
 
 def _cx_batch(layout, l, f, g, ap, ad, bp, bd, draws=None, select_draws=None, out=None, lo_index=None, hi_index=None):
