@@ -51,6 +51,13 @@ int sc_ctx_set_pair_policy(sc_ctx* ctx, double hold_ms, double max_rounds);
 /* Counters of the context since its creation: out[0] = pair launches that ran in segments, out[1] = segments queued for them,
  * out[2] = op-time calibrations this context performed (the others are zero).  For tests and tools. */
 int sc_ctx_stats(sc_ctx* ctx, uint64_t* out, int n);
+/* Launches per compiled interpreter instance since the context was created (counted on the host, next to each launch; the
+ * calibration launches of the automatic policies count like any other).  Up to `cap` (key, count) entries in ascending key order go
+ * to keys_out / counts_out (either may be NULL with cap 0); *n_out = the number of instances launched so far, which may exceed
+ * `cap`.  The key names the template instance:
+ *   bits 0..7 L, bits 8..15 G, bits 16..23 W (limb bits), bit 24 NEG1, bit 25 STAMP, bit 26 DIG, bit 27 kind (0 k_vm, 1 k_pvm);
+ * STAMP and DIG are always 0 for k_vm.  For tests and tools: which instance a call landed on is host policy no result shows. */
+int sc_ctx_launch_counts(sc_ctx* ctx, uint32_t* keys_out, uint64_t* counts_out, int cap, int* n_out);
 /* The constants behind the automatic policies, measured once per device and process when the first secret key is created (about
  * 80 ms: full, half and one-and-a-half rounds of x^e mod p, 1024 bits, on the two-lane and on the one-lane kernel) instead of fitted
  * on one box: out[0..5] =

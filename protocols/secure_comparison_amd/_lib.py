@@ -20,7 +20,7 @@ SYMBOLS = [
     "sc_initiator_select_d", "sc_paillier_one_minus", "sc_initiator_cx_differences", "sc_initiator_select_pack", "sc_keyholder_select_mult",
     "sc_initiator_select_finish", "sc_initiator_cx_finish",
     "sc_rng_seed", "sc_rng_bits", "sc_rng_below", "sc_rng_coins", "sc_rng_permutations",
-    "sc_peak_probe", "sc_mac_counter", "sc_table_traffic_probe", "sc_ctx_set_latency_mode", "sc_ctx_set_onelane_mode", "sc_ctx_set_chip_share", "sc_ctx_set_fork_mode", "sc_ctx_set_pair_policy", "sc_ctx_stats", "sc_ctx_policy", "sc_clock_probe", "sc_comm_unique_id", "sc_comm_init", "sc_allgather", "sc_comm_destroy",
+    "sc_peak_probe", "sc_mac_counter", "sc_table_traffic_probe", "sc_ctx_set_latency_mode", "sc_ctx_set_onelane_mode", "sc_ctx_set_chip_share", "sc_ctx_set_fork_mode", "sc_ctx_set_pair_policy", "sc_ctx_stats", "sc_ctx_launch_counts", "sc_ctx_policy", "sc_clock_probe", "sc_comm_unique_id", "sc_comm_init", "sc_allgather", "sc_comm_destroy",
 ]
 
 
@@ -127,6 +127,7 @@ def load() -> C.CDLL:
         "sc_ctx_set_fork_mode": (i32, [vp, i32]),
         "sc_ctx_set_pair_policy": (i32, [vp, C.c_double, C.c_double]),
         "sc_ctx_stats": (i32, [vp, C.POINTER(C.c_uint64), i32]),
+        "sc_ctx_launch_counts": (i32, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), i32, ip]),
         "sc_ctx_policy": (i32, [vp, C.POINTER(C.c_double)]),
         "sc_clock_probe": (i32, [vp, i32, vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "sc_comm_unique_id": (i32, [vp, vp]),

@@ -202,6 +202,7 @@ struct sc_ctx {
   // hold its slot for much longer than pair_hold_ms; launches of more than pair_max_rounds rounds are left whole
   double pair_hold_ms = 5.0, pair_max_rounds = 2.5;
   uint64_t stat_segmented_launches = 0, stat_segments = 0, stat_pair_calibrations = 0;   // sc_ctx_stats
+  std::map<uint32_t, uint64_t> launch_counts;                // sc_ctx_launch_counts: launches per interpreter instance (launch_key)
   int chip_share = 1;                                       // sc_ctx_set_chip_share: contexts working on this GPU at the same time
   void* comm = nullptr;                                     // RCCL communicator of this rank (sc_comm_init), one context per GPU
   int comm_rank = 0, comm_nranks = 0;
@@ -241,6 +242,11 @@ namespace sc_host {
 // sc_lib.hip
 int fail(sc_ctx* ctx, int code, const char* fmt, ...);
 int ensure_scratch(sc_ctx* ctx, size_t bytes, uint32_t** out);
+// the key of an interpreter instance in sc_ctx::launch_counts (the packing include/sc_amd_dev.h documents)
+constexpr uint32_t launch_key(bool pvm, int G, int L, int W, bool neg1, bool stamp, bool dig) {
+  return (uint32_t)L | ((uint32_t)G << 8) | ((uint32_t)W << 16) | (neg1 ? 1u << 24 : 0u) | (stamp ? 1u << 25 : 0u) | (dig ? 1u << 26 : 0u) |
+         (pvm ? 1u << 27 : 0u);
+}
 // sc_launch_vm.hip / sc_launch_pvm.hip, parts 0 .. 2: launch the instance (G, L, W, NEG1[, STAMP]) of the interpreter on the context's
 // stream (grid, scratch arena and occupancy handled there); SC_ERR_UNSUPPORTED when the instance lives in another part
 int launch_vm_part0(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);

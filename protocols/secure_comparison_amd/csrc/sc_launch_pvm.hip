@@ -36,6 +36,7 @@ int launch_pvm_cfg(sc_ctx* ctx, const VmArgs& a) {
   if (rc) return rc;
   if constexpr (STAMP) { args.stamps = ctx->stamps; ctx->stamp_grid = grid; }
   hipLaunchKernelGGL((k_pvm<G, L, WB, NEG1, STAMP, DIG>), dim3(grid), dim3(64), 0, ctx->stream, args);
+  ctx->launch_counts[sc_host::launch_key(true, G, L, WB, NEG1, STAMP, DIG)]++;
   HIPCHK(ctx, hipGetLastError());
   return SC_OK;
 }

@@ -33,6 +33,7 @@ int launch_vm_cfg(sc_ctx* ctx, const VmArgs& a) {
   int rc = sc_host::ensure_scratch(ctx, scratch_bytes, &args.scratch);
   if (rc) return rc;
   hipLaunchKernelGGL((k_vm<G, L, WB, NEG1>), dim3(grid), dim3(64), 0, ctx->stream, args);
+  ctx->launch_counts[sc_host::launch_key(false, G, L, WB, NEG1, false, false)]++;
   HIPCHK(ctx, hipGetLastError());
   return SC_OK;
 }

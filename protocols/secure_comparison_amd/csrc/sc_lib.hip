@@ -1382,7 +1382,7 @@ static int latency_pair_twin(sc_ctx* ctx, int mod, uint64_t count) {
 // The twin of a (4,18) / (4,14) / (8,14) modulus n whose own modulus is the multiple M = c n, c = -n^-1 mod 2^29, so that M = -1
 // (mod 2^29): in its context the Montgomery quotient digit needs no multiplication (Grp::NEG1).  M has at most 29 more bits than n;
 // the (4,18) configuration holds 2088 bits, so 2048-bit moduli fit (R / M >= 2^11), and the L = 14 pair twins of 1536 / 3072-bit
-// moduli (1624 / 3248 bits) have the room as well.  Residues modulo M (and pairs modulo M^2) reduce to
+// moduli (1624 / 3248 bits) have the room as well; a multiple that would not fit whole words gets no twin.  Residues modulo M (and pairs modulo M^2) reduce to
 // residues modulo n (n^2): the caller finishes in a context of the original modulus.  -1: no such twin (other configurations,
 // moduli too long, or n already = -1).
 static int neg1_twin(sc_ctx* ctx, int mod) {
@@ -1397,7 +1397,11 @@ static int neg1_twin(sc_ctx* ctx, int mod) {
       Big c(1, m.n0inv);
       Big M = big_trimmed_words(big_mul(m.n, c));
       const Config same = {m.G, m.L, m.W, false};
-      if (create_mod(ctx, M.data(), (int)M.size(), false, &twin, &same) != SC_OK) twin = -1;
+      // M must hold whole words below R like every other modulus (sc_mod_create's first pass; onelane_for and latency_pair_twin
+      // ask the same of their twins): a wide operand is read in raw chunks of M's words, and bits of a chunk at or above
+      // 2^(W S) are dropped by the limb conversion -- a 1587-bit modulus on (4,14) gave an M of 51 words for 1624 limb bits
+      if (32 * (int)M.size() > m.W * m.S) twin = -1;
+      else if (create_mod(ctx, M.data(), (int)M.size(), false, &twin, &same) != SC_OK) twin = -1;
       if (twin >= 0 && ctx->mods[twin].n0inv != 1) twin = -1;     // (cannot happen: M = -1 mod 2^29 by construction)
       if (twin >= 0) {           // what a single-modulus program needs to leave the context with a residue modulo n (sc_vm.h)
         uint32_t inv = m.n0inv;                                    // c is odd: c c = 1 (mod 8); Newton doubles the good bits
@@ -1604,6 +1608,17 @@ int sc_ctx_stats(sc_ctx* ctx, uint64_t* out, int n) {
   if (!ctx || !out || n < 0) return SC_ERR_ARG;
   const uint64_t v[3] = {ctx->stat_segmented_launches, ctx->stat_segments, ctx->stat_pair_calibrations};
   for (int i = 0; i < n; i++) out[i] = i < 3 ? v[i] : 0;
+  return SC_OK;
+}
+
+int sc_ctx_launch_counts(sc_ctx* ctx, uint32_t* keys_out, uint64_t* counts_out, int cap, int* n_out) {
+  if (!ctx || !n_out || cap < 0 || (cap > 0 && (!keys_out || !counts_out))) return SC_ERR_ARG;
+  int i = 0;
+  for (const auto& kv : ctx->launch_counts) {
+    if (i < cap) { keys_out[i] = kv.first; counts_out[i] = kv.second; }
+    i++;
+  }
+  *n_out = i;
   return SC_OK;
 }
 

@@ -1107,6 +1107,19 @@ class Engine:
         self._check(self.lib.sc_ctx_stats(self.ctx, v, 3))
         return {"segmented_pair_launches": int(v[0]), "pair_segments": int(v[1]), "pair_calibrations": int(v[2])}
 
+    def launch_counts(self) -> dict:
+        """{(kind, G, L, W, neg1, stamp, dig): launches} per compiled interpreter instance since the context was created
+        (sc_ctx_launch_counts); kind is "vm" or "pvm"."""
+        n = C.c_int()
+        self._check(self.lib.sc_ctx_launch_counts(self.ctx, None, None, 0, C.byref(n)))
+        cap = max(1, n.value)
+        keys, counts = (C.c_uint32 * cap)(), (C.c_uint64 * cap)()
+        self._check(self.lib.sc_ctx_launch_counts(self.ctx, keys, counts, cap, C.byref(n)))
+        out = {}
+        for k, v in zip(keys[:n.value], counts[:n.value]):
+            out[("pvm" if k >> 27 & 1 else "vm", k >> 8 & 0xff, k & 0xff, k >> 16 & 0xff, bool(k >> 24 & 1), bool(k >> 25 & 1), bool(k >> 26 & 1))] = int(v)
+        return out
+
     def set_chip_share(self, contexts: int) -> None:
         """This engine shares its GPU with contexts - 1 other engines working at the same time (sc_ctx_set_chip_share)."""
         self._check(self.lib.sc_ctx_set_chip_share(self.ctx, int(contexts)))

@@ -178,6 +178,18 @@ def test_bench_rank_handling_on_one_gpu():
         assert cp.returncode != 0 and "n_gpus" not in cp.stdout
 
 
+def _prime_and_non_residue(bits, _cache={}):
+    """A seeded prime of `bits` bits and a quadratic non-residue modulo it."""
+    if bits not in _cache:
+        from protocols.secure_comparison_amd.keygen import next_prime
+
+        p = next_prime(random.Random(f"prime:{bits}").getrandbits(bits - 2) | (1 << (bits - 1)))
+        assert p.bit_length() == bits
+        z = next(z for z in range(2, 200) if pow(z, (p - 1) // 2, p) == p - 1)
+        _cache[bits] = (p, z)
+    return _cache[bits]
+
+
 @pytest.mark.parametrize("bits", [523, 600, 1000, 1024, 1028])
 def test_onelane_configuration_primitives(onelane_engine, bits):
     """The one-lane (1, 37, 28-bit) kernels forced on: shared-exponent powers (short / long exponents, wide operands reduced
@@ -199,9 +211,20 @@ def test_onelane_configuration_primitives(onelane_engine, bits):
         wide = [rng.getrandbits(2 * bits + 40) for _ in xs]                       # wider than the modulus: reduced first
         tw = eng.upload(wide, 2 * mod.nwords + 2)
         assert eng.download(eng.modexp_shared(mod, tw, e)) == [pow(x % m, e, m) for x in wide]
-        ones = [pow(x, (m - 1) // 2 if i % 2 else e, m) for i, x in enumerate(xs)]
         flags = eng.modexp_shared_isone(mod, t, e).tolist()
-        assert flags == [int(pow(x, e, m) == 1) for x in xs] and (ones or True)
+        assert flags == [int(pow(x, e, m) == 1) for x in xs]
+        if bits == 1024:
+            # operands whose power IS 1: modulo a prime p, x^((p-1)/2) = 1 exactly for the quadratic residues -- squares at the even
+            # rows, a non-residue times a square at the odd ones
+            p, z = _prime_and_non_residue(bits)
+            half = (p - 1) // 2
+            sq = [pow(rng.randrange(1, p), 2, p) for _ in range(count)]
+            planted = [s if i % 2 == 0 else s * z % p for i, s in enumerate(sq)]
+            planted[0] = 1
+            want = [int(i % 2 == 0) for i in range(count)]
+            assert want == [int(pow(x, half, p) == 1) for x in planted]
+            mod_p = eng.modulus(p)
+            assert eng.modexp_shared_isone(mod_p, eng.upload(planted, mod_p.nwords), half).tolist() == want
         # pair arithmetic: x^e mod m^2 from operands of 1, 2 and (wide) 3+ chunks, with and without the fused product
         for width, src in ((mod.nwords, xs), (2 * mod.nwords, [rng.randrange(m * m) for _ in xs])):
             tx = eng.upload(src, width)
