@@ -130,7 +130,9 @@ int sc_dgk_any_zero(sc_ctx* ctx, int key, const uint32_t* c_dptr, int planes, ui
  * alpha_tilde = (r - N) mod 2^l (flag rows, see FLAG ROWS below), rsmall = [r < (N-1)/2] (uint64), rshift = r div 2^l ([count][nwords]).
  * FLAG ROWS (every protocol step and plaintext helper): 1 <= l <= 255.  alpha, alpha_tilde and beta hold lw = ceil(l / 64)
  * little-endian uint64 words per comparison, laid out [count][lw], the bits above l zero; for l <= 64 that is one uint64 per
- * comparison.  rsmall, delta_a, dbit and delta_b are one uint64 per comparison at every l. */
+ * comparison.  rsmall, delta_a, dbit and delta_b are one uint64 per comparison at every l.  The plaintext helpers (sc_plain_alice /
+ * sc_plain_bob and every step that runs them) additionally refuse l >= 32 nwords(N) with SC_ERR_ARG: 2^l + r must fit the
+ * nwords(N) + 1 words of its output, and the protocol needs l + 2 < bits(N) anyway. */
 int sc_initiator_step1(sc_ctx* ctx, int paillier_key, int l, const uint32_t* x_enc_dptr, const uint32_t* y_enc_dptr,
                        const uint32_t* r_dptr, const uint32_t* rho_z_dptr /* nullable */, int flags, uint32_t* z_out_dptr, uint64_t* alpha_dptr,
                        uint64_t* alpha_tilde_dptr, uint64_t* rsmall_dptr, uint32_t* rshift_dptr, uint64_t count);

@@ -150,7 +150,9 @@ int sc_modexp_var_scatter(sc_ctx* ctx, int mod, const uint32_t* x_dptr, const ui
  * ct * -1 / int - ct / ct - ct (SC/initiator.py:254, 320, 371, 466, 478, 531, 559).
  * Synchronous.  On SC_ERR_NOT_INVERTIBLE *bad_index (nullable) is the index of a non-invertible element (found by testing
  * the members of the failing chunk individually) and sc_last_error() names it; `out` is unspecified then.
- * `out` must not overlap `x` (SC_ERR_ARG): the operands are re-read on the error path. */
+ * `out` must not overlap `x` (SC_ERR_ARG): the operands are re-read on the error path.
+ * Operands are canonical residues.  The inversion kernel reduces an operand below 4 n and refuses a larger one: SC_ERR_ARG
+ * ("operand i is not reduced modulo n", *bad_index = i), never SC_ERR_NOT_INVERTIBLE. */
 int sc_modinv(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint32_t* out_dptr, uint64_t count,
               int64_t* bad_index);
 
@@ -180,7 +182,8 @@ int sc_crt_combine(sc_ctx* ctx, int mod_p, int mod_full, int cst_k, int cst_negk
 /* From r[count][nw] and the Paillier N: m1 = 2^l + r ([count][nw+1], SC/initiator.py:256), alpha = r mod 2^l
  * (:270), alpha_tilde = (r - N) mod 2^l (:373), rsmall = [r < (N-1)/2] (:289, :559), rshift = r >> l (:562).
  * 1 <= l <= 255.  alpha / alpha_tilde are flag rows of lw = ceil(l / 64) little-endian uint64 words per item ([count][lw], the
- * bits above l zero: one uint64 per item for l <= 64); rsmall is one uint64 per item. */
+ * bits above l zero: one uint64 per item for l <= 64); rsmall is one uint64 per item.  l >= 32 nw is SC_ERR_ARG (m1 holds nw + 1
+ * words); the same holds for sc_plain_bob. */
 int sc_plain_alice(sc_ctx* ctx, const uint32_t* r_dptr, const uint32_t* n_hptr, int nw, int l, uint64_t count,
                    uint32_t* m1_dptr, uint64_t* alpha_dptr, uint64_t* alpha_tilde_dptr, uint64_t* rsmall_dptr,
                    uint32_t* rshift_dptr);

@@ -74,7 +74,8 @@ def rounds_for(nwords: int) -> int:
 
 def modinv(x: int, n: int, nwords: int, wpl: int, stats: dict | None = None) -> int | None:
     """The kernel's computation for one residue; None when x is not invertible.  stats (optional) receives the largest lane
-    magnitude seen for (f, g) and (d, e) per round -- in units of B -- and the largest |u| + |v|, |q| + |r|."""
+    magnitude seen for (f, g) and (d, e) per round -- in units of B -- the largest |u| + |v|, |q| + |r|, the sign of the final f and
+    the round at which the loop stopped."""
     assert nwords + 2 <= LANES * wpl and n & 1 and 0 <= x < n
     B = 1 << (32 * wpl)
     N = to_lanes(n, wpl)
@@ -82,8 +83,10 @@ def modinv(x: int, n: int, nwords: int, wpl: int, stats: dict | None = None) -> 
     ninv = pow(n, -1, 1 << 30)
     eta = -1
     worst_fg = worst_de = worst_row = 0.0
+    rounds_run, early_exit, rounds_needed = rounds_for(nwords), False, (0 if x == 0 else None)
     for t in range(rounds_for(nwords)):
         if not any(g):
+            rounds_run, early_exit = t, True
             break
         eta, u, v, q, r = divsteps30(eta, f[0] & M32, g[0] & M32)
         cd, ce = (u * d[0] + v * e[0]) & 0x3FFFFFFF, (q * d[0] + r * e[0]) & 0x3FFFFFFF
@@ -94,9 +97,17 @@ def modinv(x: int, n: int, nwords: int, wpl: int, stats: dict | None = None) -> 
         assert mde < (t + 2) * (2 * B + 1), ("d/e lane bound", t)
         worst_fg, worst_de = max(worst_fg, mfg / B), max(worst_de, mde / B)
         worst_row = max(worst_row, abs(u) + abs(v), abs(q) + abs(r))
-    if stats is not None:
-        stats.update(worst_fg_in_B=worst_fg, worst_de_in_B=worst_de, worst_row_sum=worst_row)
+        if stats is not None and rounds_needed is None and value(g, wpl) == 0:
+            rounds_needed = t + 1
     fv, gv, dv = value(f, wpl), value(g, wpl), value(d, wpl)
+    if stats is not None:
+        # final_f: the sign the kernel's last branch sees (+1: x^-1 = d, -1: x^-1 = -d, 0: f is not a unit); rounds_run: the round
+        # at which the all-lanes-zero test on g stopped the loop (early_exit) or the proven bound it ran to; rounds_needed: the
+        # rounds after which the VALUE of g was zero (a redundant zero keeps the loop running: rounds_run says nothing about how
+        # many rounds the operand needs), None when g never became zero
+        stats.update(worst_fg_in_B=worst_fg, worst_de_in_B=worst_de, worst_row_sum=worst_row,
+                     final_f=fv if fv in (1, -1) else 0, rounds_run=rounds_run, early_exit=early_exit, rounds_needed=rounds_needed,
+                     rounds_bound=rounds_for(nwords))
     if gv != 0 or fv not in (1, -1):
         return None
     return (dv if fv == 1 else -dv) % n

@@ -1058,7 +1058,8 @@ int sc_plain_alice(sc_ctx* ctx, const uint32_t* r, const uint32_t* n_hptr, int n
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
   if (!ctx || !r || !n_hptr || nw <= 0 || l <= 0 || l > SC_MAX_L || !m1 || !alpha || !alpha_tilde || !rsmall || !rshift)
     return fail(ctx, SC_ERR_ARG, "sc_plain_alice: bad argument");
-  if (count == 0) return SC_OK;
+  // m1 = 2^l + r must fit nw + 1 words (the kernel adds 2^l into word l / 32 <= nw), and the protocol needs l + 2 < bits(N) anyway
+  if (l >= 32 * nw) return fail(ctx, SC_ERR_ARG, "sc_plain_alice: l = %d does not fit below a modulus of %d words (l < 32 nw)", l, nw);
   uint32_t* d_n = nullptr;
   { int rc = device_n_half(ctx, n_hptr, nw, &d_n); if (rc) return rc; }
   if (launch_plain_alice(ctx->stream, r, d_n, d_n + nw, nw, l, count, m1, alpha, alpha_tilde, rsmall, rshift)) return fail(ctx, SC_ERR_HIP, "sc_plain_alice: launch failed");
@@ -1077,7 +1078,7 @@ static int plain_bob_impl(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr
   if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
   if (!ctx || !z || !n_hptr || nw <= 0 || l <= 0 || l > SC_MAX_L || !beta || !dbit || !zeta1 || !zeta2)
     return fail(ctx, SC_ERR_ARG, "sc_plain_bob: bad argument");
-  if (count == 0) return SC_OK;
+  if (l >= 32 * nw) return fail(ctx, SC_ERR_ARG, "sc_plain_bob: l = %d does not fit below a modulus of %d words (l < 32 nw)", l, nw);
   uint32_t* d_n = nullptr;
   { int rc = device_n_half(ctx, n_hptr, nw, &d_n); if (rc) return rc; }
   if (launch_plain_bob(ctx->stream, z, d_n, d_n + nw, nw, l, count, beta, dbit, zeta1, zeta2, bits)) return fail(ctx, SC_ERR_HIP, "sc_plain_bob: launch failed");
@@ -1173,7 +1174,14 @@ static int modinv_find_member(sc_ctx* ctx, const Mod& m, const InvLevel& lv, int
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   const volatile int* st = d_status;                    // written by the kernel, in host memory
   for (uint64_t i = 0; i < members; i++)
-    if (st[i] != 1) { *out_index = (int64_t)(i * lv.C + (uint64_t)chunk); return SC_OK; }
+    if (st[i] != 1) {
+      *out_index = (int64_t)(i * lv.C + (uint64_t)chunk);
+      if (st[i] == 3) {                                   // the caller's error, not a residue without an inverse
+        ctx->last_bad_index = *out_index;
+        return fail(ctx, SC_ERR_ARG, "sc_modinv: operand %lld is not reduced modulo n", (long long)*out_index);
+      }
+      return SC_OK;
+    }
   return fail(ctx, SC_ERR_HIP, "sc_modinv: chunk %lld is not invertible but all of its members are", (long long)chunk);
 }
 
@@ -1199,12 +1207,17 @@ int sc_modinv(sc_ctx* ctx, int mod, const uint32_t* x, uint32_t* out, uint64_t c
   for (uint64_t i = 0; i < pend.top_count && bad < 0; i++) if (st[i] != 1) bad = (int64_t)i;
   if (bad < 0) return SC_OK;
   if (st[bad] == 2) return fail(ctx, SC_ERR_HIP, "sc_modinv: the inversion kernel left its proven value range (internal error)");
+  if (st[bad] == 3 && pend.levels.empty()) {              // (with levels above it the top kernel sees chunk products, which are reduced)
+    if (bad_index) *bad_index = bad;
+    ctx->last_bad_index = bad;
+    return fail(ctx, SC_ERR_ARG, "sc_modinv: operand %lld is not reduced modulo n", (long long)bad);
+  }
   // error path: `bad` indexes the deepest level's chunk products; walk back up, one member test per level
   const Mod& m = ctx->mods[mod];
   for (int lv = (int)pend.levels.size() - 1; lv >= 0; lv--) {
     int64_t member = -1;
     rc = modinv_find_member(ctx, m, pend.levels[lv], bad, &member);
-    if (rc) return rc;
+    if (rc) { if (bad_index && member >= 0 && lv == 0) *bad_index = member; return rc; }
     bad = member;
   }
   if (bad_index) *bad_index = bad;

@@ -220,7 +220,15 @@ __global__ void __launch_bounds__(64) k_xgcd(const uint32_t* __restrict__ xin, u
     n[k] = (i < nw) ? nwords_dev[i] : 0u;
     x[k] = (i < nw) ? xin[item * nw + i] : 0u;
   }
-  while (M::cmp(x, n) >= 0) M::add(x, n, true, 1);   // inputs are canonical residues: this is a guard
+  // inputs are canonical residues: this is a guard.  At most three subtractions of n (one wave-wide subtraction per multiple: an
+  // unbounded loop would spin for ~2^32 iterations on an all-ones operand under a modulus whose top word is 1); an operand that
+  // is still not below n is the caller's error, status 3 and no result.
+#pragma unroll 1
+  for (int s = 0; s < 3 && M::cmp(x, n) >= 0; s++) M::add(x, n, true, 1);
+  if (M::cmp(x, n) >= 0) {                           // wave-uniform
+    if (lane == 0) status[item] = 3;
+    return;
+  }
   uint32_t f[NW], g[NW], d[NW], e[NW];
 #pragma unroll
   for (int k = 0; k < WPL; k++) { f[k] = n[k]; g[k] = x[k]; d[k] = 0; e[k] = (lane == 0 && k == 0) ? 1u : 0u; }
@@ -302,7 +310,8 @@ __global__ void __launch_bounds__(64) k_xgcd(const uint32_t* __restrict__ xin, u
       if (i < nw) out[item * nw + i] = dw[k];
     }
   }
-  if (lane == 0) status[item] = ok ? 1 : (bound_ok ? 0 : 2);      // 2: internal bound violated (never expected; reported as an error)
+  // 2: internal bound violated (never expected; reported as an error); 3 (above): the operand was not reduced modulo n
+  if (lane == 0) status[item] = ok ? 1 : (bound_ok ? 0 : 2);
   (void)zero;
 }
 

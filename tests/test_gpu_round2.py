@@ -63,7 +63,8 @@ def test_per_gpu_shares_of_the_eight_gpu_configs_full_size(engine, keys, pbits, 
 
 
 def test_not_invertible_index_is_exact(engine):
-    """sc_modinv names a non-invertible element itself (not the chunk it sits in), at every depth of the inversion tree."""
+    """sc_modinv names a non-invertible element itself (not the chunk it sits in), at every depth of the inversion tree.  The planted
+    elements are canonical residues like every operand (an unreduced one is an argument error: tests/test_gpu_kernel_edges.py)."""
     from protocols.secure_comparison_amd.engine import NotInvertibleError
 
     rng = random.Random(5)
@@ -82,14 +83,13 @@ def test_not_invertible_index_is_exact(engine):
     for count, bad_at in ((3, 1), (48, 47), (49, 0), (500, 333), (5000, 4999), (70000, 12345)):
         xs = units(min(count, 600))
         xs = (xs * (count // len(xs) + 1))[:count]
-        xs[bad_at] = 35 * xs[bad_at]
+        xs[bad_at] = 35 * xs[bad_at] % n
         with pytest.raises(NotInvertibleError) as ei:
             engine.modinv(mod, engine.upload(xs, mod.nwords))
         assert ei.value.index == bad_at and str(bad_at) in str(ei.value)
     # two bad elements: one of them is named
     xs = units(300)
-    xs[17] *= 3
-    xs[250] *= 7
+    xs[17], xs[250] = xs[17] * 3 % n, xs[250] * 7 % n
     with pytest.raises(NotInvertibleError) as ei:
         engine.modinv(mod, engine.upload(xs, mod.nwords))
     assert ei.value.index in (17, 250)

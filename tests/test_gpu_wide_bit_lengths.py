@@ -17,6 +17,7 @@ from oracle import sc_oracle as o
 
 sys.path.insert(0, os.path.dirname(__file__))
 from _comm import DictionaryCommunicator  # noqa: E402
+from _kernel_edges import edge_rows as _edge_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -56,16 +57,6 @@ def _draw_tensors(engine, drs, l, nw, ew, er):
                       rho_z=engine.upload([d.rho_z for d in drs], nw), r_bob_dgk=bm([[d.r_d] + d.r_beta for d in drs], er),
                       r_alice_dgk=bm(rc, er), rho_zeta_1=engine.upload([d.rho_zeta1 for d in drs], nw),
                       rho_zeta_2=engine.upload([d.rho_zeta2 for d in drs], nw), rho_delta_b=engine.upload([d.rho_delta_b for d in drs], nw))
-
-
-def _edge_rows(n, l, rng):
-    """r / z rows at the edges of the flag arithmetic: 0, N - 1, N - 2^l, all-ones low words, a borrow out of the low 64-bit word
-    of r - N, both halves of (N-1)/2, and random values."""
-    nlo = n & ((1 << 64) - 1)
-    rows = [0, 1, n - 1, n - (1 << l), (n - 1) // 2, (n - 1) // 2 - 1, (n + 1) // 2, (1 << l) - 1, (1 << 64) - 1, (1 << 128) - 1,
-            ((n >> 300) << 300) | ((1 << 256) - 1), rng.randrange(n >> 64) << 64 | (nlo - 1 if nlo else 0), (1 << l) + nlo // 2]
-    rows += [rng.randrange(n) for _ in range(19)]
-    return [v % n for v in rows]
 
 
 @pytest.mark.parametrize("l", [63, 64, 65, 96, 127, 128, 129, 255])

@@ -5,18 +5,8 @@ import random
 
 import pytest
 
+from _kernel_edges import adversarial_pairs as _adversarial_pairs
 from oracle import xgcd_model as xm
-
-
-def _adversarial_pairs(bits, rng):
-    n_all_ones = (1 << bits) - 1
-    while n_all_ones % 3 == 0 or n_all_ones % 5 == 0:
-        n_all_ones -= 2
-    alt = int("a" * (bits // 4), 16) | 1                      # 1010...1011
-    ns = [n_all_ones, (1 << (bits - 1)) | 1, alt | (1 << (bits - 1)), rng.getrandbits(bits) | (1 << (bits - 1)) | 1]
-    for n in ns:
-        for x in (1, 2, n - 1, n - 2, (n + 1) // 2, n >> 1, (1 << (bits - 2)) - 1, int("5" * (bits // 4 - 1), 16) % n, rng.randrange(1, n)):
-            yield n, x % n
 
 
 @pytest.mark.parametrize("bits, wpl", [(64, 1), (256, 1), (1024, 1), (1984, 1), (2048, 2), (4032, 2), (4096, 4)])
