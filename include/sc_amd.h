@@ -227,6 +227,17 @@ int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key, int kappa, int nfields
                            const uint32_t* r_a_dptr, int aw, const uint32_t* e_dptr, int ew, const uint32_t* rab_dptr,
                            const uint64_t* lo_index_dptr /* nullable */, const uint64_t* hi_index_dptr /* nullable */, uint32_t* out_dptr,
                            uint64_t out_rows, uint64_t count);
+/* The network of a secure top-m (8d): the comparators that bring the m smallest of k values to the positions 0 .. m-1 in ascending
+ * order -- with only_last, the m-th smallest to position m-1 alone -- for 1 <= m <= k <= 1024 (SC_ERR_ARG otherwise).  Host only: no
+ * context, no device work, a pure function of (k, m, only_last) that both players evaluate.  Comparator t puts the smaller value at
+ * ij_out[t][0] < ij_out[t][1]; keep_out[t][0 / 1] is 1 when that output is read again (by a later comparator or as a result) and 0 when
+ * it is dead: hand sc_initiator_cx_finish the index out_rows for a dead output and it is not written.  Comparators come layer by
+ * layer, the comparators of a layer are disjoint, and layer_end_out[t] is the number of comparators in the layers 0 .. t.  The three
+ * arrays hold `cap` entries; cap >= *n_comparators >= *n_layers is enough.  cap = 0 (the arrays may be null) only reports the sizes;
+ * a cap in between reports them and returns SC_ERR_ARG.  m = k without only_last is the full sort's network, every flag 1.  Still
+ * SC_ABI_VERSION 5: an addition. */
+int sc_topk_network(int k, int m, int only_last, int cap, int32_t* ij_out /* [cap][2] */, uint8_t* keep_out /* [cap][2] */,
+                    int32_t* layer_end_out /* [cap] */, int* n_comparators, int* n_layers);
 
 /* ---- device-side CSPRNG: the random draws of a batch, generated where they are consumed ---------------- */
 /* The reference draws from Python's `secrets` (SC/initiator.py:223 permutation, :250 r, :420 delta_A, :512 rho_i) and the

@@ -5,10 +5,10 @@ from .initiator import AlicePlain, Initiator
 from .keyholder import BobPlain, KeyHolder
 from .schemes import DGK, DGKCiphertext, Paillier, PaillierCiphertext
 from .selection import secure_argmax_batch, secure_argmin_batch, secure_maximum_batch, secure_minimum_batch
-from .sorting import secure_sort_batch
+from .sorting import secure_kth_batch, secure_median_batch, secure_sort_batch, secure_topk_batch
 from .utils import from_bits, to_bits
 
 __all__ = ["Communicator", "InMemoryCommunicator", "StreamCommunicator", "Initiator", "KeyHolder", "from_bits", "to_bits", "Paillier", "PaillierCiphertext", "DGK",
            "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch",
-           "secure_sort_batch"]
+           "secure_sort_batch", "secure_topk_batch", "secure_kth_batch", "secure_median_batch"]
 __version__ = "0.1.0"

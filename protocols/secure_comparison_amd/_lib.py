@@ -18,7 +18,7 @@ SYMBOLS = [
     "sc_dgk_key_create", "sc_dgk_key_info", "sc_dgk_randomize", "sc_dgk_encrypt_bits_randomized", "sc_dgk_is_zero", "sc_dgk_any_zero",
     "sc_initiator_step1", "sc_keyholder_step2_4b", "sc_initiator_step4", "sc_initiator_step4i", "sc_keyholder_step4j_5", "sc_initiator_step67",
     "sc_initiator_select_d", "sc_paillier_one_minus", "sc_initiator_cx_differences", "sc_initiator_select_pack", "sc_keyholder_select_mult",
-    "sc_initiator_select_finish", "sc_initiator_cx_finish",
+    "sc_initiator_select_finish", "sc_initiator_cx_finish", "sc_topk_network",
     "sc_rng_seed", "sc_rng_bits", "sc_rng_below", "sc_rng_coins", "sc_rng_permutations",
     "sc_peak_probe", "sc_mac_counter", "sc_table_traffic_probe", "sc_ctx_set_latency_mode", "sc_ctx_set_onelane_mode", "sc_ctx_set_chip_share", "sc_ctx_set_fork_mode", "sc_ctx_set_pair_policy", "sc_ctx_stats", "sc_ctx_launch_counts", "sc_ctx_policy", "sc_clock_probe", "sc_comm_unique_id", "sc_comm_init", "sc_allgather", "sc_comm_destroy",
 ]
@@ -113,6 +113,7 @@ def load() -> C.CDLL:
         "sc_keyholder_select_mult": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, u64]),
         "sc_initiator_select_finish": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, u64]),
         "sc_initiator_cx_finish": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, u64, u64]),
+        "sc_topk_network": (i32, [i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), ip, ip]),
         "sc_rng_seed": (i32, [vp, vp]),
         "sc_rng_bits": (i32, [vp, i32, vp, u64]),
         "sc_rng_below": (i32, [vp, vp, i32, i32, vp, u64]),

@@ -2201,3 +2201,4 @@ int sc_mac_counter(sc_ctx* ctx, int reset, double* out_macs) {
 }  // extern "C"
 
 #include "sc_schemes.h"
+#include "sc_topk.h"

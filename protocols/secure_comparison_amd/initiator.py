@@ -432,6 +432,18 @@ class Initiator:
         return await alice_sort(self, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks,
                                 max_rows)
 
+    async def perform_secure_topk_batch(self, v_enc: torch.Tensor, m: int, payload: torch.Tensor | None = None, payload_bits=(),
+                                        largest: bool = False, return_indices: bool = False, kappa: int = 40, source: str = "device",
+                                        engine=None, generator=None, chunks: int = 1, max_rows: int = 65536, only_last: bool = False):
+        """(values [B][m][2nw], payload [np][B][m][2nw] or None, indices [B][m][2nw] or None), as sorting.secure_topk_batch; with
+        only_last the value of rank m - 1 alone ([B][2nw], [np][B][2nw], [B][2nw]), as sorting.secure_kth_batch(kth = m - 1).  The
+        header `topk_0_session_{sid}`, then per sub-batch of sorting.topk_network(k, m, only_last) one comparison session and one
+        selection exchange (message ids `.._session_{sid}_topk_{i}`).  chunks > 1 is not supported (ValueError)."""
+        from .sorting import alice_topk
+
+        return await alice_topk(self, v_enc, m, payload, payload_bits, largest, return_indices, kappa, source, engine, generator, chunks,
+                                max_rows, only_last)
+
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""
         if self.communicator is None:

@@ -310,6 +310,15 @@ class KeyHolder:
 
         await bob_sort(self, k, payload_bits, return_indices, kappa, source, generator, max_rows)
 
+    async def perform_secure_topk_batch(self, k: int, m: int, payload_bits=(), return_indices: bool = False, kappa: int = 40,
+                                        only_last: bool = False, source: str = "device", generator=None, max_rows: int = 65536) -> None:
+        """Bob's side of Initiator.perform_secure_topk_batch for the m smallest (or largest) of k values per row: the initiator's
+        header must announce this k, m, only_last, max_rows, kappa and these column widths; the schedule follows from it
+        (sorting.topk_schedule), and a sub-batch of another size is refused."""
+        from .sorting import bob_topk
+
+        await bob_topk(self, k, m, payload_bits, return_indices, kappa, only_last, source, generator, max_rows)
+
     async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
         message when it has been received already.  Returns the session's batch size."""

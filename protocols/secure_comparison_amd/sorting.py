@@ -10,6 +10,10 @@ Bob's [[ab_j]] of that selection, [[S_j]] = [[delta (G_j - F_j)]] = [[ab_j]] T_j
 so both outputs share one inversion (sc_select_finish_cx).  lo lands at F's position and hi at G's.  Ascending: F = the value at
 i, G = the value at j of a comparator (i, j), i < j; descending: F = the value at j, G = the value at i.  Equal keys give delta = 1,
 lo = F and hi = G: a comparator never exchanges equal keys, in either direction.  The sort is deterministic but not stable.
+
+The m smallest (or largest) of k, one order statistic and the median run the same compare-exchange over a truncated network,
+topk_network(k, m, only_last): the comparators the wanted outputs depend on, with a flag per output that says whether anything
+reads it again; a dead output is handed the row past the buffer's end and is not written.
 """
 from __future__ import annotations
 
@@ -80,6 +84,121 @@ def _sort_steps(buf: torch.Tensor, B: int, k: int, max_rows: int, descending: bo
         for a, b in cuts:
             f_rows, g_rows = fr[a:b], gr[a:b]
             yield (buf.index_select(1, f_rows), buf.index_select(1, g_rows), (col + f_rows).contiguous(), (col + g_rows).contiguous())
+
+
+# ---- the truncated network: the m smallest of k, or the m-th smallest alone ----------------------------------------
+def _truncated_merges(k: int, m: int) -> list[tuple[int, int]] | None:
+    """Candidate (A) in sequential order, or None when one block would span the whole padded row: Batcher-sort every block of
+    m' = 2^ceil(log2 m) positions, then for stride = m', 2m', .. merge the blocks at a and b = a + stride into a -- the half-cleaner
+    (a + i, b + m' - 1 - i) leaves the m' smallest of both in block a as a bitonic sequence, the bitonic merger sorts it.  A padded
+    position (index >= k) holds +inf and every comparator puts the minimum at its lower index, so a comparator that touches one
+    changes nothing and is left out, and so is the whole merge of a block b that starts at or past k."""
+    mp = 1 << (m - 1).bit_length()
+    n = 1 << (k - 1).bit_length()
+    if mp >= n:
+        return None
+    block = [c for layer in batcher_network(mp) for c in layer] if mp > 1 else []
+    seq = [(a + i, a + j) for a in range(0, k, mp) for i, j in block]
+    stride = mp
+    while stride < k:
+        for a in range(0, k - stride, 2 * stride):                    # b >= k: block b is all +inf and block a stays as it is
+            b = a + stride
+            seq += [(a + i, b + mp - 1 - i) for i in range(mp)]
+            q = mp // 2
+            while q >= 1:
+                seq += [(a + i, a + i + q) for i in range(mp) if (i // q) % 2 == 0]
+                q //= 2
+        stride *= 2
+    return [(i, j) for i, j in seq if j < k]
+
+
+def _prune(seq: list[tuple[int, int]], live: set[int]) -> list[tuple[int, int, bool, bool]]:
+    """Backwards from the live outputs: a comparator with no live output goes, one with a live output makes both of its inputs live;
+    the flags say which of its outputs is read again."""
+    live = set(live)
+    out = []
+    for i, j in reversed(seq):
+        ki, kj = i in live, j in live
+        if ki or kj:
+            out.append((i, j, ki, kj))
+            live.add(i)
+            live.add(j)
+    out.reverse()
+    return out
+
+
+def _relayer(seq: list[tuple[int, int, bool, bool]], k: int) -> list[list[tuple[int, int, bool, bool]]]:
+    """Every comparator into the earliest layer after the previous comparators of both of its positions, in sequential order."""
+    depth = [0] * k
+    layers: list[list[tuple[int, int, bool, bool]]] = []
+    for c in seq:
+        t = max(depth[c[0]], depth[c[1]])
+        if t == len(layers):
+            layers.append([])
+        layers[t].append(c)
+        depth[c[0]] = depth[c[1]] = t + 1
+    return layers
+
+
+def topk_network(k: int, m: int, only_last: bool = False) -> list[list[tuple[int, int, bool, bool]]]:
+    """Layers of disjoint comparators (i, j, keep_i, keep_j), i < j, for 1 <= m <= k <= MAX_K: each puts the smaller value at i, and
+    after the last layer the positions 0 .. m-1 hold the m smallest values in ascending order (only_last: position m-1 alone is
+    guaranteed, the m-th smallest).  keep_i / keep_j say whether that output is read again, by a later comparator or as a result: a
+    dead output need not be written.  A pure function of (k, m, only_last): the smaller of (A) the truncated merges and (B)
+    batcher_network(k), each pruned backwards from the live outputs and packed into the earliest layers; (B) on a tie.  m = k without
+    only_last prunes nothing: the layers are batcher_network(k)'s own, every flag true."""
+    net = batcher_network(k)
+    if not 1 <= int(m) <= k:
+        raise ValueError(f"m = {m}: expected 1 <= m <= k = {k}")
+    m = int(m)
+    if m == k and not only_last:
+        return [[(i, j, True, True) for i, j in layer] for layer in net]
+    live = {m - 1} if only_last else set(range(m))
+    best = _prune([c for layer in net for c in layer], live)
+    merges = _truncated_merges(k, m)
+    if merges is not None:
+        cand = _prune(merges, live)
+        if len(cand) < len(best):
+            best = cand
+    return _relayer(best, k)
+
+
+def topk_schedule(k: int, m: int, only_last: bool, B: int, max_rows: int):
+    """sort_schedule for topk_network(k, m, only_last): per layer, (its comparators (i, j, keep_i, keep_j), its sub-batches [start,
+    stop) of at most max_rows of the layer's B * len(layer) comparisons t = c * B + b).  Live and dead outputs share a sub-batch."""
+    if int(max_rows) < 1:
+        raise ValueError(f"max_rows = {max_rows}: expected >= 1")
+    out = []
+    for layer in topk_network(k, m, only_last):
+        total = B * len(layer)
+        out.append((layer, [(a, min(a + max_rows, total)) for a in range(0, total, max_rows)]))
+    return out
+
+
+def topk_counts(k: int, m: int, only_last: bool, B: int, max_rows: int) -> list[int]:
+    """The comparisons of every sub-batch of topk_schedule, in order (what the key holder needs of it)."""
+    return [b - a for _, cuts in topk_schedule(k, m, only_last, B, max_rows) for a, b in cuts]
+
+
+def _topk_steps(buf: torch.Tensor, B: int, k: int, m: int, only_last: bool, max_rows: int, largest: bool):
+    """_sort_steps over topk_schedule: (F, G, lo rows, hi rows) per sub-batch, where a dead output's row is nf * B * k, the number of
+    rows of buf: sc_select_finish_cx writes no row at or past out_rows, so the dead position keeps a ciphertext nothing reads again.
+    largest: F is the value at j and G the one at i, so the larger value goes to i and keep_i belongs to hi."""
+    nf, rows, _ = buf.shape
+    dev = buf.device
+    dead = nf * rows
+    col = (torch.arange(nf, dtype=torch.int64, device=dev) * rows).unsqueeze(1)
+    base = torch.arange(B, dtype=torch.int64, device=dev) * k
+    for layer, cuts in topk_schedule(k, m, only_last, B, max_rows):
+        c = torch.tensor(layer, dtype=torch.int64, device=dev)
+        ri, rj = (c[:, 0:1] + base).reshape(-1), (c[:, 1:2] + base).reshape(-1)
+        ki, kj = (c[:, 2:3].bool().expand(-1, B).reshape(-1), c[:, 3:4].bool().expand(-1, B).reshape(-1))
+        (fr, fk), (gr, gk) = ((rj, kj), (ri, ki)) if largest else ((ri, ki), (rj, kj))
+        for a, b in cuts:
+            f_rows, g_rows = fr[a:b], gr[a:b]
+            lo = torch.where(fk[a:b], col + f_rows, dead).contiguous()
+            hi = torch.where(gk[a:b], col + g_rows, dead).contiguous()
+            yield buf.index_select(1, f_rows), buf.index_select(1, g_rows), lo, hi
 
 
 # ---- the compare-exchange ----------------------------------------------------------------------------------------------------------
@@ -186,6 +305,71 @@ def secure_sort_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, ali
     return _sort_result(buf, payload, return_indices, B, k)
 
 
+# ---- top-m and the k-th order statistic in one process -----------------------------------------------------------------------------
+def _topk_start(v_enc, m, l, ap, payload, payload_bits, return_indices, kappa, max_rows):
+    """_sort_start and 1 <= m <= k; returns (layout, B, k, m)."""
+    layout, B, k = _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_rows)
+    if isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= k:
+        raise ValueError(f"m = {m}: expected an integer, 1 <= m <= k = {k}")
+    return layout, B, k, int(m)
+
+
+def _topk_result(buf, payload, return_indices, B, k, m, only_last):
+    """The first m positions of every row, or -- only_last -- position m - 1 alone, as copies."""
+    key, pay, idx = _sort_result(buf, payload, return_indices, B, k)
+    cut = (lambda t: t[..., m - 1, :].contiguous()) if only_last else (lambda t: t[..., :m, :].contiguous())
+    return cut(key), None if pay is None else cut(pay), None if idx is None else cut(idx)
+
+
+def _topk_buffer(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, largest, return_indices, kappa, max_rows):
+    """The checks and the network over the columns [nf][B k][2nw] in place; returns that buffer: the results sit in the first m
+    positions of every row, every other position holds whatever its last live output -- or the input -- left there."""
+    layout, B, k, m = _topk_start(v_enc, m, l, ap, payload, payload_bits, return_indices, kappa, max_rows)
+    buf = _sort_buffer(v_enc, payload, return_indices, ap, B, k)
+    out = buf.reshape(-1, buf.shape[-1])
+    for f, g, lo, hi in _topk_steps(buf, B, k, m, only_last, int(max_rows), largest):
+        _cx_batch(layout, l, f, g, ap, ad, bp, bd, out=out, lo_index=lo, hi_index=hi)
+    return buf
+
+
+def _topk_run(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, largest, return_indices, kappa, max_rows):
+    buf = _topk_buffer(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, largest, return_indices, kappa, max_rows)
+    return _topk_result(buf, payload, return_indices, v_enc.shape[0], v_enc.shape[1], int(m), only_last)
+
+
+def secure_topk_batch(v_enc: torch.Tensor, m: int, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
+                      payload: torch.Tensor | None = None, payload_bits=(), largest: bool = False, return_indices: bool = False,
+                      kappa: int = 40, max_rows: int = 65536):
+    """The m smallest of k values per row in ascending order, v_enc [B][k][2nw] (0 <= v < 2^l), 1 <= m <= k: (values [B][m][2nw],
+    payload [np][B][m][2nw] or None, indices [B][m][2nw] or None); largest: the m largest, largest first.  Payload columns and the
+    original positions travel with their key as in secure_sort_batch.  The network is topk_network(k, m): only the comparators the
+    m outputs depend on, and an output nothing reads again is not written.  Equal keys are never exchanged, so which of several
+    equal keys lands among the m -- and with it whose payload and index -- is fixed by the network, not by position: every key
+    returned is right, the choice among equals is deterministic but not the lowest index.  Not stable."""
+    return _topk_run(v_enc, m, False, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, payload, payload_bits, largest, return_indices,
+                     kappa, max_rows)
+
+
+def secure_kth_batch(v_enc: torch.Tensor, kth: int, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier,
+                     bob_dgk: DGK, payload: torch.Tensor | None = None, payload_bits=(), largest: bool = False,
+                     return_indices: bool = False, kappa: int = 40, max_rows: int = 65536):
+    """The value of rank kth (0 = the smallest; largest: 0 = the largest) of every row, 0 <= kth < k: (value [B][2nw], payload
+    [np][B][2nw] or None, index [B][2nw] or None) from topk_network(k, kth + 1, only_last=True).  Ties as in secure_topk_batch."""
+    if isinstance(kth, bool) or int(kth) != kth:
+        raise ValueError(f"kth = {kth}: expected an integer")
+    return _topk_run(v_enc, int(kth) + 1, True, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, payload, payload_bits, largest,
+                     return_indices, kappa, max_rows)
+
+
+def secure_median_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
+                        payload: torch.Tensor | None = None, payload_bits=(), return_indices: bool = False, kappa: int = 40,
+                        max_rows: int = 65536):
+    """The lower median of every row: secure_kth_batch with kth = (k - 1) // 2."""
+    k = v_enc.shape[1] if isinstance(v_enc, torch.Tensor) and v_enc.dim() == 3 else 1     # a bad v_enc is refused by the checks below
+    return secure_kth_batch(v_enc, max(k - 1, 0) // 2, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, payload, payload_bits, False,
+                            return_indices, kappa, max_rows)
+
+
 # ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_sort_batch) -----------------------------------------
 # `sort_0_session_{sid}` (int32: k, B, max_rows, kappa, the column widths) opens the sort; the key holder refuses a header that
 # differs from his own arguments and derives the schedule from it.  Sub-batch i is the unchanged comparison session and one selection
@@ -238,4 +422,63 @@ async def bob_sort(kh, k, payload_bits, return_indices, kappa, source, generator
         got = await kh._batch_session(tag, None, None, source, generator)
         if got != count:
             raise ValueError(f"sort: sub-batch {i} carries {got} comparisons, the schedule has {count}")
+        await _bob_select(kh, tag, layout, count, None, source, generator)
+
+
+# ---- top-m between the two players (Initiator / KeyHolder.perform_secure_topk_batch) -----------------------------------------------
+# `topk_0_session_{sid}` (int32: k, m, only_last, B, max_rows, kappa, the column widths) opens the run; the key holder refuses a header
+# that differs from his own arguments and derives the schedule from it (topk_counts).  Sub-batch i is the unchanged comparison session
+# and one selection exchange under the tag `session_{sid}_topk_{i}`: the key holder's work does not depend on which outputs are live.
+async def alice_topk(ini, v_enc, m, payload, payload_bits, largest, return_indices, kappa, source, engine, generator, chunks, max_rows,
+                     only_last):
+    from . import wire
+
+    _no_chunks(chunks)
+    if not isinstance(v_enc, torch.Tensor) or v_enc.dim() != 3:
+        raise ValueError("v_enc: expected [B][k][2nw]")
+    if not 1 <= int(max_rows) < 1 << 31:
+        raise ValueError(f"max_rows = {max_rows}: expected 1 <= max_rows < 2^31")
+    only_last = bool(only_last)
+    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
+    pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
+    layout, B, k, m = _topk_start(v_enc, m, l, pai, payload, payload_bits, return_indices, kappa, max_rows)
+    head = torch.tensor([k, m, int(only_last), B, int(max_rows), layout.kappa, *layout.widths], dtype=torch.int32, device=v_enc.device)
+    await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"topk_0_session_{sid}")
+    buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
+    out = buf.reshape(-1, buf.shape[-1])
+    for i, (f, g, lo, hi) in enumerate(_topk_steps(buf, B, k, m, only_last, int(max_rows), largest)):
+        tag = f"session_{sid}_topk_{i}"
+        delta, d_key = await _alice_compare(ini, tag, f[0], g[0], None, source, generator)
+        d = cx_differences(pai, layout, f, g, d_key)
+        products, plain, sd = await _alice_exchange(ini, tag, layout, delta, d, None, source, generator)
+        cx_finish(layout, delta, d, f, g, products, plain, sd, pai, out, lo, hi)
+    return _topk_result(buf, payload, return_indices, B, k, m, only_last)
+
+
+async def bob_topk(kh, k, m, payload_bits, return_indices, kappa, only_last, source, generator, max_rows):
+    from . import wire
+
+    sid = await kh._open_batch_session()
+    comm, pai, l = kh.communicator, kh.scheme_paillier, kh.l_maximum_bit_length
+    only_last = bool(only_last)
+    topk_network(k, m, only_last)                                        # k and m in range
+    widths = tuple(int(b) for b in payload_bits) + ((index_bits(k),) if return_indices else ())
+    if 1 + len(widths) > MAX_FIELDS:
+        raise ValueError(f"{1 + len(widths)} columns (key, payload, index): at most {MAX_FIELDS}")
+    layout = SelectLayout(l, kappa, widths, pai.public_key.n.bit_length())
+    (head,) = wire.incoming(await comm.recv(kh.other_party, msg_id=f"topk_0_session_{sid}"), pai.engine.device, expect=1)
+    if not isinstance(head, torch.Tensor) or head.dim() != 1 or not 7 <= head.shape[0] <= 6 + MAX_FIELDS:
+        raise ValueError("topk: malformed header")
+    hk, hm, hol, B, mr, *rest = [int(v) for v in head.cpu().tolist()]
+    mine = [k, int(m), int(only_last), int(max_rows), layout.kappa, *layout.widths]
+    if [hk, hm, hol, mr, *rest] != mine:
+        raise ValueError(f"topk: the initiator announces k, m, only_last, max_rows, kappa and widths {[hk, hm, hol, mr, *rest]}, "
+                         f"this key holder expects {mine}")
+    if B < 0:
+        raise ValueError(f"topk: the initiator announces B = {B}")
+    for i, count in enumerate(topk_counts(k, int(m), only_last, B, mr)):
+        tag = f"session_{sid}_topk_{i}"
+        got = await kh._batch_session(tag, None, None, source, generator)
+        if got != count:
+            raise ValueError(f"topk: sub-batch {i} carries {got} comparisons, the schedule has {count}")
         await _bob_select(kh, tag, layout, count, None, source, generator)
