@@ -227,6 +227,37 @@ int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key, int kappa, int nfields
                            const uint32_t* r_a_dptr, int aw, const uint32_t* e_dptr, int ew, const uint32_t* rab_dptr,
                            const uint64_t* lo_index_dptr /* nullable */, const uint64_t* hi_index_dptr /* nullable */, uint32_t* out_dptr,
                            uint64_t out_rows, uint64_t count);
+/* ---- secure multiplication: [[x y_j]] from [[x]] and up to four columns [[y_j]], one round trip ------------------ */
+/* The one operation Paillier lacks, with both factors blinded: the initiator packs A = x + e_y and B_j = y_j + e_x_j into one message,
+ * the key holder returns fresh [[A B_j]], and [[x y_j]] = [[A B_j]] T_j^-1 with T_j = [[x]]^(e_x_j) [[y_j]]^(e_y) (1 + e_x_j e_y N).
+ * LAYOUT: (kappa, wx, nfields, wy_hptr): 1 <= kappa <= 62 statistical blinding bits, 1 <= nfields <= 4 columns, widths 1 .. 255 with
+ * 0 <= x < 2^wx, 0 <= y_j < 2^wy[j], or -2^(w-1) <= value < 2^(w-1) as residues modulo N when is_signed.  s = wx + kappa + 1,
+ * fbits_j = wy[j] + kappa + 1; every entry checks s + sum_j fbits_j < bits(N) - 1 and every s + fbits_j < bits(N) - 1 against the key
+ * before anything is launched (SC_ERR_ARG, sc_last_error names the column).  Arrays, scratch, stream and the keys served: as the
+ * selection entries above (no SC_ERR_UNSUPPORTED where the modulus has no pair kernel with per-row exponents).
+ * Initiator, the message P = [[x]] prod_j [[y_j]]^(2^off_j) (1 + R N) rho_p^N and the plaintext arrays the finish needs: e_out
+ * [nfields + 1][count][ew] (e_x_j = r_b_j + oy_j per column, the LAST plane e_y = r_a + ox; the offsets are 2^(w-1) when is_signed,
+ * else 0) and rab_out[j] = e_x_j e_y [nfields][count][nwords].  y_enc: [nfields][count][2 nwords]; r_a: [count][aw] below
+ * 2^(wx + kappa); r_b: [nfields][count][bw], column j below 2^(wy[j] + kappa); aw, bw <= 10; 32 ew >= max(s, max_j fbits_j); rho_p:
+ * [count][nwords] in [1, N).  rho_p is NOT nullable (SC_ERR_ARG), for sc_initiator_select_pack's reason. */
+int sc_initiator_mul_pack(sc_ctx* ctx, int paillier_key, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
+                          const uint32_t* x_enc_dptr, const uint32_t* y_enc_dptr, const uint32_t* r_a_dptr, int aw,
+                          const uint32_t* r_b_dptr, int bw, const uint32_t* rho_p_dptr, int ew, uint32_t* p_out_dptr,
+                          uint32_t* e_out_dptr, uint32_t* rab_out_dptr, uint64_t count);
+/* Key holder (secret key): CRT decryption of P, the field products A B_j (sc_mul_split), their encryptions randomized with
+ * rho_products [nfields][count][nwords]: out [nfields][count][2 nwords].  SC_ERR_LAYOUT and synchronous exactly as
+ * sc_keyholder_select_mult: a WIDER layout of the initiator is seen in P, a narrower one only on the wire. */
+int sc_keyholder_mul(sc_ctx* ctx, int paillier_key, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p_enc_dptr,
+                     const uint32_t* rho_products_dptr, uint32_t* out_dptr, uint64_t count);
+/* Initiator: out[j] = base[j] [[x y_j]]^coef, [nfields][count][2 nwords], coef in {+1, -1, -2}; base (nullable: no factor) has the
+ * shape of out.  products = the key holder's answer, e / rab = sc_initiator_mul_pack's.  coef = +1 inverts T_j, a negative coef
+ * inverts [[A B_j]] and multiplies T_j [[A B_j]]^-1 (squared for -2): one inversion pass either way (synchronous,
+ * SC_ERR_NOT_INVERTIBLE names the flat index j count + i through sc_last_bad_index), then one launch.  With base = [[a]] [[b]] on
+ * encrypted bits, coef = -1 is a OR b = a + b - a b and coef = -2 is a XOR b = a + b - 2 a b. */
+int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* x_enc_dptr,
+                            const uint32_t* y_enc_dptr, const uint32_t* products_dptr, const uint32_t* e_dptr, int ew,
+                            const uint32_t* rab_dptr, const uint32_t* base_dptr /* nullable */, int coef, uint32_t* out_dptr,
+                            uint64_t count);
 /* The network of a secure top-m (8d): the comparators that bring the m smallest of k values to the positions 0 .. m-1 in ascending
  * order -- with only_last, the m-th smallest to position m-1 alone -- for 1 <= m <= k <= 1024 (SC_ERR_ARG otherwise).  Host only: no
  * context, no device work, a pure function of (k, m, only_last) that both players evaluate.  Comparator t puts the smaller value at

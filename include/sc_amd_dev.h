@@ -208,6 +208,22 @@ int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int n
  * (selection.py announces it in the message that carries P). */
 int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr,
                     const uint32_t* p_dptr, uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
+/* ---- secure multiplication: the plaintext-word halves of the two players ------------------------- */
+/* Layout of the packed plaintext of P = [[x]] prod_j [[y_j]]^(2^off_j) (1 + R N) rho^N, low bits first: A = x + e_y in [0, s),
+ * s = wx + kappa + 1, then field j = B_j = y_j + e_x_j of wy[j] + kappa + 1 bits; nfields <= 4, 1 <= kappa <= 62, 1 <= wx, wy[j] <= 255.
+ * Both calls return SC_ERR_ARG when the fields, or one product A * B_j, would not fit below N (n_hptr, nw words).  Every field may
+ * span several words: the products are multi-word by multi-word.
+ * sc_mul_prep (initiator): from r_a [count][aw] (< 2^(wx + kappa)) and r_b [nfields][count][bw] (column j < 2^(wy[j] + kappa)),
+ * aw, bw <= 10: e [nfields + 1][count][ew] with e[j] = e_x_j = r_b_j + oy_j and e[nfields] = e_y = r_a + ox (ox = 2^(wx - 1),
+ * oy_j = 2^(wy[j] - 1) when is_signed, else 0), R = e_y + sum_j 2^off_j e_x_j [count][nw], rab_j = e_x_j e_y [nfields][count][nw].
+ * 32 ew >= max(s, max_j fbits_j). */
+int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
+                const uint32_t* r_a_dptr, int aw, const uint32_t* r_b_dptr, int bw, int ew, uint32_t* R_dptr, uint32_t* e_dptr,
+                uint32_t* rab_dptr, uint64_t count);
+/* sc_mul_split (key holder): from the decrypted P [count][nw]: prod_j = A * B_j [nfields][count][nw].  *bad_dptr as sc_select_split's:
+ * set to 1 (never cleared here) when a row has a bit at or above the end of the last field. */
+int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr,
+                 const uint32_t* p_dptr, uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
 /* sc_select_finish_cx (initiator, the compare-exchange of a secure sort): from a selection with sigma = delta,
  * base F and d = G - F + 2^w, both outputs hi = F ab^2 u_inv and lo = G t^2 u_inv modulo mod (N^2), where u_inv = (t ab)^-1.
  * t, ab, u_inv, f, g: [nfields][count][words(mod)], nfields 1 .. 4.  lo_index / hi_index (both or neither): uint64 [nfields][count],

@@ -3,6 +3,8 @@ Initiator.step_* and KeyHolder.step_* as hand-written HIP kernels behind a C ABI
 from .communicator import Communicator, InMemoryCommunicator, StreamCommunicator
 from .initiator import AlicePlain, Initiator
 from .keyholder import BobPlain, KeyHolder
+from .multiplication import (MulDraws, MulLayout, draw_mul, secure_and_batch, secure_equal_batch, secure_in_range_batch, secure_multiply_batch,
+                             secure_or_batch, secure_xor_batch)
 from .schemes import DGK, DGKCiphertext, Paillier, PaillierCiphertext
 from .selection import secure_argmax_batch, secure_argmin_batch, secure_maximum_batch, secure_minimum_batch
 from .sorting import secure_kth_batch, secure_median_batch, secure_sort_batch, secure_topk_batch
@@ -10,5 +12,6 @@ from .utils import from_bits, to_bits
 
 __all__ = ["Communicator", "InMemoryCommunicator", "StreamCommunicator", "Initiator", "KeyHolder", "from_bits", "to_bits", "Paillier", "PaillierCiphertext", "DGK",
            "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch",
-           "secure_sort_batch", "secure_topk_batch", "secure_kth_batch", "secure_median_batch"]
+           "secure_sort_batch", "secure_topk_batch", "secure_kth_batch", "secure_median_batch", "MulLayout", "MulDraws", "draw_mul",
+           "secure_multiply_batch", "secure_and_batch", "secure_or_batch", "secure_xor_batch", "secure_equal_batch", "secure_in_range_batch"]
 __version__ = "0.1.0"

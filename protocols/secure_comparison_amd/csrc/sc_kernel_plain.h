@@ -1,4 +1,5 @@
-// Plain-word helper kernels of the protocol steps (gfx950).  Included by sc_launch_misc.hip.
+// Plain-word helper kernels of the protocol steps (gfx950).  Included by sc_launch_misc.hip and, for the multiplication's two, by
+// sc_launch_mul.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -150,6 +151,7 @@ __device__ __forceinline__ void sel_mul64(uint64_t a, const uint32_t* b, int bw,
   }
 }
 
+#ifndef SC_MUL_UNIT   // sc_launch_mul.hip takes the helpers above and the multiplication's kernels below, not these two
 // The initiator's plaintext values of a selection from her draws r_a [count][aw] (< 2^kappa) and r_b [nf][count][bw]:
 //   R = r_a + sum_j 2^off[j] r_b_j ([count][nw]), e_j = r_b_j + 2^width[j] ([nf][count][ew]), rab_j = r_a r_b_j ([nf][count][nw]).
 __global__ void k_select_prep(const uint32_t* __restrict__ ra, int aw, const uint32_t* __restrict__ rb, int bw, SelLayout lay, int nw,
@@ -203,5 +205,86 @@ __global__ void k_select_split(const uint32_t* __restrict__ p, int nw, SelLayout
     }
   }
 }
+
+#endif  // !SC_MUL_UNIT
+
+// ---------------------------------------------------------------------------------------------
+// Secure multiplication (sc_mul_prep / sc_mul_split, include/sc_amd_dev.h).  Layout of the packed plaintext of P, low
+// bits first: A = x + e_y in bits [0, s), s = wx + kappa + 1, then field j = B_j = y_j + e_x_j in bits [off[j], off[j] + fbits[j]),
+// fbits[j] = wy[j] + kappa + 1, off[0] = s, off[j + 1] = off[j] + fbits[j]; everything below the modulus (the host checks).  Every
+// field may span several words (s and fbits reach 255 + 62 + 1 = 318 bits), so both kernels multiply multi-word by multi-word.
+// ---------------------------------------------------------------------------------------------
+// (MulLayout, MUL_FIELD_WORDS: sc_vm.h)  Compiled and launched by sc_launch_mul.hip alone (SC_MUL_UNIT).
+#ifdef SC_MUL_UNIT
+
+// out[0 .. nw) = a * b mod 2^(32 nw), a of aw words, b of bw words: schoolbook by columns, a 96-bit accumulator per column
+__device__ __forceinline__ void mul_words(const uint32_t* a, int aw, const uint32_t* b, int bw, uint32_t* out, int nw) {
+  uint64_t acc = 0;
+  uint32_t top = 0;
+  for (int k = 0; k < nw; k++) {
+    const int lo = k - bw + 1 > 0 ? k - bw + 1 : 0, hi = k < aw - 1 ? k : aw - 1;
+    for (int i = lo; i <= hi; i++) {
+      const uint64_t p = (uint64_t)a[i] * b[k - i];
+      acc += p;
+      top += acc < p ? 1u : 0u;
+    }
+    out[k] = (uint32_t)acc;
+    acc = (acc >> 32) | ((uint64_t)top << 32);
+    top = 0;
+  }
+}
+// v[0 .. MUL_FIELD_WORDS) = x (xw words, 0 past its end) + 2^(bit) when bit >= 0
+__device__ __forceinline__ void mul_add_offset(const uint32_t* x, int xw, int bit, uint32_t* v) {
+  uint32_t carry = 0;
+  for (int k = 0; k < MUL_FIELD_WORDS; k++) {
+    const uint64_t t = (uint64_t)(k < xw ? x[k] : 0u) + carry + ((bit >= 0 && k == (bit >> 5)) ? (1u << (bit & 31)) : 0u);
+    v[k] = (uint32_t)t;
+    carry = (uint32_t)(t >> 32);
+  }
+}
+
+// The initiator's plaintext values of a multiplication from her draws r_a [count][aw] (< 2^(wx + kappa)) and r_b [nf][count][bw]
+// (column j < 2^(wy[j] + kappa)), with ox = 2^(wx - 1), oy_j = 2^(wy[j] - 1) for signed operands and 0 otherwise:
+//   e_y = r_a + ox and e_x_j = r_b_j + oy_j as e [nf + 1][count][ew] (planes e_x_0 .. e_x_(nf-1), then e_y),
+//   R = e_y + sum_j 2^off[j] e_x_j ([count][nw]), rab_j = e_x_j e_y ([nf][count][nw]).
+__global__ void k_mul_prep(const uint32_t* __restrict__ ra, int aw, const uint32_t* __restrict__ rb, int bw, MulLayout lay, int nw, int ew,
+                           uint64_t count, uint32_t* __restrict__ R, uint32_t* __restrict__ e, uint32_t* __restrict__ rab) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint32_t ey[MUL_FIELD_WORDS], ex[SEL_MAX_FIELDS][MUL_FIELD_WORDS];
+  mul_add_offset(ra + i * aw, aw, lay.is_signed ? lay.wx - 1 : -1, ey);
+  uint32_t* eo = e + ((uint64_t)lay.nf * count + i) * ew;
+  for (int k = 0; k < ew; k++) eo[k] = k < MUL_FIELD_WORDS ? ey[k] : 0u;
+  for (int j = 0; j < lay.nf; j++) {
+    mul_add_offset(rb + ((uint64_t)j * count + i) * bw, bw, lay.is_signed ? lay.wy[j] - 1 : -1, ex[j]);
+    uint32_t* ej = e + ((uint64_t)j * count + i) * ew;
+    for (int k = 0; k < ew; k++) ej[k] = k < MUL_FIELD_WORDS ? ex[j][k] : 0u;
+    mul_words(ex[j], MUL_FIELD_WORDS, ey, MUL_FIELD_WORDS, rab + ((uint64_t)j * count + i) * nw, nw);
+  }
+  for (int k = 0; k < nw; k++) {
+    uint32_t v = k < MUL_FIELD_WORDS ? ey[k] : 0u;
+    for (int j = 0; j < lay.nf; j++) v |= sel_shl_word(ex[j], MUL_FIELD_WORDS, lay.off[j], k);
+    R[i * nw + k] = v;
+  }
+}
+
+// The key holder's half: from the decrypted P [count][nw], prod_j = A * B_j ([nf][count][nw]) with A and B_j the fields of P.
+// A P with a bit at or above lay.end sets *bad (the players disagree on kappa or on the widths); its products are still written.
+__global__ void k_mul_split(const uint32_t* __restrict__ p, int nw, MulLayout lay, uint64_t count, uint32_t* __restrict__ prod,
+                            uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t* x = p + i * nw;
+  uint32_t over = 0;
+  for (int k = lay.end >> 5; k < nw; k++) over |= (k == (lay.end >> 5)) ? (x[k] >> (lay.end & 31)) : x[k];
+  if (over) *bad = 1u;
+  uint32_t a[MUL_FIELD_WORDS], b[MUL_FIELD_WORDS];
+  for (int k = 0; k < MUL_FIELD_WORDS; k++) a[k] = sel_field_word(x, nw, 0, lay.s, k);
+  for (int j = 0; j < lay.nf; j++) {
+    for (int k = 0; k < MUL_FIELD_WORDS; k++) b[k] = sel_field_word(x, nw, lay.off[j], lay.fbits[j], k);
+    mul_words(a, MUL_FIELD_WORDS, b, MUL_FIELD_WORDS, prod + ((uint64_t)j * count + i) * nw, nw);
+  }
+}
+#endif  // SC_MUL_UNIT
 
 }  // namespace sc

@@ -1941,6 +1941,60 @@ int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int 
   return SC_OK;
 }
 
+// ---- secure multiplication: the plaintext-word halves of the two players (k_mul_prep / k_mul_split) ---------------
+// MulLayout.__post_init__ (multiplication.py) on the host -- the one copy of the fit rule every multiplication entry checks before it
+// launches anything: s + sum_j fbits_j < bits(N) - 1 and every s + fbits_j < bits(N) - 1; every refusal names its column
+static int mul_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int nfields, const int* wy, int is_signed, MulLayout* lay) {
+  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
+  if (wx < 1 || wx > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: wx = %d: expected 1 .. %d", who, wx, MUL_MAX_WIDTH);
+  if (!wy || nfields < 1 || nfields > SEL_MAX_FIELDS)
+    return fail(ctx, SC_ERR_ARG, "%s: %d columns: expected 1 .. %d with their widths", who, nfields, SEL_MAX_FIELDS);
+  lay->s = wx + kappa + 1; lay->nf = nfields; lay->wx = wx; lay->is_signed = is_signed ? 1 : 0;
+  int off = lay->s;
+  for (int j = 0; j < nfields; j++) {
+    if (wy[j] < 1 || wy[j] > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: column %d: width %d: expected 1 .. %d", who, j, wy[j], MUL_MAX_WIDTH);
+    lay->wy[j] = wy[j]; lay->fbits[j] = wy[j] + kappa + 1; lay->off[j] = off;
+    if (lay->s + lay->fbits[j] >= nbits_n - 1)
+      return fail(ctx, SC_ERR_ARG, "%s: column %d: the product A * B (%d bits) does not fit below a %d-bit N", who, j, lay->s + lay->fbits[j], nbits_n);
+    off += lay->fbits[j];
+    if (off >= nbits_n - 1)
+      return fail(ctx, SC_ERR_ARG, "%s: column %d: the packed fields (%d bits) do not fit below a %d-bit N (kappa = %d)", who, j, off, nbits_n, kappa);
+  }
+  lay->end = off;
+  return SC_OK;
+}
+static int mul_ebits(const MulLayout& lay) { int b = lay.s; for (int j = 0; j < lay.nf; j++) b = std::max(b, lay.fbits[j]); return b; }
+// the draws' and exponents' row widths: the kernels hold a field in MUL_FIELD_WORDS words
+static int mul_row_words(sc_ctx* ctx, const char* who, const MulLayout& lay, int aw, int bw, int ew, int nw) {
+  if (aw < 1 || aw > MUL_FIELD_WORDS || bw < 1 || bw > MUL_FIELD_WORDS || bw > nw || ew < 1)
+    return fail(ctx, SC_ERR_ARG, "%s: rows of %d (r_a), %d (r_b), %d (e) words: expected 1 .. %d for the draws", who, aw, bw, ew, MUL_FIELD_WORDS);
+  if (32 * ew < mul_ebits(lay)) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, mul_ebits(lay));
+  return SC_OK;
+}
+
+int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
+                const uint32_t* r_a, int aw, const uint32_t* r_b, int bw, int ew, uint32_t* R, uint32_t* e, uint32_t* rab, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  if (!ctx || !n_hptr || nw <= 0 || !r_a || !r_b || !R || !e || !rab) return fail(ctx, SC_ERR_ARG, "sc_mul_prep: bad argument");
+  MulLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = mul_layout(ctx, "sc_mul_prep", big_bits(n), kappa, wx, nfields, wy_hptr, is_signed, &lay); if (rc) return rc;
+  rc = mul_row_words(ctx, "sc_mul_prep", lay, aw, bw, ew, nw); if (rc) return rc;
+  if (launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, nw, ew, count, R, e, rab)) return fail(ctx, SC_ERR_HIP, "sc_mul_prep: launch failed");
+  return SC_OK;
+}
+
+int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p,
+                 uint32_t* prod, uint32_t* bad, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  if (!ctx || !n_hptr || nw <= 0 || !p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_mul_split: bad argument");
+  MulLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = mul_layout(ctx, "sc_mul_split", big_bits(n), kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
+  if (launch_mul_split(ctx->stream, p, nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_mul_split: launch failed");
+  return SC_OK;
+}
+
 // ---- compare-exchange finish of a secure sort: both outputs of every column from one shared inversion ----------
 // The nf columns run as flat items (nf * count of them), so the program does not depend on nf and an index row entry is read at the
 // item's flat number.  Per item, with V = U^-1 R^3 (one product, shared by both outputs): hi = F ab ab V / R^3 = F ab^2 U^-1 and

@@ -748,10 +748,11 @@ static int sel_pow2(sc_ctx* ctx, const PaillierKey& k, int bits, const uint32_t*
   return sc_modexp_shared(ctx, k.mod_n2, it->second, x, 2 * k.nw, mul_into, out, count);
 }
 
-// T_j = [[sigma]]^(e_j) [[d_j]]^(r_a) (1 + rab_j N) for the flat items j count + i (selection.select_t): t_out [nf count][2 nw]
-static int sel_t(sc_ctx* ctx, const PaillierKey& k, const SelLayout& lay, const uint32_t* sigma, const uint32_t* d, const uint32_t* r_a, int aw,
-                 const uint32_t* e, int ew, const uint32_t* rab, uint32_t* t_out, uint64_t count) {
-  const int nf = lay.nf, w2 = 2 * k.nw, ebits = sel_t_bits(lay);
+// T_j = [[sigma]]^(e_j) [[d_j]]^(r_a) (1 + rab_j N) for the flat items j count + i (selection.select_t): t_out [nf count][2 nw].
+// The multiplication's T_j (8e) is the same product with sigma = x, d_j = y_j, e_j = e_x_j and r_a = e_y, exponents of `ebits` bits.
+static int two_base_t(sc_ctx* ctx, const PaillierKey& k, int nf, int ebits, const uint32_t* sigma, const uint32_t* d, const uint32_t* r_a, int aw,
+                      const uint32_t* e, int ew, const uint32_t* rab, uint32_t* t_out, uint64_t count) {
+  const int w2 = 2 * k.nw;
   const uint64_t items = (uint64_t)nf * count;
   uint32_t *x, *ex, *mi;
   int rc = tmp_words(ctx, TMP_SEL_A, 2 * items * w2, &x); if (rc) return rc;
@@ -778,6 +779,10 @@ static int sel_t(sc_ctx* ctx, const PaillierKey& k, const SelLayout& lay, const 
   rc = sc_modmul(ctx, k.mod_n2, mi, w2, t_out, w2, mi, items); if (rc) return rc;
   rc = sc_modexp_var(ctx, k.mod_n2, x + items * w2, ex_a, ew, ebits, -1, nullptr, 0, t_out, items); if (rc) return rc;
   return sc_modmul(ctx, k.mod_n2, mi, w2, t_out, w2, t_out, items);
+}
+static int sel_t(sc_ctx* ctx, const PaillierKey& k, const SelLayout& lay, const uint32_t* sigma, const uint32_t* d, const uint32_t* r_a, int aw,
+                 const uint32_t* e, int ew, const uint32_t* rab, uint32_t* t_out, uint64_t count) {
+  return two_base_t(ctx, k, lay.nf, sel_t_bits(lay), sigma, d, r_a, aw, e, ew, rab, t_out, count);
 }
 
 static int sel_finish_args(sc_ctx* ctx, const char* who, const PaillierKey* kp, const SelLayout& lay, int aw, int ew, bool ptrs_ok) {
@@ -983,6 +988,117 @@ int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int nfie
   rc = sc_modmul(ctx, k.mod_n2, T, w2, products, w2, U, items); if (rc) return rc;
   rc = sc_modinv(ctx, k.mod_n2, U, u_inv, items, nullptr); if (rc) return rc;
   return sc_select_finish_cx(ctx, k.mod_n2, nfields, T, products, u_inv, f_enc, g_enc, lo_index, hi_index, out, out_rows, count);
+}
+
+// ---- secure multiplication -------------------------------------------------------------------------------------------
+// The selection's round trip with both factors blinded: P carries A = x + e_y and B_j = y_j + e_x_j, the key holder returns [[A B_j]],
+// and [[x y_j]] = [[A B_j]] T_j^-1 with T_j = [[x]]^(e_x_j) [[y_j]]^(e_y) (1 + e_x_j e_y N).  Same temporaries as the selection's.
+static int mul_key_layout(sc_ctx* ctx, const char* who, const PaillierKey& k, int kappa, int wx, int nf, const int* wy, int is_signed, MulLayout* lay) {
+  return mul_layout(ctx, who, big_bits(k.n), kappa, wx, nf, wy, is_signed, lay);
+}
+
+int sc_initiator_mul_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
+                          const uint32_t* x_enc, const uint32_t* y_enc, const uint32_t* r_a, int aw, const uint32_t* r_b, int bw,
+                          const uint32_t* rho_p, int ew, uint32_t* p_out, uint32_t* e_out, uint32_t* rab_out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: bad key");
+  const PaillierKey k = *kp;
+  MulLayout lay;
+  int rc = mul_key_layout(ctx, "sc_initiator_mul_pack", k, kappa, wx, nfields, wy_hptr, is_signed, &lay); if (rc) return rc;
+  if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: rho_p is required: P must carry a fresh rho^N");
+  if (!x_enc || !y_enc || !r_a || !r_b || !p_out || !e_out || !rab_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: bad argument");
+  rc = mul_row_words(ctx, "sc_initiator_mul_pack", lay, aw, bw, ew, k.nw); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw;
+  const size_t col = (size_t)count * w2;
+  uint32_t *R, *m, *acc;
+  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &R); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, col, &m); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, 2 * col, &acc); if (rc) return rc;
+  if (launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_mul_pack: launch failed");
+  const Prog* p;
+  rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {     // the selection's program
+    const int cn = bd.use_const(k.cst_n);
+    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
+    bd.mul_const(0); bd.mul_extw(0);                                      // [[x + R]]
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(x_enc, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(m, w2, w2)};
+  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, count); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, paillier_key_id, m, rho_p, m, count); if (rc) return rc;      // * rho_p^N
+  // prod_j [[y_j]]^(2^off_j): sc_initiator_select_pack's Horner chain of shared-exponent squarings, with this layout's offsets
+  const uint32_t* t = y_enc + (size_t)(nfields - 1) * col;
+  for (int j = nfields - 1; j >= 0; j--) {
+    uint32_t* dst = j == 0 ? p_out : acc + (size_t)(j & 1) * col;
+    rc = sel_pow2(ctx, k, lay.off[j] - (j > 0 ? lay.off[j - 1] : 0), t, j > 0 ? y_enc + (size_t)(j - 1) * col : m, dst, count); if (rc) return rc;
+    t = dst;
+  }
+  return SC_OK;
+}
+
+int sc_keyholder_mul(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p_enc,
+                     const uint32_t* rho_products, uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_mul: needs the secret key");
+  const PaillierKey k = *kp;
+  MulLayout lay;
+  int rc = mul_key_layout(ctx, "sc_keyholder_mul", k, kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  if (!p_enc || !rho_products || !out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_mul: bad argument");
+  const uint64_t items = (uint64_t)nfields * count;
+  uint32_t *pl, *prod, *c;
+  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &pl); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, items * k.nw, &prod); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, items * 2 * k.nw, &c); if (rc) return rc;
+  uint32_t* bad;                              // the pinned verdict word of sc_keyholder_select_mult
+  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
+  *(volatile uint32_t*)bad = 0;
+  rc = sc_paillier_decrypt(ctx, paillier_key_id, p_enc, pl, count); if (rc) return rc;
+  if (launch_mul_split(ctx->stream, pl, k.nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_keyholder_mul: launch failed");
+  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, prod, k.nw, c, items); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, paillier_key_id, c, rho_products, out, items); if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (*(volatile uint32_t*)bad)
+    return fail(ctx, SC_ERR_LAYOUT, "mul: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)");
+  return SC_OK;
+}
+
+int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* x_enc,
+                            const uint32_t* y_enc, const uint32_t* products, const uint32_t* e, int ew, const uint32_t* rab,
+                            const uint32_t* base, int coef, uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: bad key");
+  const PaillierKey k = *kp;
+  MulLayout lay;
+  int rc = mul_key_layout(ctx, "sc_initiator_mul_finish", k, kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
+  if (!x_enc || !y_enc || !products || !e || !rab || !out || ew < 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: bad argument");
+  if (coef != 1 && coef != -1 && coef != -2) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: coef = %d: expected +1, -1 or -2", coef);
+  if (32 * ew < mul_ebits(lay)) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: exponent rows of %d words are too narrow for %d bits", ew, mul_ebits(lay));
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw;
+  const uint64_t items = (uint64_t)nfields * count;
+  uint32_t *T, *inv;
+  rc = tmp_words(ctx, TMP_SEL_D, items * w2, &T); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_E, items * w2, &inv); if (rc) return rc;
+  rc = two_base_t(ctx, k, nfields, mul_ebits(lay), x_enc, y_enc, e + items * ew /* e_y */, ew, e, ew, rab, T, count); if (rc) return rc;
+  // [[x y]]^coef = ([[A B]] T^-1)^coef: coef = +1 inverts T, a negative coef inverts [[A B]] instead -- one inversion pass either way
+  const uint32_t* num = coef == 1 ? products : T;
+  rc = sc_modinv(ctx, k.mod_n2, coef == 1 ? T : products, inv, items, nullptr); if (rc) return rc;
+  // one launch: the lift num R^m for the m Montgomery products that follow, (num inv)^|coef|, then the base
+  const int pairs = coef == -2 ? 2 : 1, nmul = 2 * pairs - 1 + (base ? 1 : 0);
+  const Mod& m2 = ctx->mods[k.mod_n2];
+  int cid;
+  { Big one(m2.nwords, 0); one[0] = 1; rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one, m2.n, nmul * m2.W * m2.S), &cid); if (rc) return rc; }   // R^nmul mod N^2
+  const Prog* p;
+  rc = cached_prog(ctx, "mulfin:" + std::to_string(k.mod_n2) + ":" + std::to_string(pairs) + (base ? ":b" : ""), k.mod_n2, [&](Builder& bd) {
+    bd.loadw(0); bd.mul_const(bd.use_const(cid));                         // num R^nmul
+    bd.mul_extw(1);                                                       // num inv
+    if (pairs == 2) { bd.mul_extw(0); bd.mul_extw(1); }                   // (num inv)^2
+    if (base) bd.mul_extw(2);
+    bd.storew(3);
+  }, &p); if (rc) return rc;
+  VmExt ex[4] = {mk_ext(num, w2, w2), mk_ext(inv, w2, w2), mk_ext(base, w2, w2), mk_ext(out, w2, w2)};
+  return run_vm(ctx, k.mod_n2, *p, ex, 4, items);
 }
 
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {

@@ -86,6 +86,14 @@ struct SelLayout {
   int off[SEL_MAX_FIELDS], fbits[SEL_MAX_FIELDS], width[SEL_MAX_FIELDS];
 };
 
+// Field layout of a secure multiplication's packed plaintext (k_mul_prep / k_mul_split, sc_kernel_plain.h): A in [0, s), then B_j
+constexpr int MUL_MAX_WIDTH = 255;
+constexpr int MUL_FIELD_WORDS = 10;   // a field or an exponent has at most 255 + 62 + 1 = 318 bits
+struct MulLayout {
+  int s, nf, end, wx, is_signed;   // end as in SelLayout
+  int off[SEL_MAX_FIELDS], fbits[SEL_MAX_FIELDS], wy[SEL_MAX_FIELDS];
+};
+
 constexpr int VM_MAX_EXT = 8;
 constexpr int VM_MAX_CONST = 8;  // including R^2 and R
 

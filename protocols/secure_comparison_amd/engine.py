@@ -1021,6 +1021,63 @@ class Engine:
                                                     out.numel() // (2 * nw), count))
         return out
 
+    # ------------------------------------------------------------------ secure multiplication (one library call each)
+    def initiator_mul_pack(self, key: PaillierKey, kappa: int, wx: int, wy, signed: bool, x_enc: torch.Tensor, y_enc: torch.Tensor,
+                           r_a: torch.Tensor, r_b: torch.Tensor, rho_p: torch.Tensor | None, ew: int):
+        """The message P [count][2nw] and the finish's plaintext arrays (e [nf + 1][count][ew], the last plane e_y; rab [nf][count][nw])
+        (sc_initiator_mul_pack).  A missing rho_p is the library's ValueError."""
+        nf, nw = len(wy), key.mod_n.nwords
+        count = self._items(x_enc)
+        self._arr(x_enc, "x_enc", count, 2 * nw)
+        self._columns(y_enc, "y_enc", nf, count, 2 * nw)
+        self._arr(r_a, "r_a", count)
+        self._columns(r_b, "r_b", nf, count, None)
+        self._arr(rho_p, "rho_p", count, nw, optional=True)
+        P = self.empty(count, 2 * nw)
+        e = torch.empty((nf + 1, count, int(ew)), dtype=torch.int32, device=self.device)
+        rab = torch.empty((nf, count, nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(wy)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_mul_pack(self.ctx, key.id, int(kappa), int(wx), nf, pw, int(bool(signed)), self._ptr(x_enc),
+                                                   self._ptr(y_enc), self._ptr(r_a), r_a.shape[-1], self._ptr(r_b), r_b.shape[-1],
+                                                   self._ptr(rho_p), int(ew), self._ptr(P), self._ptr(e), self._ptr(rab), count))
+        return P, e, rab
+
+    def keyholder_mul(self, key: PaillierKey, kappa: int, wx: int, wy, P: torch.Tensor, rho_products: torch.Tensor) -> torch.Tensor:
+        """The key holder's randomized [[A B_j]] [nf][count][2nw] from P (sc_keyholder_mul); ValueError when a decrypted row exceeds
+        the layout."""
+        nf, nw = len(wy), key.mod_n.nwords
+        count = self._items(P)
+        self._arr(P, "P", count, 2 * nw)
+        self._columns(rho_products, "rho_products", nf, count, nw)
+        out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(wy)
+        self._sync_stream()
+        self._check(self.lib.sc_keyholder_mul(self.ctx, key.id, int(kappa), int(wx), nf, pw, self._ptr(P), self._ptr(rho_products),
+                                              self._ptr(out), count))
+        return out
+
+    def initiator_mul_finish(self, key: PaillierKey, kappa: int, wx: int, wy, x_enc: torch.Tensor, y_enc: torch.Tensor,
+                             products: torch.Tensor, e: torch.Tensor, rab: torch.Tensor, base: torch.Tensor | None = None,
+                             coef: int = 1) -> torch.Tensor:
+        """base_j [[x y_j]]^coef [nf][count][2nw] from the key holder's products (sc_initiator_mul_finish); coef in {+1, -1, -2}."""
+        nf, nw = len(wy), key.mod_n.nwords
+        count = self._items(x_enc)
+        self._arr(x_enc, "x_enc", count, 2 * nw)
+        self._columns(y_enc, "y_enc", nf, count, 2 * nw)
+        self._columns(products, "products", nf, count, 2 * nw)
+        self._columns(e, "e", nf + 1, count, None)
+        self._columns(rab, "rab", nf, count, nw)
+        if base is not None:
+            self._columns(base, "base", nf, count, 2 * nw)
+        out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
+        wa, pw = self._widths(wy)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_mul_finish(self.ctx, key.id, int(kappa), int(wx), nf, pw, self._ptr(x_enc), self._ptr(y_enc),
+                                                     self._ptr(products), self._ptr(e), e.shape[-1], self._ptr(rab), self._ptr(base),
+                                                     int(coef), self._ptr(out), count))
+        return out
+
     # ------------------------------------------------------------------ device-side CSPRNG (sc_rng_*)
     def rng_seed(self, key: bytes | None = None) -> None:
         """Key the context's generator: 32 bytes from the caller (reproducible tests) or, with None, from the OS.  An unseeded

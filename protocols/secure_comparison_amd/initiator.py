@@ -444,6 +444,25 @@ class Initiator:
         return await alice_topk(self, v_enc, m, payload, payload_bits, largest, return_indices, kappa, source, engine, generator, chunks,
                                 max_rows, only_last)
 
+    # ---- secure multiplication and equality (multiplication.py)
+    async def perform_secure_multiply_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor, x_bits: int, y_bits, signed: bool = False,
+                                            kappa: int = 40, draws=None, source: str = "device", engine=None, generator=None,
+                                            chunks: int = 1) -> torch.Tensor:
+        """[[x y_j]] as multiplication.secure_multiply_batch: `mul_1_batch_{tag}` carries an int32 header (kappa, x_bits, signed, the
+        number of columns, their widths) and P, `mul_2_batch_{tag}` the key holder's products.  chunks > 1 is not supported
+        (ValueError)."""
+        from .multiplication import alice_multiply
+
+        return await alice_multiply(self, x_enc, y_enc, x_bits, y_bits, signed, kappa, draws, source, engine, generator, chunks)
+
+    async def perform_secure_equal_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor, draws=None, mul_draws=None, kappa: int = 40,
+                                         source: str = "device", engine=None, generator=None, chunks: int = 1):
+        """([[x == y]], [[x <= y]], [[y <= x]]) for B pairs: ONE comparison session of 2B rows -- (x, y) stacked on (y, x), its
+        messages those of perform_secure_comparison_batch -- then one multiplication exchange for the AND of the two bits."""
+        from .multiplication import alice_equal
+
+        return await alice_equal(self, x_enc, y_enc, draws, mul_draws, kappa, source, engine, generator, chunks)
+
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""
         if self.communicator is None:

@@ -319,6 +319,21 @@ class KeyHolder:
 
         await bob_topk(self, k, m, payload_bits, return_indices, kappa, only_last, source, generator, max_rows)
 
+    # ---- secure multiplication and equality (multiplication.py)
+    async def perform_secure_multiply_batch(self, x_bits: int, y_bits, signed: bool = False, kappa: int = 40, draws=None,
+                                            source: str = "device", generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_multiply_batch: the initiator's header must announce this kappa, these widths and
+        this signedness (ValueError before anything is decrypted); `count` (optional) is the batch size he expects."""
+        from .multiplication import bob_multiply
+
+        await bob_multiply(self, x_bits, y_bits, signed, kappa, draws, source, generator, count)
+
+    async def perform_secure_equal_batch(self, draws=None, mul_draws=None, kappa: int = 40, source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_equal_batch: the comparison session of 2B rows, then one multiplication exchange."""
+        from .multiplication import bob_equal
+
+        await bob_equal(self, draws, mul_draws, kappa, source, generator)
+
     async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
         message when it has been received already.  Returns the session's batch size."""
