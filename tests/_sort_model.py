@@ -55,16 +55,21 @@ def apply(layers, rows, descending=False, key=lambda t: t[0]):
     return out
 
 
-def compare_exchange(sk, kappa, widths, delta, f_cs, g_cs, draws, shared_inversion=True):
+def compare_exchange(sk, kappa, widths, delta, f_cs, g_cs, draws, shared_inversion=True, d_key=None, trace=None):
     """([[lo_j]], [[hi_j]]) of one compare-exchange from [[delta]] and the operand ciphertexts of every column: the selection with
     sigma = delta, base F_j and d_j = G_j F_j^-1 (1 + 2^w_j N), then hi = F ab^2 U^-1 and lo = G T^2 U^-1 with U = T ab (one
-    inversion), or -- shared_inversion=False -- S = ab T^-1, hi = F S, lo = G S^-1 (two)."""
+    inversion), or -- shared_inversion=False -- S = ab T^-1, hi = F S, lo = G S^-1 (two).  d_key: the key column's [[d]] when it is
+    the comparison's own (the same plaintext under the randomizer of the sent [[z]]); trace: receives P and Bob's products."""
     n, n2 = sk.n, sk.n2
     r_a, r_bs, rho_p, rhos = draws
     d_cs = [g * pow(f, -1, n2) % n2 * (1 + (1 << w) * n) % n2 for f, g, w in zip(f_cs, g_cs, widths)]
+    if d_key is not None:
+        d_cs[0] = d_key
     P = sm.pack(sk, kappa, widths, delta, d_cs, r_a, r_bs, rho_p)
     ab_cs, _, bad = sm.mult(sk, kappa, widths, P, rhos)
     assert not bad
+    if trace is not None:
+        trace.update(P=P, products=ab_cs)
     lo, hi = [], []
     for w, f, g, d, ab, r_b in zip(widths, f_cs, g_cs, d_cs, ab_cs, r_bs):
         T = pow(delta, r_b + (1 << w), n2) * pow(d, r_a, n2) % n2 * sm.enc(sk, r_a * r_b) % n2
