@@ -258,6 +258,44 @@ int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key, int kappa, int wx, in
                             const uint32_t* y_enc_dptr, const uint32_t* products_dptr, const uint32_t* e_dptr, int ew,
                             const uint32_t* rab_dptr, const uint32_t* base_dptr /* nullable */, int coef, uint32_t* out_dptr,
                             uint64_t count);
+/* ---- secure inner product: [[sum_j x_j y_j]] from k pairs per row, one round trip, one ciphertext back ------------ */
+/* The multiplication's round trip with the sum taken by the key holder under the blinding: the initiator packs the blinded pairs
+ * (A_j, B_j) = (x_j + a_j, y_j + b_j), g to a message and M = ceil(k / g) messages per row, the key holder returns ONE fresh [[D]],
+ * D = sum_j A_j B_j, and [[sum_j x_j y_j]] = [[D]] T^-1 with T = prod_j [[x_j]]^(b_j) [[y_j]]^(a_j) (1 + S N), S = sum_j a_j b_j.
+ * square != 0 computes [[sum_j x_j^2]]: no y, no b, D = sum_j A_j^2, T = prod_j [[x_j]]^(2 a_j) (1 + S N), S = sum_j a_j^2.
+ * LAYOUT (kappa, wx, wy, is_signed, square, k): one width per side, 1 <= wx, wy <= 255 (wy is not read for a square), 1 <= kappa <= 62,
+ * 1 <= k <= 1024; 0 <= x_j < 2^wx, 0 <= y_j < 2^wy, or -2^(w-1) <= value < 2^(w-1) as residues modulo N when is_signed.  sa = wx +
+ * kappa + 1, sb = wy + kappa + 1 (0 for a square), pb = sa + sb; g = the largest integer with g pb < bits(N) - 1 must be >= 1, and
+ * pb' + ceil(log2 k) < bits(N) - 1 with pb' = sa + sb (2 sa for a square) keeps the sum below N; M = ceil(k / g); pair j lives in
+ * message j mod M at position j div M; ebits = max(sa, sb), sa + 1 for a square.  sc_dot_layout evaluates that rule on the host alone
+ * (no context, no device work): out = {sa, sb, pb, g, M, ebits}, SC_ERR_ARG when a quantity is out of range or does not fit.  Every
+ * entry below checks the same rule against its key before anything is launched (SC_ERR_ARG, sc_last_error names the quantity).
+ * Arrays, scratch, stream and the keys served: as the multiplication's entries (no SC_ERR_UNSUPPORTED where the modulus has no pair
+ * kernel with per-row exponents).  Still SC_ABI_VERSION 5: additions. */
+int sc_dot_layout(int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, int* out /* sa, sb, pb, g, M, ebits */);
+/* Initiator, the messages P_m = prod_t [[x_(tM+m)]]^(2^(t pb)) [[y_(tM+m)]]^(2^(t pb + sa)) (1 + R_m N) rho_p_m^N and the plaintext
+ * arrays the finish needs.  x_enc, y_enc: [k][count][2 nwords]; r_a: [k][count][aw] below 2^(wx + kappa), r_b: [k][count][bw] below
+ * 2^(wy + kappa), aw, bw <= 10 -- an independent mask per field: the key holder sees every A_j of a row, a shared mask would show
+ * him x_i - x_j; rho_p: [M][count][nwords] in [1, N), NOT nullable (SC_ERR_ARG), for sc_initiator_select_pack's reason.  p_out:
+ * [M][count][2 nwords]; e_out: [2k][count][ew] (planes 0 .. k-1 = b_j, k .. 2k-1 = a_j; for a square [k][count][ew] = 2 a_j),
+ * 32 ew >= ebits; s_out: [count][nwords] = S.  y_enc and r_b are not read for a square (null allowed). */
+int sc_initiator_dot_pack(sc_ctx* ctx, int paillier_key, int kappa, int wx, int wy, int is_signed, int square, int k,
+                          const uint32_t* x_enc_dptr, const uint32_t* y_enc_dptr, const uint32_t* r_a_dptr, int aw,
+                          const uint32_t* r_b_dptr, int bw, const uint32_t* rho_p_dptr, int ew, uint32_t* p_out_dptr,
+                          uint32_t* e_out_dptr, uint32_t* s_out_dptr, uint64_t count);
+/* Key holder (secret key): CRT decryption of the M count messages, D = sum_j A_j B_j per row (sc_dot_split), its encryption randomized
+ * with rho_d [count][nwords]: out [count][2 nwords], one ciphertext per row whatever k is.  SC_ERR_LAYOUT when a decrypted message
+ * has a bit at or above its own end (`out` is unspecified then); a narrower layout is seen only on the wire.  Synchronous. */
+int sc_keyholder_dot(sc_ctx* ctx, int paillier_key, int kappa, int wx, int wy, int square, int k, const uint32_t* p_enc_dptr,
+                     const uint32_t* rho_d_dptr, uint32_t* out_dptr, uint64_t count);
+/* Initiator: out = base [[sum_j x_j y_j]]^coef, [count][2 nwords], coef in {+1, -1, -2} and base (nullable) as
+ * sc_initiator_mul_finish's.  d_enc = the key holder's answer, e / s = sc_initiator_dot_pack's.  T is built from per-row
+ * exponentiations over groups of at most three consecutive planes, then ONE inversion pass over count items (synchronous,
+ * SC_ERR_NOT_INVERTIBLE names the row through sc_last_bad_index) and one launch. */
+int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key, int kappa, int wx, int wy, int square, int k, const uint32_t* x_enc_dptr,
+                            const uint32_t* y_enc_dptr, const uint32_t* d_enc_dptr, const uint32_t* e_dptr, int ew,
+                            const uint32_t* s_dptr, const uint32_t* base_dptr /* nullable */, int coef, uint32_t* out_dptr,
+                            uint64_t count);
 /* The network of a secure top-m (8d): the comparators that bring the m smallest of k values to the positions 0 .. m-1 in ascending
  * order -- with only_last, the m-th smallest to position m-1 alone -- for 1 <= m <= k <= 1024 (SC_ERR_ARG otherwise).  Host only: no
  * context, no device work, a pure function of (k, m, only_last) that both players evaluate.  Comparator t puts the smaller value at

@@ -224,6 +224,23 @@ int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, 
  * set to 1 (never cleared here) when a row has a bit at or above the end of the last field. */
 int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr,
                  const uint32_t* p_dptr, uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
+/* ---- secure inner product: the plaintext-word halves of the two players ----------------------------- */
+/* A row has k pairs (A_j, B_j), A_j = x_j + a_j of sa = wx + kappa + 1 bits and B_j = y_j + b_j of sb = wy + kappa + 1 bits, pb = sa + sb
+ * bits per pair, g = the largest integer with g pb < bits(N) - 1 pairs per message and M = ceil(k / g) messages per row; pair j lives in
+ * message j mod M at position t = j div M, A in bits [t pb, t pb + sa), B above it.  square != 0: every pair is the one field A_j
+ * (sb = 0, pb = sa; wy, r_b and y are not read).  Layout (sc_dot_layout's rule): 1 <= kappa <= 62, 1 <= wx, wy <= 255, 1 <= k <= 1024,
+ * g >= 1 and pb' + ceil(log2 k) < bits(N) - 1 with pb' = sa + sb (2 sa for a square); SC_ERR_ARG otherwise, against N (n_hptr, nw words).
+ * sc_dot_prep (initiator): from r_a [k][count][aw] (< 2^(wx + kappa)) and r_b [k][count][bw] (< 2^(wy + kappa)), aw, bw <= 10, every
+ * field with a mask of its own: with a_j = r_a_j + ox, b_j = r_b_j + oy (ox = 2^(wx - 1), oy = 2^(wy - 1) when is_signed, else 0),
+ * e [2k][count][ew]: planes 0 .. k-1 = b_j (the exponents of x_j), planes k .. 2k-1 = a_j (the exponents of y_j); R [M][count][nw] the
+ * packed masks of every message; S [count][nw] = sum_j a_j b_j.  Square: e [k][count][ew] = 2 a_j, S = sum_j a_j^2.  32 ew >= ebits. */
+int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int is_signed, int square, int k,
+                const uint32_t* r_a_dptr, int aw, const uint32_t* r_b_dptr /* nullable when square */, int bw, int ew, uint32_t* e_dptr,
+                uint32_t* R_dptr, uint32_t* S_dptr, uint64_t count);
+/* sc_dot_split (key holder): from the decrypted P [M][count][nw]: D [count][nw] = sum_j A_j B_j (square: sum_j A_j^2).  *bad_dptr (one
+ * uint32, never cleared here) is set to 1 when a message has a bit at or above its OWN end n_m pb, n_m = the pairs it holds. */
+int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int square, int k, const uint32_t* p_dptr,
+                 uint32_t* D_dptr, uint32_t* bad_dptr, uint64_t count);
 /* sc_select_finish_cx (initiator, the compare-exchange of a secure sort): from a selection with sigma = delta,
  * base F and d = G - F + 2^w, both outputs hi = F ab^2 u_inv and lo = G t^2 u_inv modulo mod (N^2), where u_inv = (t ab)^-1.
  * t, ab, u_inv, f, g: [nfields][count][words(mod)], nfields 1 .. 4.  lo_index / hi_index (both or neither): uint64 [nfields][count],

@@ -13,13 +13,13 @@ SYMBOLS = [
     "sc_malloc", "sc_free", "sc_memcpy_h2d", "sc_memcpy_d2h",
     "sc_mod_create", "sc_mod_words", "sc_exp_create", "sc_const_create", "sc_fbt_create", "sc_fbt_import", "sc_fbt_bytes",
     "sc_modmul", "sc_modmul_const", "sc_modmul_const_sel", "sc_modexp_shared", "sc_modexp_shared_sq", "sc_modexp_var_sq", "sc_mod_supports_sq", "sc_modexp_shared_isone", "sc_modexp_shared_isone_any", "sc_fixedbase_pow", "sc_modexp_var", "sc_modexp_var_scatter",
-    "sc_modinv", "sc_paillier_encrypt_raw", "sc_paillier_encrypt_raw_neg", "sc_paillier_l_mul", "sc_crt_combine", "sc_plain_alice", "sc_plain_bob", "sc_select_prep", "sc_select_split", "sc_select_finish_cx", "sc_mul_prep", "sc_mul_split", "sc_dgk_step4",
+    "sc_modinv", "sc_paillier_encrypt_raw", "sc_paillier_encrypt_raw_neg", "sc_paillier_l_mul", "sc_crt_combine", "sc_plain_alice", "sc_plain_bob", "sc_select_prep", "sc_select_split", "sc_select_finish_cx", "sc_mul_prep", "sc_mul_split", "sc_dot_prep", "sc_dot_split", "sc_dgk_step4",
     "sc_paillier_key_create", "sc_paillier_key_mods", "sc_paillier_encrypt", "sc_paillier_randomize", "sc_paillier_decrypt",
     "sc_dgk_key_create", "sc_dgk_key_info", "sc_dgk_randomize", "sc_dgk_encrypt_bits_randomized", "sc_dgk_is_zero", "sc_dgk_any_zero",
     "sc_initiator_step1", "sc_keyholder_step2_4b", "sc_initiator_step4", "sc_initiator_step4i", "sc_keyholder_step4j_5", "sc_initiator_step67",
     "sc_initiator_select_d", "sc_paillier_one_minus", "sc_initiator_cx_differences", "sc_initiator_select_pack", "sc_keyholder_select_mult",
     "sc_initiator_select_finish", "sc_initiator_cx_finish", "sc_initiator_mul_pack", "sc_keyholder_mul", "sc_initiator_mul_finish",
-    "sc_topk_network",
+    "sc_topk_network", "sc_dot_layout", "sc_initiator_dot_pack", "sc_keyholder_dot", "sc_initiator_dot_finish",
     "sc_rng_seed", "sc_rng_bits", "sc_rng_below", "sc_rng_coins", "sc_rng_permutations",
     "sc_peak_probe", "sc_mac_counter", "sc_table_traffic_probe", "sc_ctx_set_latency_mode", "sc_ctx_set_onelane_mode", "sc_ctx_set_chip_share", "sc_ctx_set_fork_mode", "sc_ctx_set_pair_policy", "sc_ctx_stats", "sc_ctx_launch_counts", "sc_ctx_policy", "sc_clock_probe", "sc_comm_unique_id", "sc_comm_init", "sc_allgather", "sc_comm_destroy",
 ]
@@ -91,6 +91,8 @@ def load() -> C.CDLL:
         "sc_select_finish_cx": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64]),
         "sc_mul_prep": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, u64]),
         "sc_mul_split": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, u64]),
+        "sc_dot_prep": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, u64]),
+        "sc_dot_split": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
         "sc_dgk_step4": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64]),
         "sc_paillier_key_create": (i32, [vp, vp, i32, vp, vp, i32, i32, ip]),
         "sc_paillier_key_mods": (i32, [vp, i32, ip, ip]),
@@ -120,6 +122,10 @@ def load() -> C.CDLL:
         "sc_keyholder_mul": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, u64]),
         "sc_initiator_mul_finish": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, u64]),
         "sc_topk_network": (i32, [i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), ip, ip]),
+        "sc_dot_layout": (i32, [i32, i32, i32, i32, i32, i32, i32, ip]),
+        "sc_initiator_dot_pack": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, u64]),
+        "sc_keyholder_dot": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
+        "sc_initiator_dot_finish": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, u64]),
         "sc_rng_seed": (i32, [vp, vp]),
         "sc_rng_bits": (i32, [vp, i32, vp, u64]),
         "sc_rng_below": (i32, [vp, vp, i32, i32, vp, u64]),

@@ -276,6 +276,10 @@ int launch_select_split(hipStream_t stream, const uint32_t* p, int nw, const sc:
 int launch_mul_prep(hipStream_t stream, const uint32_t* ra, int aw, const uint32_t* rb, int bw, const sc::MulLayout& lay, int nw, int ew,
                     uint64_t count, uint32_t* R, uint32_t* e, uint32_t* rab);
 int launch_mul_split(hipStream_t stream, const uint32_t* p, int nw, const sc::MulLayout& lay, uint64_t count, uint32_t* prod, uint32_t* bad);
+// sc_launch_dot.hip
+int launch_dot_prep(hipStream_t stream, const uint32_t* ra, int aw, const uint32_t* rb, int bw, const sc::DotLayout& lay, int nw, int ew,
+                    uint64_t count, uint32_t* e, uint32_t* R, uint32_t* S);
+int launch_dot_split(hipStream_t stream, const uint32_t* p, int nw, const sc::DotLayout& lay, uint64_t count, uint32_t* D, uint32_t* bad);
 // sc_launch_misc.hip again
 int launch_rng_bits(hipStream_t stream, const sc::RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count);
 int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, const uint32_t* d_n, int nbits, int nw, int nonzero, uint32_t* out, uint64_t count);

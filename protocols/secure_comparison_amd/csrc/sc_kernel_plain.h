@@ -1,5 +1,5 @@
 // Plain-word helper kernels of the protocol steps (gfx950).  Included by sc_launch_misc.hip and, for the multiplication's two, by
-// sc_launch_mul.hip.
+// sc_launch_mul.hip; for the inner product's two, by sc_launch_dot.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -151,7 +151,7 @@ __device__ __forceinline__ void sel_mul64(uint64_t a, const uint32_t* b, int bw,
   }
 }
 
-#ifndef SC_MUL_UNIT   // sc_launch_mul.hip takes the helpers above and the multiplication's kernels below, not these two
+#if !defined(SC_MUL_UNIT) && !defined(SC_DOT_UNIT)   // sc_launch_mul.hip / sc_launch_dot.hip take the helpers above and their own kernels below, not these two
 // The initiator's plaintext values of a selection from her draws r_a [count][aw] (< 2^kappa) and r_b [nf][count][bw]:
 //   R = r_a + sum_j 2^off[j] r_b_j ([count][nw]), e_j = r_b_j + 2^width[j] ([nf][count][ew]), rab_j = r_a r_b_j ([nf][count][nw]).
 __global__ void k_select_prep(const uint32_t* __restrict__ ra, int aw, const uint32_t* __restrict__ rb, int bw, SelLayout lay, int nw,
@@ -206,7 +206,7 @@ __global__ void k_select_split(const uint32_t* __restrict__ p, int nw, SelLayout
   }
 }
 
-#endif  // !SC_MUL_UNIT
+#endif  // !SC_MUL_UNIT && !SC_DOT_UNIT
 
 // ---------------------------------------------------------------------------------------------
 // Secure multiplication (sc_mul_prep / sc_mul_split, include/sc_amd_dev.h).  Layout of the packed plaintext of P, low
@@ -286,5 +286,145 @@ __global__ void k_mul_split(const uint32_t* __restrict__ p, int nw, MulLayout la
   }
 }
 #endif  // SC_MUL_UNIT
+
+// ---------------------------------------------------------------------------------------------
+// Secure inner product (sc_dot_prep / sc_dot_split, include/sc_amd_dev.h).  A row has k pairs (A_j, B_j), A_j = x_j + a_j
+// of sa bits and B_j = y_j + b_j of sb bits, pb = sa + sb bits per pair (square mode: the one field A_j, pb = sa).  Pair j lives in
+// message j mod M at position t = j div M: A in bits [t pb, t pb + sa), B in [t pb + sa, (t + 1) pb).  Message m holds the
+// n_m = |{j < k : j mod M = m}| <= g pairs j = m, m + M, .. and ends at bit n_m pb.  One thread per row, one pass over the pairs with two
+// field buffers and one accumulator, every one of them indexed by constants only so that they stay in registers.
+// ---------------------------------------------------------------------------------------------
+// (DotLayout, DOT_ACC_WORDS: sc_vm.h)  Compiled and launched by sc_launch_dot.hip alone (SC_DOT_UNIT).
+#ifdef SC_DOT_UNIT
+
+// v = x (xw words, 0 past its end) + 2^bit when bit >= 0
+__device__ __forceinline__ void dot_load_field(const uint32_t* x, int xw, int bit, uint32_t (&v)[MUL_FIELD_WORDS]) {
+  uint32_t carry = 0;
+#pragma unroll
+  for (int k = 0; k < MUL_FIELD_WORDS; k++) {
+    const uint64_t t = (uint64_t)(k < xw ? x[k] : 0u) + carry + ((bit >= 0 && k == (bit >> 5)) ? (1u << (bit & 31)) : 0u);
+    v[k] = (uint32_t)t;
+    carry = (uint32_t)(t >> 32);
+  }
+}
+// acc += a * b: schoolbook by columns with a 96-bit column sum that also takes acc's own word, so the carry of the running sum
+// travels through every word of acc, not only through the words of this one product
+__device__ __forceinline__ void dot_mac(const uint32_t (&a)[MUL_FIELD_WORDS], const uint32_t (&b)[MUL_FIELD_WORDS], uint32_t (&acc)[DOT_ACC_WORDS]) {
+  uint64_t col = 0;
+  uint32_t top = 0;
+#pragma unroll
+  for (int k = 0; k < DOT_ACC_WORDS; k++) {
+#pragma unroll
+    for (int i = 0; i < MUL_FIELD_WORDS; i++) {
+      if (k - i >= 0 && k - i < MUL_FIELD_WORDS) {
+        const uint64_t p = (uint64_t)a[i] * b[k - i];
+        col += p;
+        top += col < p ? 1u : 0u;
+      }
+    }
+    col += acc[k];
+    top += col < acc[k] ? 1u : 0u;
+    acc[k] = (uint32_t)col;
+    col = (col >> 32) | ((uint64_t)top << 32);
+    top = 0;
+  }
+}
+// the low `bits` bits of v appended to a little-endian bit stream: buf holds `fill` < 32 pending bits, whole words go to *out.  v has no
+// bit at or above `bits` (the draws' widths); the number of words written depends on the widths alone, never on the values
+__device__ __forceinline__ void dot_push(const uint32_t (&v)[MUL_FIELD_WORDS], int bits, uint64_t& buf, int& fill, uint32_t*& out) {
+#pragma unroll
+  for (int w = 0; w < MUL_FIELD_WORDS; w++) {
+    const int nb = bits - 32 * w;
+    if (nb > 0) {
+      buf |= (uint64_t)v[w] << fill;
+      fill += nb < 32 ? nb : 32;
+      if (fill >= 32) { *out++ = (uint32_t)buf; buf >>= 32; fill -= 32; }
+    }
+  }
+}
+// row[0 .. w) = acc, zero-extended (or cut: the fit rule keeps the sum below N, so the words past w are zero)
+__device__ __forceinline__ void dot_store_acc(const uint32_t (&acc)[DOT_ACC_WORDS], uint32_t* row, int w) {
+#pragma unroll
+  for (int k = 0; k < DOT_ACC_WORDS; k++) if (k < w) row[k] = acc[k];
+  for (int k = DOT_ACC_WORDS; k < w; k++) row[k] = 0u;
+}
+
+// The initiator's plaintext values of an inner product from her draws r_a [k][count][aw] (< 2^(wx + kappa)) and r_b [k][count][bw]
+// (< 2^(wy + kappa)), every field with a mask of its own.  With a_j = r_a_j + ox, b_j = r_b_j + oy (ox = 2^(wx - 1), oy = 2^(wy - 1)
+// for signed operands, else 0):
+//   e [2k][count][ew]: planes 0 .. k-1 the exponents of x_j (b_j), planes k .. 2k-1 the exponents of y_j (a_j);
+//   R [M][count][nw]: the packed masks of message m;  S [count][nw] = sum_j a_j b_j.
+// Square mode (r_b unused): e [k][count][ew] = 2 a_j, R packs the a_j alone, S = sum_j a_j^2.
+__global__ void k_dot_prep(const uint32_t* __restrict__ ra, int aw, const uint32_t* __restrict__ rb, int bw, DotLayout lay, int nw, int ew,
+                           uint64_t count, uint32_t* __restrict__ e, uint32_t* __restrict__ R, uint32_t* __restrict__ S) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint32_t a[MUL_FIELD_WORDS], b[MUL_FIELD_WORDS], acc[DOT_ACC_WORDS];
+#pragma unroll
+  for (int k = 0; k < DOT_ACC_WORDS; k++) acc[k] = 0u;
+  const int oa = lay.is_signed ? lay.wx - 1 : -1, ob = lay.is_signed ? lay.wy - 1 : -1;
+  for (int m = 0; m < lay.M; m++) {
+    uint32_t* const row = R + ((uint64_t)m * count + i) * nw;
+    uint32_t* out = row;
+    uint64_t buf = 0;
+    int fill = 0;
+    for (int j = m; j < lay.k; j += lay.M) {
+      const uint64_t item = (uint64_t)j * count + i;
+      dot_load_field(ra + item * aw, aw, oa, a);
+      dot_push(a, lay.sa, buf, fill, out);
+      if (lay.square) {
+        uint32_t* ej = e + item * ew;                  // 2 a_j < 2^(sa + 1) <= 2^(32 MUL_FIELD_WORDS)
+#pragma unroll
+        for (int k = 0; k < MUL_FIELD_WORDS; k++) if (k < ew) ej[k] = (a[k] << 1) | (k ? a[k - 1] >> 31 : 0u);
+        for (int k = MUL_FIELD_WORDS; k < ew; k++) ej[k] = 0u;
+        dot_mac(a, a, acc);
+      } else {
+        dot_load_field(rb + item * bw, bw, ob, b);
+        dot_push(b, lay.sb, buf, fill, out);
+        uint32_t* ex = e + item * ew;                  // the exponent of x_j is b_j
+        uint32_t* ey = e + ((uint64_t)(lay.k + j) * count + i) * ew;
+#pragma unroll
+        for (int k = 0; k < MUL_FIELD_WORDS; k++) if (k < ew) { ex[k] = b[k]; ey[k] = a[k]; }
+        for (int k = MUL_FIELD_WORDS; k < ew; k++) { ex[k] = 0u; ey[k] = 0u; }
+        dot_mac(a, b, acc);
+      }
+    }
+    if (fill) *out++ = (uint32_t)buf;
+    while (out < row + nw) *out++ = 0u;                // n_m pb <= g pb < bits(N) - 1 <= 32 nw: the fields end inside the row
+  }
+  dot_store_acc(acc, S + i * nw, nw);
+}
+
+// The key holder's half: from the decrypted P [M][count][nw], D [count][nw] = sum_j A_j B_j (square mode: sum_j A_j^2) over the fields of
+// the row's M messages.  A message with a bit at or above its own end n_m pb sets *bad (the players disagree on the layout); D is still
+// written.
+__global__ void k_dot_split(const uint32_t* __restrict__ p, int nw, DotLayout lay, uint64_t count, uint32_t* __restrict__ D,
+                            uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  uint32_t a[MUL_FIELD_WORDS], b[MUL_FIELD_WORDS], acc[DOT_ACC_WORDS];
+#pragma unroll
+  for (int k = 0; k < DOT_ACC_WORDS; k++) acc[k] = 0u;
+  uint32_t over = 0;
+  for (int m = 0; m < lay.M; m++) {
+    const uint32_t* x = p + ((uint64_t)m * count + i) * nw;
+    const int n_m = (lay.k - m + lay.M - 1) / lay.M, end = n_m * lay.pb;      // the partial last position: end differs between messages
+    for (int k = end >> 5; k < nw; k++) over |= (k == (end >> 5)) ? (x[k] >> (end & 31)) : x[k];
+    for (int t = 0; t < n_m; t++) {
+#pragma unroll
+      for (int k = 0; k < MUL_FIELD_WORDS; k++) a[k] = sel_field_word(x, nw, t * lay.pb, lay.sa, k);
+      if (lay.square) {
+        dot_mac(a, a, acc);
+      } else {
+#pragma unroll
+        for (int k = 0; k < MUL_FIELD_WORDS; k++) b[k] = sel_field_word(x, nw, t * lay.pb + lay.sa, lay.sb, k);
+        dot_mac(a, b, acc);
+      }
+    }
+  }
+  if (over) *bad = 1u;
+  dot_store_acc(acc, D + i * nw, nw);
+}
+#endif  // SC_DOT_UNIT
 
 }  // namespace sc

@@ -1995,6 +1995,69 @@ int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx,
   return SC_OK;
 }
 
+// ---- secure inner product: the plaintext-word halves of the two players (k_dot_prep / k_dot_split) -----------------
+// DotLayout.__post_init__ (dotproduct.py) on the host -- the one copy of the fit rule every inner-product entry checks before it launches
+// anything: g = the largest integer with g pb < bits(N) - 1 must be at least 1, and the sum of k products must stay below N:
+// pb' + ceil(log2 k) < bits(N) - 1 with pb' = sa + sb (2 sa for a square).  Every refusal names its quantity.
+static int dot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, DotLayout* lay) {
+  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
+  if (wx < 1 || wx > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: wx = %d: expected 1 .. %d", who, wx, MUL_MAX_WIDTH);
+  if (!square && (wy < 1 || wy > MUL_MAX_WIDTH)) return fail(ctx, SC_ERR_ARG, "%s: wy = %d: expected 1 .. %d", who, wy, MUL_MAX_WIDTH);
+  if (k < 1 || k > DOT_MAX_K) return fail(ctx, SC_ERR_ARG, "%s: k = %d: expected 1 .. %d pairs per row", who, k, DOT_MAX_K);
+  lay->wx = wx; lay->wy = square ? 0 : wy; lay->is_signed = is_signed ? 1 : 0; lay->square = square ? 1 : 0; lay->k = k;
+  lay->sa = wx + kappa + 1; lay->sb = square ? 0 : wy + kappa + 1; lay->pb = lay->sa + lay->sb;
+  lay->ebits = square ? lay->sa + 1 : std::max(lay->sa, lay->sb);
+  lay->g = nbits_n >= 2 ? (nbits_n - 2) / lay->pb : 0;
+  if (lay->g < 1) return fail(ctx, SC_ERR_ARG, "%s: pb = %d: one pair does not fit below a %d-bit N (kappa = %d)", who, lay->pb, nbits_n, kappa);
+  const int prod = square ? 2 * lay->sa : lay->pb;
+  int lg = 0;
+  while ((1 << lg) < k) lg++;
+  if (prod + lg >= nbits_n - 1)
+    return fail(ctx, SC_ERR_ARG, "%s: the sum of k = %d products (%d + %d bits) does not fit below a %d-bit N", who, k, prod, lg, nbits_n);
+  lay->M = (k + lay->g - 1) / lay->g;
+  return SC_OK;
+}
+// the draws' and exponents' row widths: the kernels hold a field in MUL_FIELD_WORDS words
+static int dot_row_words(sc_ctx* ctx, const char* who, const DotLayout& lay, int aw, int bw, int ew) {
+  if (aw < 1 || aw > MUL_FIELD_WORDS || (!lay.square && (bw < 1 || bw > MUL_FIELD_WORDS)) || ew < 1)
+    return fail(ctx, SC_ERR_ARG, "%s: rows of %d (r_a), %d (r_b), %d (e) words: expected 1 .. %d for the draws", who, aw, bw, ew, MUL_FIELD_WORDS);
+  if (32 * ew < lay.ebits) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, lay.ebits);
+  return SC_OK;
+}
+
+int sc_dot_layout(int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, int* out) {
+  DotLayout lay;
+  if (!out) return SC_ERR_ARG;
+  int rc = dot_layout(nullptr, "sc_dot_layout", nbits_n, kappa, wx, wy, is_signed, square, k, &lay); if (rc) return rc;
+  out[0] = lay.sa; out[1] = lay.sb; out[2] = lay.pb; out[3] = lay.g; out[4] = lay.M; out[5] = lay.ebits;
+  return SC_OK;
+}
+
+int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int is_signed, int square, int k, const uint32_t* r_a,
+                int aw, const uint32_t* r_b, int bw, int ew, uint32_t* e, uint32_t* R, uint32_t* S, uint64_t count) {
+  if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_dot_prep: bad argument");
+  DotLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = dot_layout(ctx, "sc_dot_prep", big_bits(n), kappa, wx, wy, is_signed, square, k, &lay); if (rc) return rc;
+  if (!r_a || (!square && !r_b) || !e || !R || !S) return fail(ctx, SC_ERR_ARG, "sc_dot_prep: bad argument");
+  rc = dot_row_words(ctx, "sc_dot_prep", lay, aw, bw, ew); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  if (launch_dot_prep(ctx->stream, r_a, aw, r_b, bw, lay, nw, ew, count, e, R, S)) return fail(ctx, SC_ERR_HIP, "sc_dot_prep: launch failed");
+  return SC_OK;
+}
+
+int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int square, int k, const uint32_t* p, uint32_t* D,
+                 uint32_t* bad, uint64_t count) {
+  if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_dot_split: bad argument");
+  DotLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = dot_layout(ctx, "sc_dot_split", big_bits(n), kappa, wx, wy, 0, square, k, &lay); if (rc) return rc;
+  if (!p || !D || !bad) return fail(ctx, SC_ERR_ARG, "sc_dot_split: bad argument");
+  if (count == 0) return SC_OK;
+  if (launch_dot_split(ctx->stream, p, nw, lay, count, D, bad)) return fail(ctx, SC_ERR_HIP, "sc_dot_split: launch failed");
+  return SC_OK;
+}
+
 // ---- compare-exchange finish of a secure sort: both outputs of every column from one shared inversion ----------
 // The nf columns run as flat items (nf * count of them), so the program does not depend on nf and an index row entry is read at the
 // item's flat number.  Per item, with V = U^-1 R^3 (one product, shared by both outputs): hi = F ab ab V / R^3 = F ab^2 U^-1 and

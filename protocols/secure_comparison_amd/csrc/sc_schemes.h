@@ -1101,6 +1101,172 @@ int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   return run_vm(ctx, k.mod_n2, *p, ex, 4, items);
 }
 
+// ---- secure inner product ----------------------------------------------------------------------------------------------
+// The multiplication's round trip with k pairs per row: the key holder adds the products under the blinding and returns one ciphertext,
+// [[sum_j x_j y_j]] = [[D]] T^-1 with D = sum_j A_j B_j and T = prod_j [[x_j]]^(b_j) [[y_j]]^(a_j) (1 + S N), S = sum_j a_j b_j.  A row's
+// pairs are packed g to a message, pair j in message j mod M at position j div M, so the planes of one position are contiguous in
+// x_enc [k][count][2 nw] and the messages that hold the (partial) top position are a prefix of P [M][count][2 nw].  Same temporaries as
+// the selection's.
+static int dot_key_layout(sc_ctx* ctx, const char* who, const PaillierKey& k, int kappa, int wx, int wy, int is_signed, int square, int kk, DotLayout* lay) {
+  return dot_layout(ctx, who, big_bits(k.n), kappa, wx, wy, is_signed, square, kk, lay);
+}
+
+int sc_initiator_dot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int is_signed, int square, int kk, const uint32_t* x_enc,
+                          const uint32_t* y_enc, const uint32_t* r_a, int aw, const uint32_t* r_b, int bw, const uint32_t* rho_p, int ew,
+                          uint32_t* p_out, uint32_t* e_out, uint32_t* s_out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: bad key");
+  const PaillierKey k = *kp;
+  DotLayout lay;
+  int rc = dot_key_layout(ctx, "sc_initiator_dot_pack", k, kappa, wx, wy, is_signed, square, kk, &lay); if (rc) return rc;
+  if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: rho_p is required: every P must carry a fresh rho^N");
+  if (!x_enc || !r_a || (!square && (!y_enc || !r_b)) || !p_out || !e_out || !s_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: bad argument");
+  rc = dot_row_words(ctx, "sc_initiator_dot_pack", lay, aw, bw, ew); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw, M = lay.M;
+  const size_t col = (size_t)count * w2;               // one plane
+  const uint64_t items = (uint64_t)M * count;          // the messages
+  uint32_t *R, *m, *acc;
+  rc = tmp_words(ctx, TMP_SEL_A, items * k.nw, &R); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, items * w2, &m); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, 2 * items * w2, &acc); if (rc) return rc;
+  if (launch_dot_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, e_out, R, s_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_dot_pack: launch failed");
+  // the fields from the low end: x and y of position 0, x and y of position 1, ..; field f of position t = f / fp is held by the messages
+  // m < n(f), all M of them below the top position.  Field 0 -- the planes x_0 .. x_(M-1) -- is folded into [[x + R]] rho_p^N.
+  const int fp = square ? 1 : 2, npos = (kk + M - 1) / M, F = fp * npos;
+  const int n_top = kk - (npos - 1) * M;
+  auto base = [&](int f) { return ((f % fp) ? y_enc : x_enc) + (size_t)(f / fp) * M * col; };
+  auto fbits = [&](int f) { return (f % fp) ? lay.sb : lay.sa; };
+  auto held = [&](int f) { return (uint64_t)(f / fp == npos - 1 ? n_top : M); };
+  uint32_t* m_dst = F == 1 ? p_out : m;
+  const Prog* p;
+  rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {     // the selection's program
+    const int cn = bd.use_const(k.cst_n);
+    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
+    bd.mul_const(0); bd.mul_extw(0);                                      // [[x + R]]
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(x_enc, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(m_dst, w2, w2)};
+  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, items); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, paillier_key_id, m_dst, rho_p, m_dst, items); if (rc) return rc;      // * rho_p_m^N
+  // Horner from the top field with shared-exponent squarings: cur^(2^bits(f - 1)) times field f - 1; the messages that join below the
+  // partial top position start as a copy of their own field
+  const uint32_t* cur = base(F - 1);
+  uint64_t ncur = held(F - 1);
+  for (int f = F - 1; f >= 1; f--) {
+    uint32_t* dst = f == 1 ? p_out : acc + (size_t)(f & 1) * items * w2;
+    const uint32_t* low = f == 1 ? m : base(f - 1);
+    rc = sel_pow2(ctx, k, fbits(f - 1), cur, low, dst, ncur * count); if (rc) return rc;
+    const uint64_t nlow = held(f - 1);
+    if (nlow > ncur)
+      HIPCHK(ctx, hipMemcpyAsync(dst + ncur * col, low + ncur * col, (nlow - ncur) * col * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    cur = dst; ncur = nlow;
+  }
+  return SC_OK;
+}
+
+int sc_keyholder_dot(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int square, int kk, const uint32_t* p_enc, const uint32_t* rho_d,
+                     uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_dot: needs the secret key");
+  const PaillierKey k = *kp;
+  DotLayout lay;
+  int rc = dot_key_layout(ctx, "sc_keyholder_dot", k, kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
+  if (!p_enc || !rho_d || !out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_dot: bad argument");
+  if (count == 0) return SC_OK;
+  const uint64_t items = (uint64_t)lay.M * count;
+  uint32_t *pl, *D, *c;
+  rc = tmp_words(ctx, TMP_SEL_A, items * k.nw, &pl); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, (uint64_t)count * k.nw, &D); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, (uint64_t)count * 2 * k.nw, &c); if (rc) return rc;
+  uint32_t* bad;                              // the pinned verdict word of sc_keyholder_select_mult
+  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
+  *(volatile uint32_t*)bad = 0;
+  rc = sc_paillier_decrypt(ctx, paillier_key_id, p_enc, pl, items); if (rc) return rc;
+  if (launch_dot_split(ctx->stream, pl, k.nw, lay, count, D, bad)) return fail(ctx, SC_ERR_HIP, "sc_keyholder_dot: launch failed");
+  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, D, k.nw, c, count); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, paillier_key_id, c, rho_d, out, count); if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (*(volatile uint32_t*)bad)
+    return fail(ctx, SC_ERR_LAYOUT, "dot: a decrypted P exceeds the end of its message in the announced layout (kappa, widths, k or the mode differ between the players)");
+  return SC_OK;
+}
+
+// acc_out = acc_in * prod_j base_j^(e_j) over `planes` consecutive planes base [planes][count][2 nw], e [planes][count][ew]: groups of at
+// most three planes per pair launch, alternating between the two halves of `pp` [2][count][2 nw]; *acc follows the running product.
+// SC_ERR_UNSUPPORTED from the first group means that the key has no pair kernel with per-row exponents.
+static int dot_t_side(sc_ctx* ctx, const PaillierKey& k, int planes, int ebits, const uint32_t* base, const uint32_t* e, int ew, uint32_t* pp,
+                      const uint32_t** acc, uint64_t count) {
+  const int w2 = 2 * k.nw;
+  for (int j = 0; j < planes; j += 3) {
+    uint32_t* dst = *acc == pp ? pp + (size_t)count * w2 : pp;
+    int rc = sc_modexp_var_sq(ctx, k.mod_n, k.mod_n2, std::min(3, planes - j), base + (size_t)j * count * w2, w2, e + (size_t)j * count * ew, ew, ebits,
+                              *acc, dst, count); if (rc) return rc;
+    *acc = dst;
+  }
+  return SC_OK;
+}
+// the same product where the modulus has no such kernel: one exponentiation modulo N^2 and one product per plane (what two_base_t does)
+static int dot_t_side_plain(sc_ctx* ctx, const PaillierKey& k, int planes, int ebits, const uint32_t* base, const uint32_t* e, int ew, uint32_t* tmp,
+                            uint32_t* acc, uint64_t count) {
+  const int w2 = 2 * k.nw;
+  for (int j = 0; j < planes; j++) {
+    int rc = sc_modexp_var(ctx, k.mod_n2, base + (size_t)j * count * w2, e + (size_t)j * count * ew, ew, ebits, -1, nullptr, 0, tmp, count); if (rc) return rc;
+    rc = sc_modmul(ctx, k.mod_n2, acc, w2, tmp, w2, acc, count); if (rc) return rc;
+  }
+  return SC_OK;
+}
+
+int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int square, int kk, const uint32_t* x_enc,
+                            const uint32_t* y_enc, const uint32_t* d_enc, const uint32_t* e, int ew, const uint32_t* s, const uint32_t* base,
+                            int coef, uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: bad key");
+  const PaillierKey k = *kp;
+  DotLayout lay;
+  int rc = dot_key_layout(ctx, "sc_initiator_dot_finish", k, kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
+  if (!x_enc || (!square && !y_enc) || !d_enc || !e || !s || !out || ew < 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: bad argument");
+  if (coef != 1 && coef != -1 && coef != -2) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: coef = %d: expected +1, -1 or -2", coef);
+  if (32 * ew < lay.ebits) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: exponent rows of %d words are too narrow for %d bits", ew, lay.ebits);
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw;
+  const size_t col = (size_t)count * w2;
+  uint32_t *mi, *pp, *inv, *tmp;
+  rc = tmp_words(ctx, TMP_SEL_A, col, &mi); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_D, 2 * col, &pp); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_E, col, &inv); if (rc) return rc;
+  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, s, k.nw, mi, count); if (rc) return rc;        // 1 + S N
+  // T: the exponents' planes follow the bases' (e: the k planes of x, then the k planes of y)
+  const uint32_t* T = mi;
+  rc = k.pairs ? dot_t_side(ctx, k, kk, lay.ebits, x_enc, e, ew, pp, &T, count) : SC_ERR_UNSUPPORTED;
+  if (rc == SC_OK && !square) rc = dot_t_side(ctx, k, kk, lay.ebits, y_enc, e + (size_t)kk * count * ew, ew, pp, &T, count);
+  if (rc == SC_ERR_UNSUPPORTED) {
+    rc = tmp_words(ctx, TMP_SEL_B, col, &tmp); if (rc) return rc;
+    rc = dot_t_side_plain(ctx, k, kk, lay.ebits, x_enc, e, ew, tmp, mi, count);
+    if (rc == SC_OK && !square) rc = dot_t_side_plain(ctx, k, kk, lay.ebits, y_enc, e + (size_t)kk * count * ew, ew, tmp, mi, count);
+    T = mi;
+  }
+  if (rc) return rc;
+  // [[sum]]^coef = ([[D]] T^-1)^coef: sc_initiator_mul_finish's rule -- coef = +1 inverts T, a negative coef inverts [[D]]; one pass
+  // over `count` items either way, so SC_ERR_NOT_INVERTIBLE names the row
+  const uint32_t* num = coef == 1 ? d_enc : T;
+  rc = sc_modinv(ctx, k.mod_n2, coef == 1 ? T : d_enc, inv, count, nullptr); if (rc) return rc;
+  const int pairs = coef == -2 ? 2 : 1, nmul = 2 * pairs - 1 + (base ? 1 : 0);
+  const Mod& m2 = ctx->mods[k.mod_n2];
+  int cid;
+  { Big one(m2.nwords, 0); one[0] = 1; rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one, m2.n, nmul * m2.W * m2.S), &cid); if (rc) return rc; }   // R^nmul mod N^2
+  const Prog* p;
+  rc = cached_prog(ctx, "dotfin:" + std::to_string(k.mod_n2) + ":" + std::to_string(pairs) + (base ? ":b" : ""), k.mod_n2, [&](Builder& bd) {
+    bd.loadw(0); bd.mul_const(bd.use_const(cid));                         // num R^nmul
+    bd.mul_extw(1);                                                       // num inv
+    if (pairs == 2) { bd.mul_extw(0); bd.mul_extw(1); }                   // (num inv)^2
+    if (base) bd.mul_extw(2);
+    bd.storew(3);
+  }, &p); if (rc) return rc;
+  VmExt ex[4] = {mk_ext(num, w2, w2), mk_ext(inv, w2, w2), mk_ext(base, w2, w2), mk_ext(out, w2, w2)};
+  return run_vm(ctx, k.mod_n2, *p, ex, 4, count);
+}
+
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {
   const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
   if (!kp || !rho || count == 0 || !out_ghz) return fail(ctx, SC_ERR_ARG, "sc_clock_probe: bad argument");

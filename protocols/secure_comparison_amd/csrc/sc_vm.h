@@ -94,6 +94,16 @@ struct MulLayout {
   int off[SEL_MAX_FIELDS], fbits[SEL_MAX_FIELDS], wy[SEL_MAX_FIELDS];
 };
 
+// Layout of a secure inner product's packed plaintexts (k_dot_prep / k_dot_split, sc_kernel_plain.h): k pairs (A_j, B_j)
+// of sa + sb = pb bits, g of them per message, M = ceil(k / g) messages per row, pair j in message j mod M at position j div M.  The
+// widths are uniform, so the struct holds scalars only.  square: every pair is the one field A_j (sb = 0, pb = sa).
+constexpr int DOT_MAX_K = 1024;
+constexpr int DOT_ACC_WORDS = 2 * MUL_FIELD_WORDS + 1;   // sum of 1024 products of two 318-bit fields: 646 bits
+struct DotLayout {
+  int sa, sb, pb, g, M, k, ebits;  // ebits: bits of the exponents of T (max(sa, sb); sa + 1 for the 2 a_j of a square)
+  int wx, wy, is_signed, square;
+};
+
 constexpr int VM_MAX_EXT = 8;
 constexpr int VM_MAX_CONST = 8;  // including R^2 and R
 

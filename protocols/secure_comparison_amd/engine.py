@@ -91,6 +91,14 @@ def _default_hw_queues() -> None:
     os.environ["GPU_MAX_HW_QUEUES"] = "32"
 
 
+def dot_layout(lib, nbits: int, kappa: int, wx: int, wy: int, signed: bool, square: bool, k: int) -> tuple:
+    """(sa, sb, pb, g, M, ebits) from sc_dot_layout -- host code only, so it needs no context and no GPU.  ValueError on a refusal."""
+    out = (C.c_int * 6)()
+    if lib.sc_dot_layout(int(nbits), int(kappa), int(wx), int(wy), int(bool(signed)), int(bool(square)), int(k), out) != 0:
+        raise ValueError(f"sc_dot_layout refuses (nbits, kappa, wx, wy, signed, square, k) = {(nbits, kappa, wx, wy, signed, square, k)}")
+    return tuple(out)
+
+
 class Engine:
     """One library context (sc_ctx): one per process and device, or one per concurrent shard / session thread of a device.
     Tensors are int32 views of uint32 words, shape [count, nwords].  An engine belongs to ONE host thread at a time: it orders its
@@ -1076,6 +1084,74 @@ class Engine:
         self._check(self.lib.sc_initiator_mul_finish(self.ctx, key.id, int(kappa), int(wx), nf, pw, self._ptr(x_enc), self._ptr(y_enc),
                                                      self._ptr(products), self._ptr(e), e.shape[-1], self._ptr(rab), self._ptr(base),
                                                      int(coef), self._ptr(out), count))
+        return out
+
+    # ------------------------------------------------------------------ secure inner product (one library call each)
+    def dot_layout(self, nbits: int, kappa: int, wx: int, wy: int, signed: bool, square: bool, k: int) -> tuple:
+        """(sa, sb, pb, g, M, ebits) from the library's copy of the fit rule (sc_dot_layout: host only); ValueError on a refusal."""
+        return dot_layout(self.lib, nbits, kappa, wx, wy, signed, square, k)
+
+    def _dot_planes(self, key, k, square, x_enc, y_enc):
+        nw = key.mod_n.nwords
+        if not isinstance(x_enc, torch.Tensor) or x_enc.dim() != 3 or x_enc.shape[0] != k:
+            raise ValueError(f"x_enc: expected [{k}][count][words]")
+        count = x_enc.shape[1]
+        self._columns(x_enc, "x_enc", k, count, 2 * nw)
+        if not square:
+            self._columns(y_enc, "y_enc", k, count, 2 * nw)
+        return nw, count
+
+    def initiator_dot_pack(self, key: PaillierKey, kappa: int, wx: int, wy: int, signed: bool, square: bool, k: int, M: int,
+                           x_enc: torch.Tensor, y_enc: torch.Tensor | None, r_a: torch.Tensor, r_b: torch.Tensor | None,
+                           rho_p: torch.Tensor | None, ew: int):
+        """The messages P [M][count][2nw] and the finish's plaintext arrays (e [2k][count][ew], or [k][count][ew] for a square;
+        S [count][nw]) (sc_initiator_dot_pack).  A missing rho_p is the library's ValueError."""
+        nw, count = self._dot_planes(key, k, square, x_enc, y_enc)
+        self._columns(r_a, "r_a", k, count, None)
+        if not square:
+            self._columns(r_b, "r_b", k, count, None)
+        if rho_p is not None:
+            self._columns(rho_p, "rho_p", M, count, nw)
+        P = torch.empty((M, count, 2 * nw), dtype=torch.int32, device=self.device)
+        e = torch.empty((k if square else 2 * k, count, int(ew)), dtype=torch.int32, device=self.device)
+        S = self.empty(count, nw)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_dot_pack(self.ctx, key.id, int(kappa), int(wx), int(wy), int(bool(signed)), int(bool(square)), int(k),
+                                                   self._ptr(x_enc), self._ptr(None if square else y_enc), self._ptr(r_a), r_a.shape[-1],
+                                                   self._ptr(None if square else r_b), 0 if square else r_b.shape[-1], self._ptr(rho_p),
+                                                   int(ew), self._ptr(P), self._ptr(e), self._ptr(S), count))
+        return P, e, S
+
+    def keyholder_dot(self, key: PaillierKey, kappa: int, wx: int, wy: int, square: bool, k: int, M: int, P: torch.Tensor,
+                      rho_d: torch.Tensor) -> torch.Tensor:
+        """The key holder's randomized [[D]] [count][2nw] from P [M][count][2nw] (sc_keyholder_dot); ValueError when a decrypted
+        message exceeds its end in the layout."""
+        nw = key.mod_n.nwords
+        if not isinstance(P, torch.Tensor) or P.dim() != 3 or P.shape[0] != M:
+            raise ValueError(f"P: expected [{M}][count][words]")
+        count = P.shape[1]
+        self._columns(P, "P", M, count, 2 * nw)
+        self._arr(rho_d, "rho_d", count, nw)
+        out = self.empty(count, 2 * nw)
+        self._sync_stream()
+        self._check(self.lib.sc_keyholder_dot(self.ctx, key.id, int(kappa), int(wx), int(wy), int(bool(square)), int(k), self._ptr(P),
+                                              self._ptr(rho_d), self._ptr(out), count))
+        return out
+
+    def initiator_dot_finish(self, key: PaillierKey, kappa: int, wx: int, wy: int, square: bool, k: int, x_enc: torch.Tensor,
+                             y_enc: torch.Tensor | None, d_enc: torch.Tensor, e: torch.Tensor, S: torch.Tensor,
+                             base: torch.Tensor | None = None, coef: int = 1) -> torch.Tensor:
+        """base [[sum_j x_j y_j]]^coef [count][2nw] from the key holder's [[D]] (sc_initiator_dot_finish); coef in {+1, -1, -2}."""
+        nw, count = self._dot_planes(key, k, square, x_enc, y_enc)
+        self._arr(d_enc, "d_enc", count, 2 * nw)
+        self._columns(e, "e", k if square else 2 * k, count, None)
+        self._arr(S, "S", count, nw)
+        self._arr(base, "base", count, 2 * nw, optional=True)
+        out = self.empty(count, 2 * nw)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_dot_finish(self.ctx, key.id, int(kappa), int(wx), int(wy), int(bool(square)), int(k), self._ptr(x_enc),
+                                                     self._ptr(None if square else y_enc), self._ptr(d_enc), self._ptr(e), e.shape[-1],
+                                                     self._ptr(S), self._ptr(base), int(coef), self._ptr(out), count))
         return out
 
     # ------------------------------------------------------------------ device-side CSPRNG (sc_rng_*)

@@ -463,6 +463,17 @@ class Initiator:
 
         return await alice_equal(self, x_enc, y_enc, draws, mul_draws, kappa, source, engine, generator, chunks)
 
+    # ---- secure inner product (dotproduct.py)
+    async def perform_secure_dot_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor | None, x_bits: int, y_bits: int = 0,
+                                       signed: bool = False, square: bool = False, kappa: int = 40, draws=None, source: str = "device",
+                                       engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[sum_j x_j y_j]] [B][2nw] from x_enc, y_enc [k][B][2nw] as dotproduct.secure_dot_batch (square: [[sum_j x_j^2]], y_enc
+        ignored): `dot_1_batch_{tag}` carries an int32 header (kappa, x_bits, y_bits, signed, square, k) and the messages P
+        [M][B][2nw], `dot_2_batch_{tag}` the key holder's one [[D]] per row.  chunks > 1 is not supported (ValueError)."""
+        from .dotproduct import alice_dot
+
+        return await alice_dot(self, x_enc, y_enc, x_bits, y_bits, signed, square, kappa, draws, source, engine, generator, chunks)
+
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""
         if self.communicator is None:

@@ -334,6 +334,17 @@ class KeyHolder:
 
         await bob_equal(self, draws, mul_draws, kappa, source, generator)
 
+    # ---- secure inner product (dotproduct.py)
+    async def perform_secure_dot_batch(self, k: int, x_bits: int, y_bits: int = 0, signed: bool = False, square: bool = False,
+                                       kappa: int = 40, draws=None, source: str = "device", generator=None,
+                                       count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_dot_batch for k pairs per row: the initiator's header must announce this kappa,
+        these widths, this signedness, mode and k (ValueError before anything is decrypted); `count` (optional) is the batch size
+        he expects."""
+        from .dotproduct import bob_dot
+
+        await bob_dot(self, k, x_bits, y_bits, signed, square, kappa, draws, source, generator, count)
+
     async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
         message when it has been received already.  Returns the session's batch size."""
