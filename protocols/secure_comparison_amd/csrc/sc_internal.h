@@ -1,7 +1,7 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
 // (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel) and
-// sc_launch_misc.hip; sc_lib.hip (+ sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// sc_launch_misc.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>

@@ -3,6 +3,7 @@
 // the sc_launch_*.hip translation units (sc_internal.h), so this file holds no device code.
 #include "sc_internal.h"
 
+#include <functional>
 #include <type_traits>
 
 using namespace sc;
@@ -1893,206 +1894,7 @@ int sc_modexp_var_sq(sc_ctx* ctx, int mod_m, int mod_m2, int nbases, const uint3
   return pair_assemble(ctx, mod_m, mod_m2, d_w, d_w1, wm, mul_into, out, count);
 }
 
-// ---- secure selection: the plaintext-word halves of the two players (k_select_prep / k_select_split) -------------------------------
-// SelectLayout.__post_init__ (selection.py) on the host -- the one copy of the rule every selection entry checks before it launches
-// anything (sc_select_prep / sc_select_split here, the scheme-level entries of sc_schemes.h); every refusal names its column
-static int select_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int nfields, const int* widths, SelLayout* lay) {
-  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
-  if (!widths || nfields < 1 || nfields > SEL_MAX_FIELDS)
-    return fail(ctx, SC_ERR_ARG, "%s: %d columns: expected 1 .. %d with their widths", who, nfields, SEL_MAX_FIELDS);
-  lay->s = kappa + 1; lay->nf = nfields;
-  int off = lay->s;
-  for (int j = 0; j < nfields; j++) {
-    if (widths[j] < 1 || widths[j] > 4096) return fail(ctx, SC_ERR_ARG, "%s: column %d: width %d: expected 1 .. 4096", who, j, widths[j]);
-    lay->width[j] = widths[j]; lay->fbits[j] = widths[j] + kappa + 2; lay->off[j] = off;
-    if (lay->s + lay->fbits[j] >= nbits_n - 1)
-      return fail(ctx, SC_ERR_ARG, "%s: column %d: the product a * b (%d bits) does not fit below a %d-bit N", who, j, lay->s + lay->fbits[j], nbits_n);
-    off += lay->fbits[j];
-    if (off >= nbits_n - 1)
-      return fail(ctx, SC_ERR_ARG, "%s: column %d: the packed fields (%d bits) do not fit below a %d-bit N (kappa = %d)", who, j, off, nbits_n, kappa);
-  }
-  lay->end = off;
-  return SC_OK;
-}
-
-int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* r_a,
-                   int aw, const uint32_t* r_b, int bw, int ew, uint32_t* R, uint32_t* e, uint32_t* rab, uint64_t count) {
-  if (ctx && count == 0) return SC_OK;
-  if (!ctx || !n_hptr || nw <= 0 || !r_a || !r_b || !R || !e || !rab || aw < 1 || aw > 2 || bw < 1 || ew < 1)
-    return fail(ctx, SC_ERR_ARG, "sc_select_prep: bad argument");
-  SelLayout lay;
-  Big n(n_hptr, n_hptr + nw);
-  int rc = select_layout(ctx, "sc_select_prep", big_bits(n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
-  if (bw > nw) return fail(ctx, SC_ERR_ARG, "sc_select_prep: r_b rows of %d words are wider than N (%d words)", bw, nw);
-  for (int j = 0; j < nfields; j++)
-    if (32 * ew < lay.fbits[j]) return fail(ctx, SC_ERR_ARG, "sc_select_prep: exponent rows of %d words are too narrow", ew);
-  if (launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, nw, ew, count, R, e, rab)) return fail(ctx, SC_ERR_HIP, "sc_select_prep: launch failed");
-  return SC_OK;
-}
-
-int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* p,
-                    uint32_t* prod, uint32_t* bad, uint64_t count) {
-  if (ctx && count == 0) return SC_OK;
-  if (!ctx || !n_hptr || nw <= 0 || !p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_select_split: bad argument");
-  SelLayout lay;
-  Big n(n_hptr, n_hptr + nw);
-  int rc = select_layout(ctx, "sc_select_split", big_bits(n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
-  if (launch_select_split(ctx->stream, p, nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_select_split: launch failed");
-  return SC_OK;
-}
-
-// ---- secure multiplication: the plaintext-word halves of the two players (k_mul_prep / k_mul_split) ---------------
-// MulLayout.__post_init__ (multiplication.py) on the host -- the one copy of the fit rule every multiplication entry checks before it
-// launches anything: s + sum_j fbits_j < bits(N) - 1 and every s + fbits_j < bits(N) - 1; every refusal names its column
-static int mul_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int nfields, const int* wy, int is_signed, MulLayout* lay) {
-  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
-  if (wx < 1 || wx > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: wx = %d: expected 1 .. %d", who, wx, MUL_MAX_WIDTH);
-  if (!wy || nfields < 1 || nfields > SEL_MAX_FIELDS)
-    return fail(ctx, SC_ERR_ARG, "%s: %d columns: expected 1 .. %d with their widths", who, nfields, SEL_MAX_FIELDS);
-  lay->s = wx + kappa + 1; lay->nf = nfields; lay->wx = wx; lay->is_signed = is_signed ? 1 : 0;
-  int off = lay->s;
-  for (int j = 0; j < nfields; j++) {
-    if (wy[j] < 1 || wy[j] > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: column %d: width %d: expected 1 .. %d", who, j, wy[j], MUL_MAX_WIDTH);
-    lay->wy[j] = wy[j]; lay->fbits[j] = wy[j] + kappa + 1; lay->off[j] = off;
-    if (lay->s + lay->fbits[j] >= nbits_n - 1)
-      return fail(ctx, SC_ERR_ARG, "%s: column %d: the product A * B (%d bits) does not fit below a %d-bit N", who, j, lay->s + lay->fbits[j], nbits_n);
-    off += lay->fbits[j];
-    if (off >= nbits_n - 1)
-      return fail(ctx, SC_ERR_ARG, "%s: column %d: the packed fields (%d bits) do not fit below a %d-bit N (kappa = %d)", who, j, off, nbits_n, kappa);
-  }
-  lay->end = off;
-  return SC_OK;
-}
-static int mul_ebits(const MulLayout& lay) { int b = lay.s; for (int j = 0; j < lay.nf; j++) b = std::max(b, lay.fbits[j]); return b; }
-// the draws' and exponents' row widths: the kernels hold a field in MUL_FIELD_WORDS words
-static int mul_row_words(sc_ctx* ctx, const char* who, const MulLayout& lay, int aw, int bw, int ew, int nw) {
-  if (aw < 1 || aw > MUL_FIELD_WORDS || bw < 1 || bw > MUL_FIELD_WORDS || bw > nw || ew < 1)
-    return fail(ctx, SC_ERR_ARG, "%s: rows of %d (r_a), %d (r_b), %d (e) words: expected 1 .. %d for the draws", who, aw, bw, ew, MUL_FIELD_WORDS);
-  if (32 * ew < mul_ebits(lay)) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, mul_ebits(lay));
-  return SC_OK;
-}
-
-int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
-                const uint32_t* r_a, int aw, const uint32_t* r_b, int bw, int ew, uint32_t* R, uint32_t* e, uint32_t* rab, uint64_t count) {
-  if (ctx && count == 0) return SC_OK;
-  if (!ctx || !n_hptr || nw <= 0 || !r_a || !r_b || !R || !e || !rab) return fail(ctx, SC_ERR_ARG, "sc_mul_prep: bad argument");
-  MulLayout lay;
-  Big n(n_hptr, n_hptr + nw);
-  int rc = mul_layout(ctx, "sc_mul_prep", big_bits(n), kappa, wx, nfields, wy_hptr, is_signed, &lay); if (rc) return rc;
-  rc = mul_row_words(ctx, "sc_mul_prep", lay, aw, bw, ew, nw); if (rc) return rc;
-  if (launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, nw, ew, count, R, e, rab)) return fail(ctx, SC_ERR_HIP, "sc_mul_prep: launch failed");
-  return SC_OK;
-}
-
-int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p,
-                 uint32_t* prod, uint32_t* bad, uint64_t count) {
-  if (ctx && count == 0) return SC_OK;
-  if (!ctx || !n_hptr || nw <= 0 || !p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_mul_split: bad argument");
-  MulLayout lay;
-  Big n(n_hptr, n_hptr + nw);
-  int rc = mul_layout(ctx, "sc_mul_split", big_bits(n), kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
-  if (launch_mul_split(ctx->stream, p, nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_mul_split: launch failed");
-  return SC_OK;
-}
-
-// ---- secure inner product: the plaintext-word halves of the two players (k_dot_prep / k_dot_split) -----------------
-// DotLayout.__post_init__ (dotproduct.py) on the host -- the one copy of the fit rule every inner-product entry checks before it launches
-// anything: g = the largest integer with g pb < bits(N) - 1 must be at least 1, and the sum of k products must stay below N:
-// pb' + ceil(log2 k) < bits(N) - 1 with pb' = sa + sb (2 sa for a square).  Every refusal names its quantity.
-static int dot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, DotLayout* lay) {
-  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
-  if (wx < 1 || wx > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: wx = %d: expected 1 .. %d", who, wx, MUL_MAX_WIDTH);
-  if (!square && (wy < 1 || wy > MUL_MAX_WIDTH)) return fail(ctx, SC_ERR_ARG, "%s: wy = %d: expected 1 .. %d", who, wy, MUL_MAX_WIDTH);
-  if (k < 1 || k > DOT_MAX_K) return fail(ctx, SC_ERR_ARG, "%s: k = %d: expected 1 .. %d pairs per row", who, k, DOT_MAX_K);
-  lay->wx = wx; lay->wy = square ? 0 : wy; lay->is_signed = is_signed ? 1 : 0; lay->square = square ? 1 : 0; lay->k = k;
-  lay->sa = wx + kappa + 1; lay->sb = square ? 0 : wy + kappa + 1; lay->pb = lay->sa + lay->sb;
-  lay->ebits = square ? lay->sa + 1 : std::max(lay->sa, lay->sb);
-  lay->g = nbits_n >= 2 ? (nbits_n - 2) / lay->pb : 0;
-  if (lay->g < 1) return fail(ctx, SC_ERR_ARG, "%s: pb = %d: one pair does not fit below a %d-bit N (kappa = %d)", who, lay->pb, nbits_n, kappa);
-  const int prod = square ? 2 * lay->sa : lay->pb;
-  int lg = 0;
-  while ((1 << lg) < k) lg++;
-  if (prod + lg >= nbits_n - 1)
-    return fail(ctx, SC_ERR_ARG, "%s: the sum of k = %d products (%d + %d bits) does not fit below a %d-bit N", who, k, prod, lg, nbits_n);
-  lay->M = (k + lay->g - 1) / lay->g;
-  return SC_OK;
-}
-// the draws' and exponents' row widths: the kernels hold a field in MUL_FIELD_WORDS words
-static int dot_row_words(sc_ctx* ctx, const char* who, const DotLayout& lay, int aw, int bw, int ew) {
-  if (aw < 1 || aw > MUL_FIELD_WORDS || (!lay.square && (bw < 1 || bw > MUL_FIELD_WORDS)) || ew < 1)
-    return fail(ctx, SC_ERR_ARG, "%s: rows of %d (r_a), %d (r_b), %d (e) words: expected 1 .. %d for the draws", who, aw, bw, ew, MUL_FIELD_WORDS);
-  if (32 * ew < lay.ebits) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, lay.ebits);
-  return SC_OK;
-}
-
-int sc_dot_layout(int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, int* out) {
-  DotLayout lay;
-  if (!out) return SC_ERR_ARG;
-  int rc = dot_layout(nullptr, "sc_dot_layout", nbits_n, kappa, wx, wy, is_signed, square, k, &lay); if (rc) return rc;
-  out[0] = lay.sa; out[1] = lay.sb; out[2] = lay.pb; out[3] = lay.g; out[4] = lay.M; out[5] = lay.ebits;
-  return SC_OK;
-}
-
-int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int is_signed, int square, int k, const uint32_t* r_a,
-                int aw, const uint32_t* r_b, int bw, int ew, uint32_t* e, uint32_t* R, uint32_t* S, uint64_t count) {
-  if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_dot_prep: bad argument");
-  DotLayout lay;
-  Big n(n_hptr, n_hptr + nw);
-  int rc = dot_layout(ctx, "sc_dot_prep", big_bits(n), kappa, wx, wy, is_signed, square, k, &lay); if (rc) return rc;
-  if (!r_a || (!square && !r_b) || !e || !R || !S) return fail(ctx, SC_ERR_ARG, "sc_dot_prep: bad argument");
-  rc = dot_row_words(ctx, "sc_dot_prep", lay, aw, bw, ew); if (rc) return rc;
-  if (count == 0) return SC_OK;
-  if (launch_dot_prep(ctx->stream, r_a, aw, r_b, bw, lay, nw, ew, count, e, R, S)) return fail(ctx, SC_ERR_HIP, "sc_dot_prep: launch failed");
-  return SC_OK;
-}
-
-int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int square, int k, const uint32_t* p, uint32_t* D,
-                 uint32_t* bad, uint64_t count) {
-  if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_dot_split: bad argument");
-  DotLayout lay;
-  Big n(n_hptr, n_hptr + nw);
-  int rc = dot_layout(ctx, "sc_dot_split", big_bits(n), kappa, wx, wy, 0, square, k, &lay); if (rc) return rc;
-  if (!p || !D || !bad) return fail(ctx, SC_ERR_ARG, "sc_dot_split: bad argument");
-  if (count == 0) return SC_OK;
-  if (launch_dot_split(ctx->stream, p, nw, lay, count, D, bad)) return fail(ctx, SC_ERR_HIP, "sc_dot_split: launch failed");
-  return SC_OK;
-}
-
-// ---- compare-exchange finish of a secure sort: both outputs of every column from one shared inversion ----------
-// The nf columns run as flat items (nf * count of them), so the program does not depend on nf and an index row entry is read at the
-// item's flat number.  Per item, with V = U^-1 R^3 (one product, shared by both outputs): hi = F ab ab V / R^3 = F ab^2 U^-1 and
-// lo = G T T V / R^3 = G T^2 U^-1 -- seven Montgomery products on operands loaded once.
-int sc_select_finish_cx(sc_ctx* ctx, int mod, int nfields, const uint32_t* t, const uint32_t* ab, const uint32_t* u_inv, const uint32_t* f,
-                        const uint32_t* g, const uint64_t* lo_index, const uint64_t* hi_index, uint32_t* out, uint64_t out_rows,
-                        uint64_t count) {
-  if (ctx && count == 0) return SC_OK;
-  if (!valid_mod(ctx, mod) || nfields < 1 || nfields > SEL_MAX_FIELDS || !t || !ab || !u_inv || !f || !g || !out ||
-      (!lo_index) != (!hi_index))
-    return fail(ctx, SC_ERR_ARG, "sc_select_finish_cx: bad argument");
-  const uint64_t items = (uint64_t)nfields * count;
-  const bool indexed = lo_index != nullptr;
-  if (!indexed && out_rows < 2 * items)
-    return fail(ctx, SC_ERR_ARG, "sc_select_finish_cx: out holds %llu rows, the contiguous [2][nf][count] form needs %llu",
-                (unsigned long long)out_rows, (unsigned long long)(2 * items));
-  const Mod& m = ctx->mods[mod];
-  int cid;
-  {
-    Big one(m.nwords, 0); one[0] = 1;
-    int rc = sc_const_create_cached(ctx, mod, big_shl_mod(one, m.n, 3 * m.W * m.S), &cid); if (rc) return rc;   // R^3 mod n
-  }
-  const Prog* p;
-  int rc = cached_prog(ctx, "cxfin:" + std::to_string(mod) + ":" + std::to_string(indexed ? 1 : 0), mod, [&](Builder& bd) {
-    bd.loadw(2); bd.mul_const(bd.use_const(cid)); bd.stt(0);        // V = U^-1 R^3
-    bd.loadw(3); bd.mul_extw(1); bd.mul_extw(1); bd.mul_tbl(0);     // hi = F ab^2 U^-1
-    if (indexed) bd.storew_at(5, 7); else bd.storew(5, 1);
-    bd.loadw(4); bd.mul_extw(0); bd.mul_extw(0); bd.mul_tbl(0);     // lo = G T^2 U^-1
-    if (indexed) bd.storew_at(5, 6); else bd.storew(5, 0);
-  }, &p); if (rc) return rc;
-  const uint32_t nw = m.nwords;
-  VmExt ex[8] = {mk_ext(t, nw, nw), mk_ext(ab, nw, nw), mk_ext(u_inv, nw, nw), mk_ext(f, nw, nw), mk_ext(g, nw, nw),
-                 mk_ext(out, nw, nw, out_rows), mk_ext(lo_index, 0, 0), mk_ext(hi_index, 0, 0)};   // rows >= out_rows are not written
-  return run_vm(ctx, mod, *p, ex, 8, items);
-}
+#include "sc_families.h"
 
 // ------------------------------------------------------------------------------------------------
 // Multi-GPU: comparisons are independent, so the only exchange is the reassembly of per-rank result blocks -- one

@@ -708,14 +708,11 @@ int sc_initiator_step67(sc_ctx* ctx, int paillier_key_id, const uint64_t* delta_
 // What selection.py / sorting.py used to compose from the primitives, one call per protocol step: the field layout, the Horner chain
 // of shared-exponent squarings, T_j with per-row exponents (pair kernel, or exponentiations modulo N^2 where the modulus has no
 // per-row pair instance), and the two finishes.  Temporaries TMP_SEL_*; the callees' own (TMP_S_A .. TMP_S_D, TMP_PAIR) are not held
-// across their calls.
+// across their calls.  The selection, the multiplication (§8e) and the inner product (§8g) share one blinded round trip (DESIGN.md
+// §8h): blind_and_randomize and horner_pow2 pack, keyholder_round is the key holder's step, finish_ratio divides the blinding out.
 enum SelectTmp { TMP_SEL_A = 49, TMP_SEL_B, TMP_SEL_C, TMP_SEL_D, TMP_SEL_E, TMP_SEL_F };
 
-// the layout check of every entry, against the key's N (select_layout, sc_lib.hip: the one copy of the rule)
-static int sel_layout(sc_ctx* ctx, const char* who, const PaillierKey& k, int kappa, int nf, const int* widths, SelLayout* lay) {
-  return select_layout(ctx, who, big_bits(k.n), kappa, nf, widths, lay);
-}
-// one pinned, device-visible word per context for sc_keyholder_select_mult's verdict (freed with the context's other allocations)
+// one pinned, device-visible word per context for keyholder_round's verdict (freed with the context's other allocations)
 static int select_verdict_word(sc_ctx* ctx, uint32_t** out) {
   auto* ks = keys_of(ctx);
   if (!ks->select_verdict) {
@@ -748,6 +745,18 @@ static int sel_pow2(sc_ctx* ctx, const PaillierKey& k, int bits, const uint32_t*
   return sc_modexp_shared(ctx, k.mod_n2, it->second, x, 2 * k.nw, mul_into, out, count);
 }
 
+// out = acc * prod_j base_j^(e_j) over `planes` consecutive planes base [planes][items][2 nw], e [planes][items][ew] where the modulus has
+// no pair kernel with per-row exponents: one exponentiation modulo N^2 (into tmp) and one product (into acc, the last into out) per plane
+static int pow_product_plain(sc_ctx* ctx, const PaillierKey& k, int planes, int ebits, const uint32_t* base, const uint32_t* e, int ew, uint32_t* tmp,
+                             uint32_t* acc, uint32_t* out, uint64_t items) {
+  const int w2 = 2 * k.nw;
+  for (int j = 0; j < planes; j++) {
+    int rc = sc_modexp_var(ctx, k.mod_n2, base + (size_t)j * items * w2, e + (size_t)j * items * ew, ew, ebits, -1, nullptr, 0, tmp, items); if (rc) return rc;
+    rc = sc_modmul(ctx, k.mod_n2, acc, w2, tmp, w2, j == planes - 1 ? out : acc, items); if (rc) return rc;
+  }
+  return SC_OK;
+}
+
 // T_j = [[sigma]]^(e_j) [[d_j]]^(r_a) (1 + rab_j N) for the flat items j count + i (selection.select_t): t_out [nf count][2 nw].
 // The multiplication's T_j (8e) is the same product with sigma = x, d_j = y_j, e_j = e_x_j and r_a = e_y, exponents of `ebits` bits.
 static int two_base_t(sc_ctx* ctx, const PaillierKey& k, int nf, int ebits, const uint32_t* sigma, const uint32_t* d, const uint32_t* r_a, int aw,
@@ -774,11 +783,8 @@ static int two_base_t(sc_ctx* ctx, const PaillierKey& k, int nf, int ebits, cons
   rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, rab, k.nw, mi, items); if (rc) return rc;
   rc = k.pairs ? sc_modexp_var_sq(ctx, k.mod_n, k.mod_n2, 2, x, w2, ex, ew, ebits, mi, t_out, items) : SC_ERR_UNSUPPORTED;
   if (rc != SC_ERR_UNSUPPORTED) return rc;
-  // no pair kernel with per-row exponents for this modulus: the same residues from exponentiations modulo N^2
-  rc = sc_modexp_var(ctx, k.mod_n2, x, ex, ew, ebits, -1, nullptr, 0, t_out, items); if (rc) return rc;
-  rc = sc_modmul(ctx, k.mod_n2, mi, w2, t_out, w2, mi, items); if (rc) return rc;
-  rc = sc_modexp_var(ctx, k.mod_n2, x + items * w2, ex_a, ew, ebits, -1, nullptr, 0, t_out, items); if (rc) return rc;
-  return sc_modmul(ctx, k.mod_n2, mi, w2, t_out, w2, t_out, items);
+  // no pair kernel with per-row exponents for this modulus: the same residues from exponentiations modulo N^2 (ex_a follows ex)
+  return pow_product_plain(ctx, k, 2, ebits, x, ex, ew, t_out, mi, t_out, items);
 }
 static int sel_t(sc_ctx* ctx, const PaillierKey& k, const SelLayout& lay, const uint32_t* sigma, const uint32_t* d, const uint32_t* r_a, int aw,
                  const uint32_t* e, int ew, const uint32_t* rab, uint32_t* t_out, uint64_t count) {
@@ -789,6 +795,108 @@ static int sel_finish_args(sc_ctx* ctx, const char* who, const PaillierKey* kp, 
   if (!kp || !ptrs_ok || aw < 1 || aw > 2 || ew < 1) return fail(ctx, SC_ERR_ARG, "%s: bad argument", who);
   if (32 * ew < sel_t_bits(lay)) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, sel_t_bits(lay));
   return SC_OK;
+}
+
+// ---- the blinded round trip the selection, the multiplication and the inner product share ----------------------------
+// dst = [[x + R]] rho^N over `items` rows (x, dst [items][2 nw], R [items][nw]): the packing program of all three families
+static int blind_and_randomize(sc_ctx* ctx, const PaillierKey& k, int key_id, const uint32_t* x, const uint32_t* R, const uint32_t* rho, uint32_t* dst,
+                               uint64_t items) {
+  const int w2 = 2 * k.nw;
+  const Prog* p;
+  int rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {
+    const int cn = bd.use_const(k.cst_n);
+    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
+    bd.mul_const(0); bd.mul_extw(0);                                      // [[x + R]]
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(x, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(dst, w2, w2)};
+  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, items); if (rc) return rc;
+  return sc_paillier_randomize(ctx, key_id, dst, rho, dst, items);        // * rho^N
+}
+
+// prod_f field_f^(2^off_f): the exponents are shared by the batch, so Horner from the top field with squarings only.  fld[0 .. n] from the
+// top down, fld[n] the low operand: a field's rows, the bits it lies above the next field, and the rows it holds -- a prefix of the next
+// field's, whose further rows join as copies of themselves.  Step i writes half[(n - 1 - i) & 1], the last one `out`.
+struct HornerField { const uint32_t* rows; int shift; uint64_t held; };
+static int horner_pow2(sc_ctx* ctx, const PaillierKey& k, const HornerField* fld, int n, uint32_t* const half[2], uint32_t* out) {
+  const size_t w2 = 2 * (size_t)k.nw;
+  const uint32_t* cur = fld[0].rows;
+  for (int i = 0; i < n; i++) {
+    uint32_t* dst = i == n - 1 ? out : half[(n - 1 - i) & 1];
+    const HornerField& low = fld[i + 1];
+    const uint64_t ncur = fld[i].held;
+    int rc = sel_pow2(ctx, k, fld[i].shift, cur, low.rows, dst, ncur); if (rc) return rc;
+    if (low.held > ncur)
+      HIPCHK(ctx, hipMemcpyAsync(dst + ncur * w2, low.rows + ncur * w2, (low.held - ncur) * w2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    cur = dst;
+  }
+  return SC_OK;
+}
+
+// The pack step of the selection and the multiplication once the entry has checked its arguments: R from the family's prep kernel
+// (`prep`, given R), m = [[x + R]] rho_p^N, then P = m prod_j [[col_j]]^(2^off_j) -- every field holds `count` rows
+static int pack_columns(sc_ctx* ctx, const PaillierKey& k, int key_id, const char* who, int nf, const int* off, const uint32_t* x, const uint32_t* cols,
+                        const uint32_t* rho_p, uint32_t* p_out, uint64_t count, const std::function<int(uint32_t*)>& prep) {
+  const size_t col = (size_t)count * 2 * k.nw;
+  uint32_t *R, *m, *acc;
+  int rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &R); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, col, &m); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, 2 * col, &acc); if (rc) return rc;
+  if (prep(R)) return fail(ctx, SC_ERR_HIP, "%s: launch failed", who);
+  rc = blind_and_randomize(ctx, k, key_id, x, R, rho_p, m, count); if (rc) return rc;
+  HornerField fld[SEL_MAX_FIELDS + 1];
+  for (int j = nf - 1; j >= 0; j--) fld[nf - 1 - j] = {cols + (size_t)j * col, off[j] - (j > 0 ? off[j - 1] : 0), count};
+  fld[nf] = {m, 0, count};
+  uint32_t* const half[2] = {acc, acc + col};
+  return horner_pow2(ctx, k, fld, nf, half, p_out);
+}
+
+// The key holder's step: decrypt the n_messages rows of P, let the family's split kernel (`split`, given the plaintexts, the n_products
+// products and the verdict word) multiply the fields, encrypt and randomize the products, then read the kernel's verdict.
+static int keyholder_round(sc_ctx* ctx, const char* who, const PaillierKey& k, int key_id, const uint32_t* p_enc, const uint32_t* rho, uint32_t* out,
+                           uint64_t n_messages, uint64_t n_products, const std::function<int(const uint32_t*, uint32_t*, uint32_t*)>& split,
+                           const char* layout_message) {
+  uint32_t *pl, *prod, *c;
+  int rc = tmp_words(ctx, TMP_SEL_A, n_messages * k.nw, &pl); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, n_products * k.nw, &prod); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, n_products * 2 * k.nw, &c); if (rc) return rc;
+  // the verdict word lives in pinned host memory the kernel writes itself (like the inversion's verdicts: no copy back) -- a word
+  // of its own, so nothing a callee does with the inversion's status words (status_words may free and regrow them) can touch it
+  uint32_t* bad;
+  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
+  *(volatile uint32_t*)bad = 0;             // (an earlier call has waited for its kernels before it returned)
+  rc = sc_paillier_decrypt(ctx, key_id, p_enc, pl, n_messages); if (rc) return rc;
+  if (split(pl, prod, bad)) return fail(ctx, SC_ERR_HIP, "%s: launch failed", who);
+  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, prod, k.nw, c, n_products); if (rc) return rc;
+  rc = sc_paillier_randomize(ctx, key_id, c, rho, out, n_products); if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (*(volatile uint32_t*)bad) return fail(ctx, SC_ERR_LAYOUT, "%s", layout_message);
+  return SC_OK;
+}
+
+// out = ([[AB]] T^-1)^coef * base for coef in {+1, -1, -2} (checked by the entry, before anything is launched) and an optional base:
+// coef = +1 inverts T, a negative coef inverts num_if_plus = [[AB]] instead -- one inversion pass over `items` rows either way (into
+// inv_tmp), so SC_ERR_NOT_INVERTIBLE names the row; then one launch: the lift num R^m for the m Montgomery products that follow,
+// (num inv)^|coef|, then the base
+static int finish_ratio(sc_ctx* ctx, const PaillierKey& k, int coef, const uint32_t* num_if_plus, const uint32_t* T, const uint32_t* base, uint32_t* out,
+                        uint64_t items, uint32_t* inv_tmp) {
+  const int w2 = 2 * k.nw;
+  const uint32_t* num = coef == 1 ? num_if_plus : T;
+  int rc = sc_modinv(ctx, k.mod_n2, coef == 1 ? T : num_if_plus, inv_tmp, items, nullptr); if (rc) return rc;
+  const int pairs = coef == -2 ? 2 : 1, nmul = 2 * pairs - 1 + (base ? 1 : 0);
+  const Mod& m2 = ctx->mods[k.mod_n2];
+  int cid;
+  { Big one(m2.nwords, 0); one[0] = 1; rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one, m2.n, nmul * m2.W * m2.S), &cid); if (rc) return rc; }   // R^nmul mod N^2
+  const Prog* p;
+  rc = cached_prog(ctx, "ratiofin:" + std::to_string(k.mod_n2) + ":" + std::to_string(pairs) + (base ? ":b" : ""), k.mod_n2, [&](Builder& bd) {
+    bd.loadw(0); bd.mul_const(bd.use_const(cid));                         // num R^nmul
+    bd.mul_extw(1);                                                       // num inv
+    if (pairs == 2) { bd.mul_extw(0); bd.mul_extw(1); }                   // (num inv)^2
+    if (base) bd.mul_extw(2);
+    bd.storew(3);
+  }, &p); if (rc) return rc;
+  VmExt ex[4] = {mk_ext(num, w2, w2), mk_ext(inv_tmp, w2, w2), mk_ext(base, w2, w2), mk_ext(out, w2, w2)};
+  return run_vm(ctx, k.mod_n2, *p, ex, 4, items);
 }
 
 int sc_initiator_select_d(sc_ctx* ctx, int paillier_key_id, const uint32_t* z_enc, const uint32_t* r, uint32_t* d_out, uint64_t count) {
@@ -825,7 +933,7 @@ int sc_initiator_cx_differences(sc_ctx* ctx, int paillier_key_id, int kappa, int
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_differences: bad key");
   const PaillierKey k = *kp;
   SelLayout lay;
-  int rc = sel_layout(ctx, "sc_initiator_cx_differences", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  int rc = select_layout(ctx, "sc_initiator_cx_differences", big_bits(k.n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
   if (count == 0) return SC_OK;
   if (!f_enc || !g_enc || !d_key || !d_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_differences: bad argument");
   const int w2 = 2 * k.nw, np = nfields - 1;
@@ -870,37 +978,15 @@ int sc_initiator_select_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int nf
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: bad key");
   const PaillierKey k = *kp;
   SelLayout lay;
-  int rc = sel_layout(ctx, "sc_initiator_select_pack", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  int rc = select_layout(ctx, "sc_initiator_select_pack", big_bits(k.n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
   if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: rho_p is required: P must carry a fresh rho^N");
   if (!sigma_enc || !d_enc || !r_a || !r_b || !p_out || !e_out || !rab_out || aw < 1 || aw > 2 || bw < 1 || bw > k.nw || ew < 1)
     return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: bad argument");
   if (32 * ew < sel_t_bits(lay)) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: exponent rows of %d words are too narrow for %d bits", ew, sel_t_bits(lay));
   if (count == 0) return SC_OK;
-  const int w2 = 2 * k.nw;
-  const size_t col = (size_t)count * w2;
-  uint32_t *R, *m, *acc;
-  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &R); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, col, &m); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, 2 * col, &acc); if (rc) return rc;
-  if (launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_select_pack: launch failed");
-  const Prog* p;
-  rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {
-    const int cn = bd.use_const(k.cst_n);
-    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
-    bd.mul_const(0); bd.mul_extw(0);                                      // [[sigma + R]]
-    bd.storew(2);
-  }, &p); if (rc) return rc;
-  VmExt ex[3] = {mk_ext(sigma_enc, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(m, w2, w2)};
-  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, count); if (rc) return rc;
-  rc = sc_paillier_randomize(ctx, paillier_key_id, m, rho_p, m, count); if (rc) return rc;      // * rho_p^N
-  // prod_j [[d_j]]^(2^off_j): the exponents are shared by the batch, so Horner from the top column with squarings only
-  const uint32_t* t = d_enc + (size_t)(nfields - 1) * col;
-  for (int j = nfields - 1; j >= 0; j--) {
-    uint32_t* dst = j == 0 ? p_out : acc + (size_t)(j & 1) * col;
-    rc = sel_pow2(ctx, k, lay.off[j] - (j > 0 ? lay.off[j - 1] : 0), t, j > 0 ? d_enc + (size_t)(j - 1) * col : m, dst, count); if (rc) return rc;
-    t = dst;
-  }
-  return SC_OK;
+  return pack_columns(ctx, k, paillier_key_id, "sc_initiator_select_pack", nfields, lay.off, sigma_enc, d_enc, rho_p, p_out, count, [&](uint32_t* R) {
+    return launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out);
+  });
 }
 
 int sc_keyholder_select_mult(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* p_enc,
@@ -909,27 +995,12 @@ int sc_keyholder_select_mult(sc_ctx* ctx, int paillier_key_id, int kappa, int nf
   if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_select_mult: needs the secret key");
   const PaillierKey k = *kp;
   SelLayout lay;
-  int rc = sel_layout(ctx, "sc_keyholder_select_mult", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  int rc = select_layout(ctx, "sc_keyholder_select_mult", big_bits(k.n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
   if (count == 0) return SC_OK;
   if (!p_enc || !rho_products || !out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_select_mult: bad argument");
-  const uint64_t items = (uint64_t)nfields * count;
-  uint32_t *pl, *prod, *c;
-  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &pl); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, items * k.nw, &prod); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, items * 2 * k.nw, &c); if (rc) return rc;
-  // the verdict word lives in pinned host memory the kernel writes itself (like the inversion's verdicts: no copy back) -- a word
-  // of its own, so nothing a callee does with the inversion's status words (status_words may free and regrow them) can touch it
-  uint32_t* bad;
-  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
-  *(volatile uint32_t*)bad = 0;             // (an earlier call has waited for its kernels before it returned)
-  rc = sc_paillier_decrypt(ctx, paillier_key_id, p_enc, pl, count); if (rc) return rc;
-  if (launch_select_split(ctx->stream, pl, k.nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_keyholder_select_mult: launch failed");
-  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, prod, k.nw, c, items); if (rc) return rc;
-  rc = sc_paillier_randomize(ctx, paillier_key_id, c, rho_products, out, items); if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (*(volatile uint32_t*)bad)
-    return fail(ctx, SC_ERR_LAYOUT, "select: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)");
-  return SC_OK;
+  return keyholder_round(ctx, "sc_keyholder_select_mult", k, paillier_key_id, p_enc, rho_products, out, count, (uint64_t)nfields * count,
+                         [&](const uint32_t* pl, uint32_t* prod, uint32_t* bad) { return launch_select_split(ctx->stream, pl, k.nw, lay, count, prod, bad); },
+                         "select: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)");
 }
 
 int sc_initiator_select_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* sigma_enc,
@@ -939,7 +1010,7 @@ int sc_initiator_select_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int 
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_finish: bad key");
   const PaillierKey k = *kp;
   SelLayout lay;
-  int rc = sel_layout(ctx, "sc_initiator_select_finish", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  int rc = select_layout(ctx, "sc_initiator_select_finish", big_bits(k.n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
   rc = sel_finish_args(ctx, "sc_initiator_select_finish", kp, lay, aw, ew, sigma_enc && d_enc && b_enc && products && r_a && e && rab && out); if (rc) return rc;
   if (count == 0) return SC_OK;
   const int w2 = 2 * k.nw;
@@ -971,7 +1042,7 @@ int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int nfie
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_cx_finish: bad key");
   const PaillierKey k = *kp;
   SelLayout lay;
-  int rc = sel_layout(ctx, "sc_initiator_cx_finish", k, kappa, nfields, widths_hptr, &lay); if (rc) return rc;
+  int rc = select_layout(ctx, "sc_initiator_cx_finish", big_bits(k.n), kappa, nfields, widths_hptr, &lay); if (rc) return rc;
   rc = sel_finish_args(ctx, "sc_initiator_cx_finish", kp, lay, aw, ew,
                        delta_enc && d_enc && f_enc && g_enc && products && r_a && e && rab && out && (!lo_index) == (!hi_index)); if (rc) return rc;
   const uint64_t items = (uint64_t)nfields * count;
@@ -993,10 +1064,6 @@ int sc_initiator_cx_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int nfie
 // ---- secure multiplication -------------------------------------------------------------------------------------------
 // The selection's round trip with both factors blinded: P carries A = x + e_y and B_j = y_j + e_x_j, the key holder returns [[A B_j]],
 // and [[x y_j]] = [[A B_j]] T_j^-1 with T_j = [[x]]^(e_x_j) [[y_j]]^(e_y) (1 + e_x_j e_y N).  Same temporaries as the selection's.
-static int mul_key_layout(sc_ctx* ctx, const char* who, const PaillierKey& k, int kappa, int wx, int nf, const int* wy, int is_signed, MulLayout* lay) {
-  return mul_layout(ctx, who, big_bits(k.n), kappa, wx, nf, wy, is_signed, lay);
-}
-
 int sc_initiator_mul_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
                           const uint32_t* x_enc, const uint32_t* y_enc, const uint32_t* r_a, int aw, const uint32_t* r_b, int bw,
                           const uint32_t* rho_p, int ew, uint32_t* p_out, uint32_t* e_out, uint32_t* rab_out, uint64_t count) {
@@ -1004,36 +1071,14 @@ int sc_initiator_mul_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, i
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: bad key");
   const PaillierKey k = *kp;
   MulLayout lay;
-  int rc = mul_key_layout(ctx, "sc_initiator_mul_pack", k, kappa, wx, nfields, wy_hptr, is_signed, &lay); if (rc) return rc;
+  int rc = mul_layout(ctx, "sc_initiator_mul_pack", big_bits(k.n), kappa, wx, nfields, wy_hptr, is_signed, &lay); if (rc) return rc;
   if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: rho_p is required: P must carry a fresh rho^N");
   if (!x_enc || !y_enc || !r_a || !r_b || !p_out || !e_out || !rab_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: bad argument");
-  rc = mul_row_words(ctx, "sc_initiator_mul_pack", lay, aw, bw, ew, k.nw); if (rc) return rc;
+  rc = row_words(ctx, "sc_initiator_mul_pack", mul_ebits(lay), aw, bw, true, std::min(k.nw, MUL_FIELD_WORDS), ew); if (rc) return rc;
   if (count == 0) return SC_OK;
-  const int w2 = 2 * k.nw;
-  const size_t col = (size_t)count * w2;
-  uint32_t *R, *m, *acc;
-  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &R); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, col, &m); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, 2 * col, &acc); if (rc) return rc;
-  if (launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_mul_pack: launch failed");
-  const Prog* p;
-  rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {     // the selection's program
-    const int cn = bd.use_const(k.cst_n);
-    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
-    bd.mul_const(0); bd.mul_extw(0);                                      // [[x + R]]
-    bd.storew(2);
-  }, &p); if (rc) return rc;
-  VmExt ex[3] = {mk_ext(x_enc, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(m, w2, w2)};
-  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, count); if (rc) return rc;
-  rc = sc_paillier_randomize(ctx, paillier_key_id, m, rho_p, m, count); if (rc) return rc;      // * rho_p^N
-  // prod_j [[y_j]]^(2^off_j): sc_initiator_select_pack's Horner chain of shared-exponent squarings, with this layout's offsets
-  const uint32_t* t = y_enc + (size_t)(nfields - 1) * col;
-  for (int j = nfields - 1; j >= 0; j--) {
-    uint32_t* dst = j == 0 ? p_out : acc + (size_t)(j & 1) * col;
-    rc = sel_pow2(ctx, k, lay.off[j] - (j > 0 ? lay.off[j - 1] : 0), t, j > 0 ? y_enc + (size_t)(j - 1) * col : m, dst, count); if (rc) return rc;
-    t = dst;
-  }
-  return SC_OK;
+  return pack_columns(ctx, k, paillier_key_id, "sc_initiator_mul_pack", nfields, lay.off, x_enc, y_enc, rho_p, p_out, count, [&](uint32_t* R) {
+    return launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out);
+  });
 }
 
 int sc_keyholder_mul(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p_enc,
@@ -1042,25 +1087,12 @@ int sc_keyholder_mul(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nf
   if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_mul: needs the secret key");
   const PaillierKey k = *kp;
   MulLayout lay;
-  int rc = mul_key_layout(ctx, "sc_keyholder_mul", k, kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
+  int rc = mul_layout(ctx, "sc_keyholder_mul", big_bits(k.n), kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
   if (count == 0) return SC_OK;
   if (!p_enc || !rho_products || !out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_mul: bad argument");
-  const uint64_t items = (uint64_t)nfields * count;
-  uint32_t *pl, *prod, *c;
-  rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &pl); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, items * k.nw, &prod); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, items * 2 * k.nw, &c); if (rc) return rc;
-  uint32_t* bad;                              // the pinned verdict word of sc_keyholder_select_mult
-  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
-  *(volatile uint32_t*)bad = 0;
-  rc = sc_paillier_decrypt(ctx, paillier_key_id, p_enc, pl, count); if (rc) return rc;
-  if (launch_mul_split(ctx->stream, pl, k.nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_keyholder_mul: launch failed");
-  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, prod, k.nw, c, items); if (rc) return rc;
-  rc = sc_paillier_randomize(ctx, paillier_key_id, c, rho_products, out, items); if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (*(volatile uint32_t*)bad)
-    return fail(ctx, SC_ERR_LAYOUT, "mul: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)");
-  return SC_OK;
+  return keyholder_round(ctx, "sc_keyholder_mul", k, paillier_key_id, p_enc, rho_products, out, count, (uint64_t)nfields * count,
+                         [&](const uint32_t* pl, uint32_t* prod, uint32_t* bad) { return launch_mul_split(ctx->stream, pl, k.nw, lay, count, prod, bad); },
+                         "mul: a decrypted P exceeds the announced field layout (kappa or widths differ between the players)");
 }
 
 int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* x_enc,
@@ -1070,7 +1102,7 @@ int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: bad key");
   const PaillierKey k = *kp;
   MulLayout lay;
-  int rc = mul_key_layout(ctx, "sc_initiator_mul_finish", k, kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
+  int rc = mul_layout(ctx, "sc_initiator_mul_finish", big_bits(k.n), kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
   if (!x_enc || !y_enc || !products || !e || !rab || !out || ew < 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: bad argument");
   if (coef != 1 && coef != -1 && coef != -2) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: coef = %d: expected +1, -1 or -2", coef);
   if (32 * ew < mul_ebits(lay)) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: exponent rows of %d words are too narrow for %d bits", ew, mul_ebits(lay));
@@ -1081,24 +1113,7 @@ int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   rc = tmp_words(ctx, TMP_SEL_D, items * w2, &T); if (rc) return rc;
   rc = tmp_words(ctx, TMP_SEL_E, items * w2, &inv); if (rc) return rc;
   rc = two_base_t(ctx, k, nfields, mul_ebits(lay), x_enc, y_enc, e + items * ew /* e_y */, ew, e, ew, rab, T, count); if (rc) return rc;
-  // [[x y]]^coef = ([[A B]] T^-1)^coef: coef = +1 inverts T, a negative coef inverts [[A B]] instead -- one inversion pass either way
-  const uint32_t* num = coef == 1 ? products : T;
-  rc = sc_modinv(ctx, k.mod_n2, coef == 1 ? T : products, inv, items, nullptr); if (rc) return rc;
-  // one launch: the lift num R^m for the m Montgomery products that follow, (num inv)^|coef|, then the base
-  const int pairs = coef == -2 ? 2 : 1, nmul = 2 * pairs - 1 + (base ? 1 : 0);
-  const Mod& m2 = ctx->mods[k.mod_n2];
-  int cid;
-  { Big one(m2.nwords, 0); one[0] = 1; rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one, m2.n, nmul * m2.W * m2.S), &cid); if (rc) return rc; }   // R^nmul mod N^2
-  const Prog* p;
-  rc = cached_prog(ctx, "mulfin:" + std::to_string(k.mod_n2) + ":" + std::to_string(pairs) + (base ? ":b" : ""), k.mod_n2, [&](Builder& bd) {
-    bd.loadw(0); bd.mul_const(bd.use_const(cid));                         // num R^nmul
-    bd.mul_extw(1);                                                       // num inv
-    if (pairs == 2) { bd.mul_extw(0); bd.mul_extw(1); }                   // (num inv)^2
-    if (base) bd.mul_extw(2);
-    bd.storew(3);
-  }, &p); if (rc) return rc;
-  VmExt ex[4] = {mk_ext(num, w2, w2), mk_ext(inv, w2, w2), mk_ext(base, w2, w2), mk_ext(out, w2, w2)};
-  return run_vm(ctx, k.mod_n2, *p, ex, 4, items);
+  return finish_ratio(ctx, k, coef, products, T, base, out, items, inv);
 }
 
 // ---- secure inner product ----------------------------------------------------------------------------------------------
@@ -1107,10 +1122,6 @@ int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
 // pairs are packed g to a message, pair j in message j mod M at position j div M, so the planes of one position are contiguous in
 // x_enc [k][count][2 nw] and the messages that hold the (partial) top position are a prefix of P [M][count][2 nw].  Same temporaries as
 // the selection's.
-static int dot_key_layout(sc_ctx* ctx, const char* who, const PaillierKey& k, int kappa, int wx, int wy, int is_signed, int square, int kk, DotLayout* lay) {
-  return dot_layout(ctx, who, big_bits(k.n), kappa, wx, wy, is_signed, square, kk, lay);
-}
-
 int sc_initiator_dot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int is_signed, int square, int kk, const uint32_t* x_enc,
                           const uint32_t* y_enc, const uint32_t* r_a, int aw, const uint32_t* r_b, int bw, const uint32_t* rho_p, int ew,
                           uint32_t* p_out, uint32_t* e_out, uint32_t* s_out, uint64_t count) {
@@ -1118,10 +1129,10 @@ int sc_initiator_dot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, i
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: bad key");
   const PaillierKey k = *kp;
   DotLayout lay;
-  int rc = dot_key_layout(ctx, "sc_initiator_dot_pack", k, kappa, wx, wy, is_signed, square, kk, &lay); if (rc) return rc;
+  int rc = dot_layout(ctx, "sc_initiator_dot_pack", big_bits(k.n), kappa, wx, wy, is_signed, square, kk, &lay); if (rc) return rc;
   if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: rho_p is required: every P must carry a fresh rho^N");
   if (!x_enc || !r_a || (!square && (!y_enc || !r_b)) || !p_out || !e_out || !s_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: bad argument");
-  rc = dot_row_words(ctx, "sc_initiator_dot_pack", lay, aw, bw, ew); if (rc) return rc;
+  rc = row_words(ctx, "sc_initiator_dot_pack", lay.ebits, aw, bw, !square, MUL_FIELD_WORDS, ew); if (rc) return rc;
   if (count == 0) return SC_OK;
   const int w2 = 2 * k.nw, M = lay.M;
   const size_t col = (size_t)count * w2;               // one plane
@@ -1135,34 +1146,18 @@ int sc_initiator_dot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, i
   // m < n(f), all M of them below the top position.  Field 0 -- the planes x_0 .. x_(M-1) -- is folded into [[x + R]] rho_p^N.
   const int fp = square ? 1 : 2, npos = (kk + M - 1) / M, F = fp * npos;
   const int n_top = kk - (npos - 1) * M;
-  auto base = [&](int f) { return ((f % fp) ? y_enc : x_enc) + (size_t)(f / fp) * M * col; };
+  auto rows = [&](int f) { return ((f % fp) ? y_enc : x_enc) + (size_t)(f / fp) * M * col; };
   auto fbits = [&](int f) { return (f % fp) ? lay.sb : lay.sa; };
-  auto held = [&](int f) { return (uint64_t)(f / fp == npos - 1 ? n_top : M); };
+  auto held = [&](int f) { return (uint64_t)(f / fp == npos - 1 ? n_top : M) * count; };
   uint32_t* m_dst = F == 1 ? p_out : m;
-  const Prog* p;
-  rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {     // the selection's program
-    const int cn = bd.use_const(k.cst_n);
-    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[R]] = 1 + R N
-    bd.mul_const(0); bd.mul_extw(0);                                      // [[x + R]]
-    bd.storew(2);
-  }, &p); if (rc) return rc;
-  VmExt ex[3] = {mk_ext(x_enc, w2, w2), mk_ext(R, k.nw, k.nw), mk_ext(m_dst, w2, w2)};
-  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, items); if (rc) return rc;
-  rc = sc_paillier_randomize(ctx, paillier_key_id, m_dst, rho_p, m_dst, items); if (rc) return rc;      // * rho_p_m^N
-  // Horner from the top field with shared-exponent squarings: cur^(2^bits(f - 1)) times field f - 1; the messages that join below the
-  // partial top position start as a copy of their own field
-  const uint32_t* cur = base(F - 1);
-  uint64_t ncur = held(F - 1);
-  for (int f = F - 1; f >= 1; f--) {
-    uint32_t* dst = f == 1 ? p_out : acc + (size_t)(f & 1) * items * w2;
-    const uint32_t* low = f == 1 ? m : base(f - 1);
-    rc = sel_pow2(ctx, k, fbits(f - 1), cur, low, dst, ncur * count); if (rc) return rc;
-    const uint64_t nlow = held(f - 1);
-    if (nlow > ncur)
-      HIPCHK(ctx, hipMemcpyAsync(dst + ncur * col, low + ncur * col, (nlow - ncur) * col * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    cur = dst; ncur = nlow;
-  }
-  return SC_OK;
+  rc = blind_and_randomize(ctx, k, paillier_key_id, x_enc, R, rho_p, m_dst, items); if (rc) return rc;      // * rho_p_m^N
+  // Horner from the top field: cur^(2^bits(f - 1)) times field f - 1; the messages that join below the partial top position start as a
+  // copy of their own field
+  std::vector<HornerField> fld(F);
+  for (int f = F - 1; f >= 1; f--) fld[F - 1 - f] = {rows(f), fbits(f - 1), held(f)};
+  fld[F - 1] = {m, 0, held(0)};
+  uint32_t* const half[2] = {acc + items * w2, acc};
+  return horner_pow2(ctx, k, fld.data(), F - 1, half, p_out);
 }
 
 int sc_keyholder_dot(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int square, int kk, const uint32_t* p_enc, const uint32_t* rho_d,
@@ -1171,25 +1166,12 @@ int sc_keyholder_dot(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy
   if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_dot: needs the secret key");
   const PaillierKey k = *kp;
   DotLayout lay;
-  int rc = dot_key_layout(ctx, "sc_keyholder_dot", k, kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
+  int rc = dot_layout(ctx, "sc_keyholder_dot", big_bits(k.n), kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
   if (!p_enc || !rho_d || !out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_dot: bad argument");
   if (count == 0) return SC_OK;
-  const uint64_t items = (uint64_t)lay.M * count;
-  uint32_t *pl, *D, *c;
-  rc = tmp_words(ctx, TMP_SEL_A, items * k.nw, &pl); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, (uint64_t)count * k.nw, &D); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, (uint64_t)count * 2 * k.nw, &c); if (rc) return rc;
-  uint32_t* bad;                              // the pinned verdict word of sc_keyholder_select_mult
-  rc = select_verdict_word(ctx, &bad); if (rc) return rc;
-  *(volatile uint32_t*)bad = 0;
-  rc = sc_paillier_decrypt(ctx, paillier_key_id, p_enc, pl, items); if (rc) return rc;
-  if (launch_dot_split(ctx->stream, pl, k.nw, lay, count, D, bad)) return fail(ctx, SC_ERR_HIP, "sc_keyholder_dot: launch failed");
-  rc = sc_paillier_encrypt_raw(ctx, k.mod_n2, k.cst_n, D, k.nw, c, count); if (rc) return rc;
-  rc = sc_paillier_randomize(ctx, paillier_key_id, c, rho_d, out, count); if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (*(volatile uint32_t*)bad)
-    return fail(ctx, SC_ERR_LAYOUT, "dot: a decrypted P exceeds the end of its message in the announced layout (kappa, widths, k or the mode differ between the players)");
-  return SC_OK;
+  return keyholder_round(ctx, "sc_keyholder_dot", k, paillier_key_id, p_enc, rho_d, out, (uint64_t)lay.M * count, count,
+                         [&](const uint32_t* pl, uint32_t* D, uint32_t* bad) { return launch_dot_split(ctx->stream, pl, k.nw, lay, count, D, bad); },
+                         "dot: a decrypted P exceeds the end of its message in the announced layout (kappa, widths, k or the mode differ between the players)");
 }
 
 // acc_out = acc_in * prod_j base_j^(e_j) over `planes` consecutive planes base [planes][count][2 nw], e [planes][count][ew]: groups of at
@@ -1206,16 +1188,6 @@ static int dot_t_side(sc_ctx* ctx, const PaillierKey& k, int planes, int ebits, 
   }
   return SC_OK;
 }
-// the same product where the modulus has no such kernel: one exponentiation modulo N^2 and one product per plane (what two_base_t does)
-static int dot_t_side_plain(sc_ctx* ctx, const PaillierKey& k, int planes, int ebits, const uint32_t* base, const uint32_t* e, int ew, uint32_t* tmp,
-                            uint32_t* acc, uint64_t count) {
-  const int w2 = 2 * k.nw;
-  for (int j = 0; j < planes; j++) {
-    int rc = sc_modexp_var(ctx, k.mod_n2, base + (size_t)j * count * w2, e + (size_t)j * count * ew, ew, ebits, -1, nullptr, 0, tmp, count); if (rc) return rc;
-    rc = sc_modmul(ctx, k.mod_n2, acc, w2, tmp, w2, acc, count); if (rc) return rc;
-  }
-  return SC_OK;
-}
 
 int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int square, int kk, const uint32_t* x_enc,
                             const uint32_t* y_enc, const uint32_t* d_enc, const uint32_t* e, int ew, const uint32_t* s, const uint32_t* base,
@@ -1224,7 +1196,7 @@ int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: bad key");
   const PaillierKey k = *kp;
   DotLayout lay;
-  int rc = dot_key_layout(ctx, "sc_initiator_dot_finish", k, kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
+  int rc = dot_layout(ctx, "sc_initiator_dot_finish", big_bits(k.n), kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
   if (!x_enc || (!square && !y_enc) || !d_enc || !e || !s || !out || ew < 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: bad argument");
   if (coef != 1 && coef != -1 && coef != -2) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: coef = %d: expected +1, -1 or -2", coef);
   if (32 * ew < lay.ebits) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: exponent rows of %d words are too narrow for %d bits", ew, lay.ebits);
@@ -1242,29 +1214,12 @@ int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   if (rc == SC_OK && !square) rc = dot_t_side(ctx, k, kk, lay.ebits, y_enc, e + (size_t)kk * count * ew, ew, pp, &T, count);
   if (rc == SC_ERR_UNSUPPORTED) {
     rc = tmp_words(ctx, TMP_SEL_B, col, &tmp); if (rc) return rc;
-    rc = dot_t_side_plain(ctx, k, kk, lay.ebits, x_enc, e, ew, tmp, mi, count);
-    if (rc == SC_OK && !square) rc = dot_t_side_plain(ctx, k, kk, lay.ebits, y_enc, e + (size_t)kk * count * ew, ew, tmp, mi, count);
+    rc = pow_product_plain(ctx, k, kk, lay.ebits, x_enc, e, ew, tmp, mi, mi, count);
+    if (rc == SC_OK && !square) rc = pow_product_plain(ctx, k, kk, lay.ebits, y_enc, e + (size_t)kk * count * ew, ew, tmp, mi, mi, count);
     T = mi;
   }
   if (rc) return rc;
-  // [[sum]]^coef = ([[D]] T^-1)^coef: sc_initiator_mul_finish's rule -- coef = +1 inverts T, a negative coef inverts [[D]]; one pass
-  // over `count` items either way, so SC_ERR_NOT_INVERTIBLE names the row
-  const uint32_t* num = coef == 1 ? d_enc : T;
-  rc = sc_modinv(ctx, k.mod_n2, coef == 1 ? T : d_enc, inv, count, nullptr); if (rc) return rc;
-  const int pairs = coef == -2 ? 2 : 1, nmul = 2 * pairs - 1 + (base ? 1 : 0);
-  const Mod& m2 = ctx->mods[k.mod_n2];
-  int cid;
-  { Big one(m2.nwords, 0); one[0] = 1; rc = sc_const_create_cached(ctx, k.mod_n2, big_shl_mod(one, m2.n, nmul * m2.W * m2.S), &cid); if (rc) return rc; }   // R^nmul mod N^2
-  const Prog* p;
-  rc = cached_prog(ctx, "dotfin:" + std::to_string(k.mod_n2) + ":" + std::to_string(pairs) + (base ? ":b" : ""), k.mod_n2, [&](Builder& bd) {
-    bd.loadw(0); bd.mul_const(bd.use_const(cid));                         // num R^nmul
-    bd.mul_extw(1);                                                       // num inv
-    if (pairs == 2) { bd.mul_extw(0); bd.mul_extw(1); }                   // (num inv)^2
-    if (base) bd.mul_extw(2);
-    bd.storew(3);
-  }, &p); if (rc) return rc;
-  VmExt ex[4] = {mk_ext(num, w2, w2), mk_ext(inv, w2, w2), mk_ext(base, w2, w2), mk_ext(out, w2, w2)};
-  return run_vm(ctx, k.mod_n2, *p, ex, 4, count);
+  return finish_ratio(ctx, k, coef, d_enc, T, base, out, count, inv);
 }
 
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {

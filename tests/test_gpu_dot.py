@@ -586,3 +586,72 @@ def test_selection_and_multiplication_residues_are_unchanged(engine, keys):
                          rho_products=engine.upload([d[3][0] for d in sdraws], nw).unsqueeze(0).contiguous())
     got = sel.select_batch(lay, s_t, d_t.unsqueeze(0), b_t.unsqueeze(0), ap, bp, sd)
     assert _rows(engine, got) == [smodel.select(sk, kappa, [l], s_c[i], [d_c[i]], [b_c[i]], sdraws[i])[0] for i in range(B)]
+
+
+# ---- the three families interleaved on one context -----------------------------------------------------------------------------------------
+def test_families_interleaved_on_one_context(engine, keys):
+    """The selection, the multiplication and the inner product share their temporaries (TMP_SEL_*), the packing program and the ratio
+    finish's programs, so they run here in turn on one context and a 512-bit key (no per-row pair instance: the plain product of
+    powers): a two-column selection on B = 3 rows, a two-column multiplication with coef = -2 and a base, an inner product with k = 3 at
+    g = 2, M = 2 (message 0 holds pairs 0 and 2, message 1 holds pair 1 and joins the Horner chain below the partial top position), a
+    sum of squares with k = 3 (g = 4, M = 1: no message joins), and the selection again on B = 5 rows -- every slot grows and shrinks,
+    the packing program runs with `count` and with M * count items, the finish under the keys (2 pairs, base) and (1 pair, no base).
+    Every ciphertext against the models under injected draws, and every decryption against the plain result."""
+    from protocols.secure_comparison_amd import selection as sel
+    from protocols.secure_comparison_amd.dotproduct import dot_batch
+    from protocols.secure_comparison_amd.multiplication import MulDraws, MulLayout, mul_batch
+
+    sk = _key(keys, 512)
+    ap, bp = _paillier(engine, sk)
+    n, nw, B, kappa = sk.n, ap.mod_n.nwords, 3, KAPPA
+    nbits = n.bit_length()
+    rng = random.Random(900)
+    dec = lambda t: engine.download(bp.decrypt_raw_batch(t.reshape(-1, t.shape[-1]).contiguous()))  # noqa: E731
+    stack = lambda f, cols, w, draws: torch.stack([engine.upload([f(d, j) for d in draws], w) for j in range(cols)]).contiguous()  # noqa: E731
+
+    def selection(count):
+        widths = [16, 12]
+        lay = sel.SelectLayout(widths[0], kappa, (widths[1],), nbits)
+        sig = [i % 2 for i in range(count)]
+        av = [[rng.getrandbits(w) for _ in range(count)] for w in widths]
+        bv = [[rng.getrandbits(w) for _ in range(count)] for w in widths]
+        dv = [[av[j][i] - bv[j][i] + (1 << w) for i in range(count)] for j, w in enumerate(widths)]
+        (s_c, s_t), (d_c, d_t), (b_c, b_t) = _enc(engine, sk, ap, rng, sig), _enc_planes(engine, sk, ap, rng, dv), _enc_planes(engine, sk, ap, rng, bv)
+        draws = [smodel.draw(rng, kappa, widths, n) for _ in range(count)]
+        sd = sel.SelectDraws(r_a=engine.upload([d[0] for d in draws], 2), r_b=stack(lambda d, j: d[1][j], 2, (max(lay.fbits) + 31) // 32, draws),
+                             rho_p=engine.upload([d[2] for d in draws], nw), rho_products=stack(lambda d, j: d[3][j], 2, nw, draws))
+        got = sel.select_batch(lay, s_t, d_t, b_t, ap, bp, sd)
+        want = [smodel.select(sk, kappa, widths, s_c[i], [c[i] for c in d_c], [c[i] for c in b_c], draws[i]) for i in range(count)]
+        assert _rows(engine, got) == [want[i][j] for j in range(2) for i in range(count)]
+        assert dec(got) == [(av if sig[i] else bv)[j][i] for j in range(2) for i in range(count)]
+
+    def multiplication():
+        wx, wy = 16, [16, 9]
+        xs = [_value(rng, wx, True) for _ in range(B)]
+        ys = [[_value(rng, w, True) for _ in range(B)] for w in wy]
+        bs = [[rng.getrandbits(40) for _ in range(B)] for _ in wy]
+        (x_c, x_t), (y_c, y_t), (b_c, b_t) = _enc(engine, sk, ap, rng, xs), _enc_planes(engine, sk, ap, rng, ys), _enc_planes(engine, sk, ap, rng, bs)
+        draws = [mmodel.draw(rng, kappa, wx, wy, n) for _ in range(B)]
+        md = MulDraws(r_a=engine.upload([d[0] for d in draws], 2), r_b=stack(lambda d, j: d[1][j], 2, 2, draws),
+                      rho_p=engine.upload([d[2] for d in draws], nw), rho_products=stack(lambda d, j: d[3][j], 2, nw, draws))
+        got = mul_batch(MulLayout(kappa, wx, tuple(wy), True, nbits), x_t, y_t, ap, bp, md, b_t, -2)
+        want = [mmodel.multiply_enc(sk, kappa, wx, wy, True, x_c[i], [c[i] for c in y_c], draws[i], [c[i] for c in b_c], -2) for i in range(B)]
+        assert _rows(engine, got) == [want[i][j] for j in range(2) for i in range(B)]
+        assert dec(got) == [(bs[j][i] - 2 * xs[i] * ys[j][i]) % n for j in range(2) for i in range(B)]
+
+    def inner_product(wx, wy, square, k, g, M):
+        lay = _layout(sk, kappa, wx, wy, True, square, k)
+        assert (lay.g, lay.M) == (g, M)
+        xs, ys, draws = _case(rng, sk, kappa, wx, wy, True, square, k, B)
+        x_c, x_t = _enc_planes(engine, sk, ap, rng, xs)
+        y_c, y_t = (None, None) if square else _enc_planes(engine, sk, ap, rng, ys)
+        got = dot_batch(lay, x_t, y_t, ap, bp, _upload_draws(engine, ap, lay, draws))
+        assert engine.download(got) == [model.dot_enc(sk, kappa, wx, wy, True, square, [c[i] for c in x_c], None if square else [c[i] for c in y_c],
+                                                      draws[i]) for i in range(B)]
+        assert dec(got) == [sum(xs[j][i] * (xs[j][i] if square else ys[j][i]) for j in range(k)) % n for i in range(B)]
+
+    selection(B)
+    multiplication()
+    inner_product(64, 48, False, 3, 2, 2)
+    inner_product(64, 0, True, 3, 4, 1)
+    selection(5)
