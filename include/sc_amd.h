@@ -296,6 +296,37 @@ int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key, int kappa, int wx, in
                             const uint32_t* y_enc_dptr, const uint32_t* d_enc_dptr, const uint32_t* e_dptr, int ew,
                             const uint32_t* s_dptr, const uint32_t* base_dptr /* nullable */, int coef, uint32_t* out_dptr,
                             uint64_t count);
+/* ---- secure one-hot encoding and table lookup by an encrypted index: blind, decrypt, rotate -------------------------- */
+/* From [[i]] the k ciphertexts [[ [t == i mod k] ]], t < k, in one round trip; sc_initiator_dot_pack / sc_keyholder_dot /
+ * sc_initiator_dot_finish over these planes (width 1) and a table's planes then give [[table[i]]] in a second one.  Per row and index
+ * q < m the initiator draws r_q < 2^(ib + kappa) and sends the field d_q = i_q + r_q, f = ib + kappa + 1 bits, g fields to a message at
+ * the bit offsets 0, f, 2f, .. and M = ceil(m / g) messages per row: index q lives in message q div g at position q mod g, so only the
+ * last message may hold fewer than g fields.  The key holder decrypts, takes j_q = d_q mod k and returns E[q][t] = [[ [t == j_q] ]],
+ * every one freshly randomized; the initiator reads out[q][t] = E[q][(t + r_q mod k) mod k], a gather of rows.
+ * PRECONDITION 0 <= i_q < 2^ib.  The result marks position i_q mod k: an index at or above k is reduced, not refused.
+ * LAYOUT (kappa, ib, k, m): 1 <= kappa <= 62, 1 <= ib <= 32, 1 <= k <= 1024, 1 <= m <= 65536 and the one fit rule f < bits(N) - 1; then
+ * g = floor((bits(N) - 2) / f).  sc_onehot_layout evaluates that rule on the host alone (no context, no device work): out = {f, g, M, rw}
+ * with rw = ceil((ib + kappa) / 32) the words of a mask; SC_ERR_ARG when a quantity is out of range or does not fit.  Every entry below
+ * checks the same rule against its key, then its arrays in the order of its parameters, before anything is launched (SC_ERR_ARG,
+ * sc_last_error names the argument).  m k count < 2^31.  Arrays, scratch, stream and the keys served: as the inner product's entries.
+ * Still SC_ABI_VERSION 5: additions. */
+int sc_onehot_layout(int nbits_n, int kappa, int ib, int k, int m, int* out /* f, g, M, rw */);
+/* Initiator, the messages P_mm = prod_j [[i_(mm g + j)]]^(2^(j f)) (1 + R_mm N) rho_p_mm^N with R_mm = sum_j 2^(j f) r_(mm g + j), and the
+ * rotations the finish needs.  index_enc: [m][count][2 nwords]; r: [m][count][rw] below 2^(ib + kappa), rw <= 3 and 32 rw >= ib + kappa --
+ * an independent mask per index; rho_p: [M][count][nwords] in [1, N), NOT nullable (SC_ERR_ARG), for sc_initiator_select_pack's reason.
+ * p_out: [M][count][2 nwords]; rot_out: [m][count] int32 = r mod k, taken over all the words of r. */
+int sc_initiator_onehot_pack(sc_ctx* ctx, int paillier_key, int kappa, int ib, int k, int m, const uint32_t* index_enc_dptr,
+                             const uint32_t* r_dptr, int rw, const uint32_t* rho_p_dptr, uint32_t* p_out_dptr, int32_t* rot_out_dptr,
+                             uint64_t count);
+/* Key holder (secret key): CRT decryption of the M count messages, the m k count plaintexts [t == d_q mod k] (sc_onehot_split), their
+ * encryptions randomized with rho_e [m][k][count][nwords]: e_out [m][k][count][2 nwords].  SC_ERR_LAYOUT when a decrypted message has a
+ * bit at or above its own end (`e_out` is unspecified then); a narrower layout is seen only on the wire.  Synchronous. */
+int sc_keyholder_onehot(sc_ctx* ctx, int paillier_key, int kappa, int ib, int k, int m, const uint32_t* p_enc_dptr,
+                        const uint32_t* rho_e_dptr, uint32_t* e_out_dptr, uint64_t count);
+/* Initiator: out[q][t][b] = e_enc[q][(t + rot[q][b]) mod k][b], both [m][k][count][2 nwords]; rot = sc_initiator_onehot_pack's.  One
+ * launch, no arithmetic modulo N^2.  out must not overlap e_enc (SC_ERR_ARG). */
+int sc_initiator_onehot_finish(sc_ctx* ctx, int paillier_key, int kappa, int ib, int k, int m, const uint32_t* e_enc_dptr,
+                               const int32_t* rot_dptr, uint32_t* out_dptr, uint64_t count);
 /* The network of a secure top-m (8d): the comparators that bring the m smallest of k values to the positions 0 .. m-1 in ascending
  * order -- with only_last, the m-th smallest to position m-1 alone -- for 1 <= m <= k <= 1024 (SC_ERR_ARG otherwise).  Host only: no
  * context, no device work, a pure function of (k, m, only_last) that both players evaluate.  Comparator t puts the smaller value at

@@ -241,6 +241,22 @@ int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, 
  * uint32, never cleared here) is set to 1 when a message has a bit at or above its OWN end n_m pb, n_m = the pairs it holds. */
 int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int square, int k, const uint32_t* p_dptr,
                  uint32_t* D_dptr, uint32_t* bad_dptr, uint64_t count);
+/* ---- secure one-hot encoding: the plaintext-word kernels of the two players ------------------------------------------ */
+/* Layout as sc_onehot_layout's (include/sc_amd.h), against N (n_hptr, nw words): field q of a row, d_q = i_q + r_q of f = ib + kappa + 1
+ * bits, lives in message q div g at bits [(q mod g) f, (q mod g + 1) f); message mm holds n_mm = min(g, m - mm g) fields.
+ * sc_onehot_prep (initiator): from r [m][count][rw] (< 2^(ib + kappa), rw <= 3, 32 rw >= ib + kappa): R [M][count][nw], the masks of
+ * every message at their bit offsets, and rot [m][count] int32 = r mod k over all the words of r. */
+int sc_onehot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* r_dptr, int rw,
+                   uint32_t* R_dptr, int32_t* rot_dptr, uint64_t count);
+/* sc_onehot_split (key holder): from the decrypted P [M][count][nw]: prod [m][k][count][nw] with prod[q][t][b] = [t == d_q mod k] (the
+ * remainder over all the words of the field).  *bad_dptr (one uint32, never cleared here) is set to 1 when a message has a bit at or
+ * above its OWN end n_mm f. */
+int sc_onehot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* p_dptr,
+                    uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
+/* sc_onehot_rotate (initiator): out[q][t][b] = e[q][(t + rot[q][b]) mod k][b] for rows of `words` words, e and out [m][k][count][words],
+ * rot [m][count] int32 (reduced modulo k by the kernel).  out must not overlap e (SC_ERR_ARG). */
+int sc_onehot_rotate(sc_ctx* ctx, int words, int k, int m, const uint32_t* e_dptr, const int32_t* rot_dptr, uint32_t* out_dptr,
+                     uint64_t count);
 /* sc_select_finish_cx (initiator, the compare-exchange of a secure sort): from a selection with sigma = delta,
  * base F and d = G - F + 2^w, both outputs hi = F ab^2 u_inv and lo = G t^2 u_inv modulo mod (N^2), where u_inv = (t ab)^-1.
  * t, ab, u_inv, f, g: [nfields][count][words(mod)], nfields 1 .. 4.  lo_index / hi_index (both or neither): uint64 [nfields][count],

@@ -4,6 +4,7 @@ from .communicator import Communicator, InMemoryCommunicator, StreamCommunicator
 from .dotproduct import (DotDraws, DotLayout, draw_dot, secure_dot_batch, secure_squared_distance_batch, secure_sum_squares_batch)
 from .initiator import AlicePlain, Initiator
 from .keyholder import BobPlain, KeyHolder
+from .lookup import OnehotDraws, OnehotLayout, draw_onehot, secure_gather_batch, secure_lookup_batch, secure_onehot_batch
 from .multiplication import (MulDraws, MulLayout, draw_mul, secure_and_batch, secure_equal_batch, secure_in_range_batch, secure_multiply_batch,
                              secure_or_batch, secure_xor_batch)
 from .schemes import DGK, DGKCiphertext, Paillier, PaillierCiphertext
@@ -15,5 +16,6 @@ __all__ = ["Communicator", "InMemoryCommunicator", "StreamCommunicator", "Initia
            "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch",
            "secure_sort_batch", "secure_topk_batch", "secure_kth_batch", "secure_median_batch", "MulLayout", "MulDraws", "draw_mul",
            "secure_multiply_batch", "secure_and_batch", "secure_or_batch", "secure_xor_batch", "secure_equal_batch", "secure_in_range_batch",
-           "DotLayout", "DotDraws", "draw_dot", "secure_dot_batch", "secure_sum_squares_batch", "secure_squared_distance_batch"]
+           "DotLayout", "DotDraws", "draw_dot", "secure_dot_batch", "secure_sum_squares_batch", "secure_squared_distance_batch",
+           "OnehotLayout", "OnehotDraws", "draw_onehot", "secure_onehot_batch", "secure_gather_batch", "secure_lookup_batch"]
 __version__ = "0.1.0"

@@ -20,6 +20,8 @@ SYMBOLS = [
     "sc_initiator_select_d", "sc_paillier_one_minus", "sc_initiator_cx_differences", "sc_initiator_select_pack", "sc_keyholder_select_mult",
     "sc_initiator_select_finish", "sc_initiator_cx_finish", "sc_initiator_mul_pack", "sc_keyholder_mul", "sc_initiator_mul_finish",
     "sc_topk_network", "sc_dot_layout", "sc_initiator_dot_pack", "sc_keyholder_dot", "sc_initiator_dot_finish",
+    "sc_onehot_prep", "sc_onehot_split", "sc_onehot_rotate", "sc_onehot_layout", "sc_initiator_onehot_pack", "sc_keyholder_onehot",
+    "sc_initiator_onehot_finish",
     "sc_rng_seed", "sc_rng_bits", "sc_rng_below", "sc_rng_coins", "sc_rng_permutations",
     "sc_peak_probe", "sc_mac_counter", "sc_table_traffic_probe", "sc_ctx_set_latency_mode", "sc_ctx_set_onelane_mode", "sc_ctx_set_chip_share", "sc_ctx_set_fork_mode", "sc_ctx_set_pair_policy", "sc_ctx_stats", "sc_ctx_launch_counts", "sc_ctx_policy", "sc_clock_probe", "sc_comm_unique_id", "sc_comm_init", "sc_allgather", "sc_comm_destroy",
 ]
@@ -126,6 +128,13 @@ def load() -> C.CDLL:
         "sc_initiator_dot_pack": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, u64]),
         "sc_keyholder_dot": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
         "sc_initiator_dot_finish": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, u64]),
+        "sc_onehot_prep": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, u64]),
+        "sc_onehot_split": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
+        "sc_onehot_rotate": (i32, [vp, i32, i32, i32, vp, vp, vp, u64]),
+        "sc_onehot_layout": (i32, [i32, i32, i32, i32, i32, ip]),
+        "sc_initiator_onehot_pack": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, u64]),
+        "sc_keyholder_onehot": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
+        "sc_initiator_onehot_finish": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
         "sc_rng_seed": (i32, [vp, vp]),
         "sc_rng_bits": (i32, [vp, i32, vp, u64]),
         "sc_rng_below": (i32, [vp, vp, i32, i32, vp, u64]),

@@ -1,6 +1,6 @@
-// Secure selection, multiplication and inner product: each family's layout rule on the host and the
-// plaintext-word halves of its two players (k_*_prep / k_*_split); the compare-exchange finish of a sort (§8c).  The scheme-level
-// entries of the three families (sc_schemes.h) check the same layouts before they launch anything.
+// Secure selection, multiplication, inner product and one-hot encoding: each family's layout rule on the
+// host and the plaintext-word halves of its two players (k_*_prep / k_*_split, the one-hot's k_onehot_rotate); the compare-exchange
+// finish of a sort (§8c).  The scheme-level entries of the four families (sc_schemes.h) check the same layouts before they launch anything.
 //
 // Included in the middle of sc_lib.hip, inside its extern "C" block (same translation unit: uses its context, program builder and
 // launch helpers).
@@ -162,6 +162,89 @@ int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx,
   if (count == 0) return SC_OK;
   if (launch_dot_split(ctx->stream, p, nw, lay, count, D, bad)) return fail(ctx, SC_ERR_HIP, "sc_dot_split: launch failed");
   return SC_OK;
+}
+
+// ---- secure one-hot encoding: the plaintext-word kernels of the two players (k_onehot_prep / _split / _rotate) ---------
+// OnehotLayout.__post_init__ (lookup.py) on the host -- the one copy of the fit rule every one-hot entry checks before it launches
+// anything: a field of f = ib + kappa + 1 bits must fit, f < bits(N) - 1; then g = floor((bits(N) - 2) / f) >= 1 fields per message.
+// Every refusal names its quantity.
+static int onehot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int ib, int k, int m, OnehotLayout* lay) {
+  if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
+  if (ib < 1 || ib > 32) return fail(ctx, SC_ERR_ARG, "%s: ib = %d: expected an index width of 1 .. 32 bits", who, ib);
+  if (k < 1 || k > ONEHOT_MAX_K) return fail(ctx, SC_ERR_ARG, "%s: k = %d: expected a table length of 1 .. %d", who, k, ONEHOT_MAX_K);
+  if (m < 1 || m > ONEHOT_MAX_M) return fail(ctx, SC_ERR_ARG, "%s: m = %d: expected 1 .. %d indices per row", who, m, ONEHOT_MAX_M);
+  lay->kappa = kappa; lay->ib = ib; lay->k = k; lay->m = m;
+  lay->f = ib + kappa + 1; lay->rw = (ib + kappa + 31) / 32;
+  if (lay->f >= nbits_n - 1)
+    return fail(ctx, SC_ERR_ARG, "%s: f = %d: one field does not fit below a %d-bit N (kappa = %d)", who, lay->f, nbits_n, kappa);
+  lay->g = std::max(1, (nbits_n - 2) / lay->f);
+  lay->M = (m + lay->g - 1) / lay->g;
+  return SC_OK;
+}
+// the launches number their rows in 32 bits
+static int onehot_rows(sc_ctx* ctx, const char* who, int k, int m, uint64_t count) {
+  if (count > (uint64_t)0x7fffffff / ((uint64_t)k * m))
+    return fail(ctx, SC_ERR_ARG, "%s: m k count = %d * %d * %llu rows: expected fewer than 2^31", who, m, k, (unsigned long long)count);
+  return SC_OK;
+}
+static int onehot_mask_words(sc_ctx* ctx, const char* who, const OnehotLayout& lay, int rw) {
+  if (rw < lay.rw) return fail(ctx, SC_ERR_ARG, "%s: draw rows of %d words are too narrow for %d bits", who, rw, lay.ib + lay.kappa);
+  if (rw > ONEHOT_FIELD_WORDS) return fail(ctx, SC_ERR_ARG, "%s: draw rows of %d words: expected at most %d", who, rw, ONEHOT_FIELD_WORDS);
+  return SC_OK;
+}
+
+int sc_onehot_layout(int nbits_n, int kappa, int ib, int k, int m, int* out) {
+  OnehotLayout lay;
+  if (!out) return SC_ERR_ARG;
+  int rc = onehot_layout(nullptr, "sc_onehot_layout", nbits_n, kappa, ib, k, m, &lay); if (rc) return rc;
+  out[0] = lay.f; out[1] = lay.g; out[2] = lay.M; out[3] = lay.rw;
+  return SC_OK;
+}
+
+int sc_onehot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* r, int rw, uint32_t* R,
+                   int32_t* rot, uint64_t count) {
+  if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_onehot_prep: bad argument");
+  OnehotLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = onehot_layout(ctx, "sc_onehot_prep", big_bits(n), kappa, ib, k, m, &lay); if (rc) return rc;
+  if (!r || !R || !rot) return fail(ctx, SC_ERR_ARG, "sc_onehot_prep: bad argument");
+  rc = onehot_mask_words(ctx, "sc_onehot_prep", lay, rw); if (rc) return rc;
+  rc = onehot_rows(ctx, "sc_onehot_prep", k, m, count); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  if (launch_onehot_prep(ctx->stream, r, rw, lay, nw, count, R, rot)) return fail(ctx, SC_ERR_HIP, "sc_onehot_prep: launch failed");
+  return SC_OK;
+}
+
+int sc_onehot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* p, uint32_t* prod,
+                    uint32_t* bad, uint64_t count) {
+  if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_onehot_split: bad argument");
+  OnehotLayout lay;
+  Big n(n_hptr, n_hptr + nw);
+  int rc = onehot_layout(ctx, "sc_onehot_split", big_bits(n), kappa, ib, k, m, &lay); if (rc) return rc;
+  if (!p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_onehot_split: bad argument");
+  rc = onehot_rows(ctx, "sc_onehot_split", k, m, count); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  if (launch_onehot_split(ctx->stream, p, nw, lay, count, prod, bad)) return fail(ctx, SC_ERR_HIP, "sc_onehot_split: launch failed");
+  return SC_OK;
+}
+
+// out [m][k][count][words] from e [m][k][count][words] and rot [m][count]; the two arrays must not overlap: a row of out is read from
+// another row of e
+static int onehot_rotate(sc_ctx* ctx, const char* who, int words, int k, int m, const uint32_t* e, const int32_t* rot, uint32_t* out, uint64_t count) {
+  const uint64_t total = (uint64_t)m * k * count * words;
+  if (out < e + total && e < out + total) return fail(ctx, SC_ERR_ARG, "%s: out overlaps e: the rotation is not done in place", who);
+  if (count == 0) return SC_OK;
+  if (launch_onehot_rotate(ctx->stream, e, rot, k, m, words, count, out)) return fail(ctx, SC_ERR_HIP, "%s: launch failed", who);
+  return SC_OK;
+}
+
+int sc_onehot_rotate(sc_ctx* ctx, int words, int k, int m, const uint32_t* e, const int32_t* rot, uint32_t* out, uint64_t count) {
+  if (!ctx || words < 1) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: bad argument");
+  if (k < 1 || k > ONEHOT_MAX_K) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: k = %d: expected a table length of 1 .. %d", k, ONEHOT_MAX_K);
+  if (m < 1 || m > ONEHOT_MAX_M) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: m = %d: expected 1 .. %d indices per row", m, ONEHOT_MAX_M);
+  if (!e || !rot || !out) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: bad argument");
+  int rc = onehot_rows(ctx, "sc_onehot_rotate", k, m, count); if (rc) return rc;
+  return onehot_rotate(ctx, "sc_onehot_rotate", words, k, m, e, rot, out, count);
 }
 
 // ---- compare-exchange finish of a secure sort: both outputs of every column from one shared inversion ----------

@@ -1,7 +1,7 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
 // (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
-// units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel) and
-// sc_launch_misc.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
+// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip and sc_launch_lookup.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -280,6 +280,10 @@ int launch_mul_split(hipStream_t stream, const uint32_t* p, int nw, const sc::Mu
 int launch_dot_prep(hipStream_t stream, const uint32_t* ra, int aw, const uint32_t* rb, int bw, const sc::DotLayout& lay, int nw, int ew,
                     uint64_t count, uint32_t* e, uint32_t* R, uint32_t* S);
 int launch_dot_split(hipStream_t stream, const uint32_t* p, int nw, const sc::DotLayout& lay, uint64_t count, uint32_t* D, uint32_t* bad);
+// sc_launch_lookup.hip
+int launch_onehot_prep(hipStream_t stream, const uint32_t* r, int rw, const sc::OnehotLayout& lay, int nw, uint64_t count, uint32_t* R, int32_t* rot);
+int launch_onehot_split(hipStream_t stream, const uint32_t* p, int nw, const sc::OnehotLayout& lay, uint64_t count, uint32_t* prod, uint32_t* bad);
+int launch_onehot_rotate(hipStream_t stream, const uint32_t* E, const int32_t* rot, int k, int m, int w2, uint64_t count, uint32_t* out);
 // sc_launch_misc.hip again
 int launch_rng_bits(hipStream_t stream, const sc::RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count);
 int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, const uint32_t* d_n, int nbits, int nw, int nonzero, uint32_t* out, uint64_t count);

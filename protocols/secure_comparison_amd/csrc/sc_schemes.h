@@ -708,8 +708,9 @@ int sc_initiator_step67(sc_ctx* ctx, int paillier_key_id, const uint64_t* delta_
 // What selection.py / sorting.py used to compose from the primitives, one call per protocol step: the field layout, the Horner chain
 // of shared-exponent squarings, T_j with per-row exponents (pair kernel, or exponentiations modulo N^2 where the modulus has no
 // per-row pair instance), and the two finishes.  Temporaries TMP_SEL_*; the callees' own (TMP_S_A .. TMP_S_D, TMP_PAIR) are not held
-// across their calls.  The selection, the multiplication (§8e) and the inner product (§8g) share one blinded round trip (DESIGN.md
-// §8h): blind_and_randomize and horner_pow2 pack, keyholder_round is the key holder's step, finish_ratio divides the blinding out.
+// across their calls.  The selection, the multiplication (§8e), the inner product (§8g) and the one-hot encoding (§8i) share one blinded
+// round trip: blind_and_randomize and horner_pow2 pack, keyholder_round is the key holder's step, finish_ratio divides
+// the blinding out (the one-hot has nothing to divide out: its finish is a rotation of rows).
 enum SelectTmp { TMP_SEL_A = 49, TMP_SEL_B, TMP_SEL_C, TMP_SEL_D, TMP_SEL_E, TMP_SEL_F };
 
 // one pinned, device-visible word per context for keyholder_round's verdict (freed with the context's other allocations)
@@ -798,7 +799,7 @@ static int sel_finish_args(sc_ctx* ctx, const char* who, const PaillierKey* kp, 
 }
 
 // ---- the blinded round trip the selection, the multiplication and the inner product share ----------------------------
-// dst = [[x + R]] rho^N over `items` rows (x, dst [items][2 nw], R [items][nw]): the packing program of all three families
+// dst = [[x + R]] rho^N over `items` rows (x, dst [items][2 nw], R [items][nw]): the packing program of all four families
 static int blind_and_randomize(sc_ctx* ctx, const PaillierKey& k, int key_id, const uint32_t* x, const uint32_t* R, const uint32_t* rho, uint32_t* dst,
                                uint64_t items) {
   const int w2 = 2 * k.nw;
@@ -1220,6 +1221,92 @@ int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   }
   if (rc) return rc;
   return finish_ratio(ctx, k, coef, d_enc, T, base, out, count, inv);
+}
+
+// ---- secure one-hot encoding -------------------------------------------------------------------------------------------
+// Blind, decrypt, rotate: P carries the fields d_q = i_q + r_q, the key holder returns the k fresh encryptions [[ [t == d_q mod k] ]] of
+// every index, and since d_q mod k = (i_q + r_q) mod k the initiator reads row (t + r_q mod k) mod k as row t -- no arithmetic modulo N^2
+// after the key holder's answer.  Index q lives in message q div g at position q mod g, so the planes of one position are NOT contiguous
+// in index_enc [m][count][2 nw] once a row takes more than one message: they are gathered position by position (TMP_SEL_D) before the
+// Horner chain, which then runs as the inner product's.  Same temporaries as the selection's.
+int sc_initiator_onehot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int ib, int kk, int m, const uint32_t* index_enc, const uint32_t* r,
+                             int rw, const uint32_t* rho_p, uint32_t* p_out, int32_t* rot_out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: bad key");
+  const PaillierKey k = *kp;
+  OnehotLayout lay;
+  int rc = onehot_layout(ctx, "sc_initiator_onehot_pack", big_bits(k.n), kappa, ib, kk, m, &lay); if (rc) return rc;
+  if (!index_enc) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: index_enc: missing array");
+  if (!r) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: r: missing array");
+  rc = onehot_mask_words(ctx, "sc_initiator_onehot_pack", lay, rw); if (rc) return rc;
+  if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: rho_p is required: every P must carry a fresh rho^N");
+  if (!p_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: p_out: missing array");
+  if (!rot_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: rot_out: missing array");
+  rc = onehot_rows(ctx, "sc_initiator_onehot_pack", kk, m, count); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  const int w2 = 2 * k.nw, M = lay.M, g = lay.g;
+  const size_t col = (size_t)count * w2;               // one plane
+  const uint64_t items = (uint64_t)M * count;          // the messages
+  const int F = M > 1 ? g : m;                         // positions in use
+  const int n_last = m - (M - 1) * g;                  // fields of the last message: positions >= n_last are held by M - 1 messages
+  uint32_t *R, *msg, *acc, *gat = nullptr;
+  rc = tmp_words(ctx, TMP_SEL_A, items * k.nw, &R); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_B, items * w2, &msg); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, 2 * items * w2, &acc); if (rc) return rc;
+  if (launch_onehot_prep(ctx->stream, r, rw, lay, k.nw, count, R, rot_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_onehot_pack: launch failed");
+  auto held = [&](int pos) { return (uint64_t)(pos < n_last ? M : M - 1) * count; };
+  std::vector<const uint32_t*> rows(F);
+  if (M == 1) {
+    for (int pos = 0; pos < F; pos++) rows[pos] = index_enc + (size_t)pos * col;
+  } else {
+    rc = tmp_words(ctx, TMP_SEL_D, (uint64_t)m * col, &gat); if (rc) return rc;
+    uint32_t* dst = gat;
+    for (int pos = 0; pos < F; pos++) {
+      rows[pos] = dst;
+      for (int mm = 0; (uint64_t)mm * count < held(pos); mm++, dst += col)
+        HIPCHK(ctx, hipMemcpyAsync(dst, index_enc + (size_t)(mm * g + pos) * col, col * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+  }
+  // position 0 -- held by every message -- is folded into [[i + R]] rho_p^N; Horner from the top position: cur^(2^f) times the next one
+  // down; the last message joins below its own top position as a copy of its field
+  uint32_t* m_dst = F == 1 ? p_out : msg;
+  rc = blind_and_randomize(ctx, k, paillier_key_id, rows[0], R, rho_p, m_dst, items); if (rc) return rc;
+  if (F == 1) return SC_OK;
+  std::vector<HornerField> fld(F);
+  for (int pos = F - 1; pos >= 1; pos--) fld[F - 1 - pos] = {rows[pos], lay.f, held(pos)};
+  fld[F - 1] = {msg, 0, items};
+  uint32_t* const half[2] = {acc + items * w2, acc};
+  return horner_pow2(ctx, k, fld.data(), F - 1, half, p_out);
+}
+
+int sc_keyholder_onehot(sc_ctx* ctx, int paillier_key_id, int kappa, int ib, int kk, int m, const uint32_t* p_enc, const uint32_t* rho_e,
+                        uint32_t* e_out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !kp->secret) return fail(ctx, SC_ERR_ARG, "sc_keyholder_onehot: needs the secret key");
+  const PaillierKey k = *kp;
+  OnehotLayout lay;
+  int rc = onehot_layout(ctx, "sc_keyholder_onehot", big_bits(k.n), kappa, ib, kk, m, &lay); if (rc) return rc;
+  if (!p_enc) return fail(ctx, SC_ERR_ARG, "sc_keyholder_onehot: p_enc: missing array");
+  if (!rho_e) return fail(ctx, SC_ERR_ARG, "sc_keyholder_onehot: rho_e: missing array");
+  if (!e_out) return fail(ctx, SC_ERR_ARG, "sc_keyholder_onehot: e_out: missing array");
+  rc = onehot_rows(ctx, "sc_keyholder_onehot", kk, m, count); if (rc) return rc;
+  if (count == 0) return SC_OK;
+  return keyholder_round(ctx, "sc_keyholder_onehot", k, paillier_key_id, p_enc, rho_e, e_out, (uint64_t)lay.M * count, (uint64_t)m * kk * count,
+                         [&](const uint32_t* pl, uint32_t* prod, uint32_t* bad) { return launch_onehot_split(ctx->stream, pl, k.nw, lay, count, prod, bad); },
+                         "onehot: a decrypted P exceeds the end of its message in the announced layout (kappa, ib or m differ between the players)");
+}
+
+int sc_initiator_onehot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int ib, int kk, int m, const uint32_t* e_enc, const int32_t* rot,
+                               uint32_t* out, uint64_t count) {
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_finish: bad key");
+  OnehotLayout lay;
+  int rc = onehot_layout(ctx, "sc_initiator_onehot_finish", big_bits(kp->n), kappa, ib, kk, m, &lay); if (rc) return rc;
+  if (!e_enc) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_finish: e_enc: missing array");
+  if (!rot) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_finish: rot: missing array");
+  if (!out) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_finish: out: missing array");
+  rc = onehot_rows(ctx, "sc_initiator_onehot_finish", kk, m, count); if (rc) return rc;
+  return onehot_rotate(ctx, "sc_initiator_onehot_finish", 2 * kp->nw, kk, m, e_enc, rot, out, count);
 }
 
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {

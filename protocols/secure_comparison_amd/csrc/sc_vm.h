@@ -104,6 +104,17 @@ struct DotLayout {
   int wx, wy, is_signed, square;
 };
 
+// Layout of a secure one-hot's packed plaintexts (k_onehot_prep / k_onehot_split, sc_kernel_plain.h): m indices per row,
+// every one a field d_q = i_q + r_q of f = ib + kappa + 1 bits, g of them per message at the bit offsets 0, f, 2f, .., M = ceil(m / g)
+// messages per row; index q lives in message q div g at position q mod g, so only the last message may hold fewer than g fields.
+constexpr int ONEHOT_MAX_K = 1024;
+constexpr int ONEHOT_MAX_M = 65536;
+constexpr int ONEHOT_FIELD_WORDS = 3;    // a field has at most 32 + 62 + 1 = 95 bits
+struct OnehotLayout {
+  int f, g, M, rw;                       // rw = ceil((ib + kappa) / 32): the words of a mask
+  int kappa, ib, k, m;
+};
+
 constexpr int VM_MAX_EXT = 8;
 constexpr int VM_MAX_CONST = 8;  // including R^2 and R
 

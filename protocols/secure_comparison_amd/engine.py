@@ -99,6 +99,14 @@ def dot_layout(lib, nbits: int, kappa: int, wx: int, wy: int, signed: bool, squa
     return tuple(out)
 
 
+def onehot_layout(lib, nbits: int, kappa: int, ib: int, k: int, m: int) -> tuple:
+    """(f, g, M, rw) from sc_onehot_layout -- host code only, so it needs no context and no GPU.  ValueError on a refusal."""
+    out = (C.c_int * 4)()
+    if lib.sc_onehot_layout(int(nbits), int(kappa), int(ib), int(k), int(m), out) != 0:
+        raise ValueError(f"sc_onehot_layout refuses (nbits, kappa, ib, k, m) = {(nbits, kappa, ib, k, m)}")
+    return tuple(out)
+
+
 class Engine:
     """One library context (sc_ctx): one per process and device, or one per concurrent shard / session thread of a device.
     Tensors are int32 views of uint32 words, shape [count, nwords].  An engine belongs to ONE host thread at a time: it orders its
@@ -1152,6 +1160,66 @@ class Engine:
         self._check(self.lib.sc_initiator_dot_finish(self.ctx, key.id, int(kappa), int(wx), int(wy), int(bool(square)), int(k), self._ptr(x_enc),
                                                      self._ptr(None if square else y_enc), self._ptr(d_enc), self._ptr(e), e.shape[-1],
                                                      self._ptr(S), self._ptr(base), int(coef), self._ptr(out), count))
+        return out
+
+    # ------------------------------------------------------------------ secure one-hot encoding (one library call each)
+    def _onehot_planes(self, t: torch.Tensor, name: str, lead: tuple[int, ...], words: int | None, dtype=torch.int32) -> int:
+        """`t` is [*lead][count][words] (or [*lead][count] when words is None); returns count."""
+        dims = len(lead) + (1 if words is None else 2)
+        if not isinstance(t, torch.Tensor) or t.dim() != dims or tuple(t.shape[:len(lead)]) != tuple(lead):
+            shape = "".join(f"[{d}]" for d in lead) + "[count]" + ("" if words is None else "[words]")
+            raise ValueError(f"{name}: expected {shape}")
+        count = t.shape[len(lead)]
+        rows = count
+        for d in lead:
+            rows *= d
+        self._arr(t, name, rows if words is not None else None, words, dtype=dtype)
+        return count
+
+    def initiator_onehot_pack(self, key: PaillierKey, kappa: int, ib: int, k: int, m: int, M: int, index_enc: torch.Tensor, r: torch.Tensor,
+                              rho_p: torch.Tensor | None):
+        """The messages P [M][count][2nw] and the rotations rot [m][count] (int32, r mod k) from [[i_q]] [m][count][2nw] and the masks
+        r [m][count][rw] (sc_initiator_onehot_pack).  A missing rho_p is the library's ValueError."""
+        nw = key.mod_n.nwords
+        count = self._onehot_planes(index_enc, "index_enc", (m,), 2 * nw)
+        self._columns(r, "r", m, count, None)
+        if rho_p is not None and self._onehot_planes(rho_p, "rho_p", (M,), nw) != count:
+            raise ValueError(f"rho_p: expected [{M}][{count}][{nw}]")
+        P = torch.empty((M, count, 2 * nw), dtype=torch.int32, device=self.device)
+        rot = torch.empty((m, count), dtype=torch.int32, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_onehot_pack(self.ctx, key.id, int(kappa), int(ib), int(k), int(m), self._ptr(index_enc), self._ptr(r),
+                                                      r.shape[-1], self._ptr(rho_p), self._ptr(P), self._ptr(rot), count))
+        return P, rot
+
+    def keyholder_onehot(self, key: PaillierKey, kappa: int, ib: int, k: int, m: int, M: int, P: torch.Tensor, rho_e: torch.Tensor) -> torch.Tensor:
+        """The key holder's randomized E [m][k][count][2nw], E[q][t] = [[ [t == d_q mod k] ]], from P [M][count][2nw] and the bases
+        rho_e [m][k][count][nw] (sc_keyholder_onehot); ValueError when a decrypted message exceeds its end in the layout."""
+        nw = key.mod_n.nwords
+        count = self._onehot_planes(P, "P", (M,), 2 * nw)
+        if self._onehot_planes(rho_e, "rho_e", (m, k), nw) != count:
+            raise ValueError(f"rho_e: expected [{m}][{k}][{count}][{nw}]")
+        E = torch.empty((m, k, count, 2 * nw), dtype=torch.int32, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_keyholder_onehot(self.ctx, key.id, int(kappa), int(ib), int(k), int(m), self._ptr(P), self._ptr(rho_e),
+                                                 self._ptr(E), count))
+        return E
+
+    def initiator_onehot_finish(self, key: PaillierKey, kappa: int, ib: int, k: int, m: int, E: torch.Tensor, rot: torch.Tensor,
+                                out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[q][t][b] = E[q][(t + rot[q][b]) mod k][b], [m][k][count][2nw] (sc_initiator_onehot_finish).  `out` (optional) must not
+        overlap E: the library's ValueError."""
+        nw = key.mod_n.nwords
+        count = self._onehot_planes(E, "E", (m, k), 2 * nw)
+        if self._onehot_planes(rot, "rot", (m,), None) != count:
+            raise ValueError(f"rot: expected [{m}][{count}]")
+        if out is None:
+            out = torch.empty_like(E)
+        elif self._onehot_planes(out, "out", (m, k), 2 * nw) != count:
+            raise ValueError(f"out: expected [{m}][{k}][{count}][{2 * nw}]")
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_onehot_finish(self.ctx, key.id, int(kappa), int(ib), int(k), int(m), self._ptr(E), self._ptr(rot),
+                                                        self._ptr(out), count))
         return out
 
     # ------------------------------------------------------------------ device-side CSPRNG (sc_rng_*)

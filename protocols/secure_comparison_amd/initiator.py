@@ -474,6 +474,25 @@ class Initiator:
 
         return await alice_dot(self, x_enc, y_enc, x_bits, y_bits, signed, square, kappa, draws, source, engine, generator, chunks)
 
+    # ---- secure one-hot encoding and table lookup (lookup.py)
+    async def perform_secure_onehot_batch(self, index_enc: torch.Tensor, k: int, index_bits: int | None = None, kappa: int = 40, draws=None,
+                                          source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[ [t == i mod k] ]] [k][B][2nw] from index_enc [B][2nw] (or [m][k][B][2nw] from [m][B][2nw]) as lookup.secure_onehot_batch:
+        `onehot_1_batch_{tag}` carries an int32 header (kappa, ib, k, m) and the messages P [M][B][2nw], `onehot_2_batch_{tag}` the key
+        holder's E [m][k][B][2nw].  chunks > 1 is not supported (ValueError)."""
+        from .lookup import alice_onehot
+
+        return await alice_onehot(self, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks)
+
+    async def perform_secure_gather_batch(self, table_enc: torch.Tensor, index_enc: torch.Tensor, bits: int, signed: bool = False,
+                                          kappa: int = 40, index_bits: int | None = None, source: str = "device", engine=None, generator=None,
+                                          chunks: int = 1) -> torch.Tensor:
+        """[[table[i_q]]] [m][B][2nw] from table_enc [k][B][2nw] and index_enc [m][B][2nw] as lookup.secure_gather_batch: a one-hot
+        session, then an inner-product session over m B rows (two round trips).  chunks > 1 is not supported (ValueError)."""
+        from .lookup import alice_gather
+
+        return await alice_gather(self, table_enc, index_enc, bits, signed, kappa, index_bits, source, engine, generator, chunks)
+
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""
         if self.communicator is None:

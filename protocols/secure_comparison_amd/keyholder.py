@@ -345,6 +345,24 @@ class KeyHolder:
 
         await bob_dot(self, k, x_bits, y_bits, signed, square, kappa, draws, source, generator, count)
 
+    # ---- secure one-hot encoding and table lookup (lookup.py)
+    async def perform_secure_onehot_batch(self, k: int, m: int = 1, index_bits: int | None = None, kappa: int = 40, draws=None,
+                                          source: str = "device", generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_onehot_batch for m indices per row against a table of k entries: the initiator's header
+        must announce this kappa, index width, k and m (ValueError before anything is decrypted); `count` (optional) is the batch size
+        he expects."""
+        from .lookup import bob_onehot
+
+        await bob_onehot(self, k, m, index_bits, kappa, draws, source, generator, count)
+
+    async def perform_secure_gather_batch(self, k: int, m: int, bits: int, signed: bool = False, kappa: int = 40,
+                                          index_bits: int | None = None, source: str = "device", generator=None,
+                                          count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_gather_batch: the one-hot session, then the inner-product session over m count rows."""
+        from .lookup import bob_gather
+
+        await bob_gather(self, k, m, bits, signed, kappa, index_bits, source, generator, count)
+
     async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
         message when it has been received already.  Returns the session's batch size."""
