@@ -26,6 +26,10 @@ int sc_ctx_set_latency_mode(sc_ctx* ctx, int mode);
  * both forms' rounds of resident waves says is faster for this batch size, with the per-round times MEASURED on this device
  * (sc_ctx_policy); 2: whenever the modulus fits (tests).  Results are the same canonical residues in every mode. */
 int sc_ctx_set_onelane_mode(sc_ctx* ctx, int mode);
+/* Chunk length of sc_modprod_axis' tree.  0 (default): automatic -- the shortest chains of at least 4 and at most 32 members that still
+ * fill the chip's resident group slots at each level; 2 .. 32: that length at every level (tests reach deep trees at small K this
+ * way).  Results are the same canonical residues whatever the setting. */
+int sc_ctx_set_reduce_chunk(sc_ctx* ctx, int c);
 /* Tell the context that `contexts` library contexts (this one included) work on its GPU at the same time -- the concurrent
  * shards of one batch, each on its own stream.  Batch-size policies then count rounds of 1/contexts of the chip (a launch that
  * under-fills the whole chip is not alone on it).  Default 1. */
@@ -55,7 +59,8 @@ int sc_ctx_stats(sc_ctx* ctx, uint64_t* out, int n);
  * calibration launches of the automatic policies count like any other).  Up to `cap` (key, count) entries in ascending key order go
  * to keys_out / counts_out (either may be NULL with cap 0); *n_out = the number of instances launched so far, which may exceed
  * `cap`.  The key names the template instance:
- *   bits 0..7 L, bits 8..15 G, bits 16..23 W (limb bits), bit 24 NEG1, bit 25 STAMP, bit 26 DIG, bit 27 kind (0 k_vm, 1 k_pvm);
+ *   bits 0..7 L, bits 8..15 G, bits 16..23 W (limb bits), bit 24 NEG1, bit 25 STAMP, bit 26 DIG, bit 27 kind (0 k_vm, 1 k_pvm),
+ *   bit 28 k_prod_axis (sc_modprod_axis; bits 24..27 zero);
  * STAMP and DIG are always 0 for k_vm.  For tests and tools: which instance a call landed on is host policy no result shows. */
 int sc_ctx_launch_counts(sc_ctx* ctx, uint32_t* keys_out, uint64_t* counts_out, int cap, int* n_out);
 /* The constants behind the automatic policies, measured once per device and process when the first secret key is created (about
@@ -155,6 +160,20 @@ int sc_modexp_var_scatter(sc_ctx* ctx, int mod, const uint32_t* x_dptr, const ui
  * ("operand i is not reduced modulo n", *bad_index = i), never SC_ERR_NOT_INVERTIBLE. */
 int sc_modinv(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint32_t* out_dptr, uint64_t count,
               int64_t* bad_index);
+/* The product along one axis: x viewed as [outer][K][inner][nwords] canonical residues, out[o][i] = prod_{j < K} x[o][j][i] mod n,
+ * [outer][inner][nwords] canonical.  A tree of launches of the dedicated kernel k_prod_axis on the context's stream, one per level:
+ * a chain of at most 32 members per group of lanes and exactly one Montgomery product acc * x / R per member after the first -- no
+ * operand is converted, no product reduced on its own, partials travel in limb form, lazily reduced.  Each product leaves a factor
+ * 1 / R behind, K - 1 of them whatever the shape of the tree, and the last level's product with the constant R^K mod n (built on the
+ * host once per modulus and K and copied on the context's stream from a pinned buffer) removes them: the shape of the tree does not
+ * change the result.  Asynchronous, no host round trip.  K = 1 is a
+ * canonical copy.  Operands must be canonical (below n): the kernel does not check them, and an unreduced operand gives an unspecified
+ * residue (sc_modinv, whose kernel sees every operand anyway, reports one; this call would need a pass of its own).  A context keeps
+ * the closing factors of the last 64 (modulus, K) pairs.  Checked before anything is launched or allocated (SC_ERR_ARG): null pointers, K >= 1,
+ * outer * K * inner * nwords <= 2^40 words, `out` must not overlap `x`; an empty outer or inner is SC_OK.  The modulus runs in its own
+ * configuration; one without an instance (one-lane (1,18), 28-bit limbs, modulus multiples) is SC_ERR_ARG and the message names the
+ * configuration.  Launches are counted in sc_ctx_launch_counts under the key  L | G << 8 | 29 << 16 | 1 << 28. */
+int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out_dptr);
 
 /* ---- Paillier pieces that are not plain residue products --------------------------------------- */
 /* out[i] = 1 + m[i] * N mod N^2 (g = N+1 encryption without randomness: unsafe_encrypt(..) of

@@ -1,7 +1,7 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
 // (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
-// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip and sc_launch_lookup.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip and sc_launch_reduce.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -233,6 +233,9 @@ struct sc_ctx {
   std::mutex rng_seed_mutex;                                // the lazy first seeding happens once
   uint64_t* stamps = nullptr;                               // sc_clock_probe: the next (4,18,neg1) pair launch runs its stamping twin
   uint32_t stamp_grid = 0;                                  // ... and reports its grid size here
+  int reduce_chunk = 0;                                     // sc_ctx_set_reduce_chunk: 0 automatic, 2 .. 32 the chunk length of every level
+  // (mod, K) -> limbs of R^K mod n, sc_modprod_axis' closing factor: the device copy and the pinned host buffer it is filled from (bounded)
+  std::map<std::pair<int, uint64_t>, std::pair<uint32_t*, uint32_t*>> reduce_consts;
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sc_host::fail(ctx, SC_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
@@ -247,6 +250,8 @@ constexpr uint32_t launch_key(bool pvm, int G, int L, int W, bool neg1, bool sta
   return (uint32_t)L | ((uint32_t)G << 8) | ((uint32_t)W << 16) | (neg1 ? 1u << 24 : 0u) | (stamp ? 1u << 25 : 0u) | (dig ? 1u << 26 : 0u) |
          (pvm ? 1u << 27 : 0u);
 }
+// the key of a k_prod_axis instance there: bit 28 set, L, G and W where the interpreters have them
+constexpr uint32_t reduce_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 28); }
 // sc_launch_vm.hip / sc_launch_pvm.hip, parts 0 .. 2: launch the instance (G, L, W, NEG1[, STAMP]) of the interpreter on the context's
 // stream (grid, scratch arena and occupancy handled there); SC_ERR_UNSUPPORTED when the instance lives in another part
 int launch_vm_part0(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);
@@ -284,6 +289,10 @@ int launch_dot_split(hipStream_t stream, const uint32_t* p, int nw, const sc::Do
 int launch_onehot_prep(hipStream_t stream, const uint32_t* r, int rw, const sc::OnehotLayout& lay, int nw, uint64_t count, uint32_t* R, int32_t* rot);
 int launch_onehot_split(hipStream_t stream, const uint32_t* p, int nw, const sc::OnehotLayout& lay, uint64_t count, uint32_t* prod, uint32_t* bad);
 int launch_onehot_rotate(hipStream_t stream, const uint32_t* E, const int32_t* rot, int k, int m, int w2, uint64_t count, uint32_t* out);
+// sc_launch_reduce.hip: one level of the product along an axis (k_prod_axis) on the context's stream; SC_ERR_UNSUPPORTED when
+// (G, L, W) has no instance
+int launch_prod_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* fin, const uint32_t* src, uint32_t* dst, uint64_t K,
+                     uint64_t inner, uint32_t chunk, uint64_t nch, uint64_t nchains, int nwords, bool in_words, bool final);
 // sc_launch_misc.hip again
 int launch_rng_bits(hipStream_t stream, const sc::RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count);
 int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, const uint32_t* d_n, int nbits, int nw, int nonzero, uint32_t* out, uint64_t count);

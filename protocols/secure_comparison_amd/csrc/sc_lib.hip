@@ -167,7 +167,7 @@ inline bool small_enough_to_fork(const sc_ctx* ctx, const Mod& m, uint64_t count
   return (count + per_wave - 1) / per_wave <= (uint64_t)ctx->num_cu * 4 / (uint64_t)ctx->chip_share;
 }
 
-enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
+enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_REDUCE = 6, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
 
 // A u64 accumulator array of the context that is ZERO whenever no step is using it: cleared when it is (re)allocated, reset by its
 // reader afterwards (OP_TAKEFLAG).  The zero tests of step 4j OR their verdicts into it; no clearing launch inside a step.
@@ -603,6 +603,7 @@ void sc_ctx_destroy(sc_ctx* ctx) {
   if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
   if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
   for (auto& kv : ctx->tmp) if (kv.second.first) (void)hipFree(kv.second.first);
+  for (auto& kv : ctx->reduce_consts) { (void)hipFree(kv.second.first); (void)hipHostFree(kv.second.second); }
   for (int* h : ctx->status_host) if (h) (void)hipHostFree(h);
   if (ctx->switch_event) (void)hipEventDestroy(ctx->switch_event);
   if (ctx->comm) (void)sc_comm_destroy(ctx);
@@ -1224,6 +1225,121 @@ int sc_modinv(sc_ctx* ctx, int mod, const uint32_t* x, uint32_t* out, uint64_t c
   if (bad_index) *bad_index = bad;
   ctx->last_bad_index = bad;
   return fail(ctx, SC_ERR_NOT_INVERTIBLE, "element %lld is not invertible", (long long)bad);
+}
+
+// ------------------------------------------------------------------------------------------------
+// product along an axis: a tree of k_prod_axis levels (sc_launch_reduce.hip)
+// ------------------------------------------------------------------------------------------------
+// One level: K members per output in chains of `chunk` (the last one of an output may be shorter), nch = ceil(K / chunk) partials.
+struct ReduceLevel { uint64_t K; uint32_t chunk; uint64_t nch; };
+// Chunk length as in modinv_rec: a chain is sequential, so a level's latency is its chunk length while the tree's work (one product
+// per member, plus one per partial) hardly depends on it.  The shortest chunks of at least 4 and at most 32 members that still fill
+// every resident group slot of the chip at this level; `forced` (sc_ctx_set_reduce_chunk) overrides that at every level.  A level
+// never cuts finer than its K.  protocols/secure_comparison_amd/aggregate.py::reduce_plan mirrors this for the tests.
+static std::vector<ReduceLevel> reduce_plan(uint64_t outer, uint64_t K, uint64_t inner, uint64_t resident_groups, int forced) {
+  std::vector<ReduceLevel> lv;
+  for (;;) {
+    const uint64_t total = outer * K * inner;
+    uint64_t c = forced ? (uint64_t)forced : std::min<uint64_t>(32, std::max<uint64_t>(4, (total + resident_groups - 1) / resident_groups));
+    c = std::min(c, K);
+    const uint64_t nch = (K + c - 1) / c;
+    lv.push_back(ReduceLevel{K, (uint32_t)c, nch});
+    if (nch == 1) return lv;
+    K = nch;
+  }
+}
+
+// The closing factor of a reduction over K members: the limbs of R^K mod n, by square and multiply on the host, once per (modulus, K).
+// It reaches the device by a copy on the context's stream out of a pinned host buffer that lives as long as the entry, so the call
+// does not wait for the stream.  The context keeps at most REDUCE_CONSTS_MAX of them: a caller who sums over ever new K does not grow
+// device memory; only when the table is full does a call wait for the stream, to free it and start again.
+static const size_t REDUCE_CONSTS_MAX = 64;
+static void free_reduce_consts(sc_ctx* ctx) {
+  for (auto& kv : ctx->reduce_consts) { (void)hipFree(kv.second.first); (void)hipHostFree(kv.second.second); }
+  ctx->reduce_consts.clear();
+}
+static int reduce_closing_const(sc_ctx* ctx, int mod, uint64_t K, const uint32_t** out_limbs) {
+  auto it = ctx->reduce_consts.find({mod, K});
+  if (it == ctx->reduce_consts.end()) {
+    const Mod& m = ctx->mods[mod];
+    auto mulmod = [&](const Big& a, const Big& b) { Big q, r; big_divmod(big_mul(a, b), m.n, &q, &r); return r; };
+    Big one(m.nwords, 0); one[0] = 1;
+    Big base = big_shl_mod(one, m.n, m.W * m.S), v = one;
+    for (uint64_t e = K; e; e >>= 1) {
+      if (e & 1) v = mulmod(v, base);
+      if (e > 1) base = mulmod(base, base);
+    }
+    const std::vector<uint32_t> limbs = to_limbs(v, m.S, m.W);
+    const size_t bytes = limbs.size() * 4;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->reduce_consts.size() >= REDUCE_CONSTS_MAX) {
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      free_reduce_consts(ctx);
+    }
+    uint32_t *d = nullptr, *h = nullptr;
+    HIPCHK(ctx, hipMalloc((void**)&d, bytes));
+    if (hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipFree(d); return fail(ctx, SC_ERR_HIP, "sc_modprod_axis: hipHostMalloc failed"); }
+    memcpy(h, limbs.data(), bytes);
+    it = ctx->reduce_consts.emplace(std::make_pair(mod, K), std::make_pair(d, h)).first;
+    HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  *out_limbs = it->second.first;
+  return SC_OK;
+}
+
+int sc_ctx_set_reduce_chunk(sc_ctx* ctx, int c) {
+  if (!ctx || (c != 0 && (c < 2 || c > 32))) return SC_ERR_ARG;
+  ctx->reduce_chunk = c;
+  return SC_OK;
+}
+
+int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out) {
+  if (!valid_mod(ctx, mod) || !x || !out) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: bad argument");
+  if (K < 1) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: K must be at least 1");
+  const Mod& m = ctx->mods[mod];
+  {
+    // outer * K * inner * nwords <= 2^40 words, checked factor by factor so that no product wraps
+    const uint64_t LIM = 1ull << 40;
+    uint64_t words = (uint64_t)m.nwords;
+    for (uint64_t f : {K, outer, inner}) {
+      if (f != 0 && words > LIM / f) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: outer * K * inner * nwords exceeds 2^40 words");
+      words *= f;
+    }
+  }
+  if (outer == 0 || inner == 0) return SC_OK;
+  {
+    const size_t xbytes = (size_t)outer * K * inner * m.nwords * 4, obytes = (size_t)outer * inner * m.nwords * 4;
+    const char *xb = (const char*)x, *ob = (const char*)out;
+    if (xb < ob + obytes && ob < xb + xbytes) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: out overlaps x (in-place reduction is not supported)");
+  }
+  if (m.W != 29 || m.G < 2 || m.small_c != 0)
+    return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: no k_prod_axis instance for configuration (G=%d, L=%d, W=%d%s)", m.G, m.L, m.W, m.small_c ? ", NEG1" : "");
+  const std::vector<ReduceLevel> plan = reduce_plan(outer, K, inner, (uint64_t)ctx->num_cu * 8 * (64 / m.G), ctx->reduce_chunk);
+  // partials: level v writes outer * nch_v * inner numbers in limb form; levels alternate between the two halves of one temporary
+  // (sizes shrink from level to level, so the first two decide)
+  uint32_t* half[2] = {nullptr, nullptr};
+  if (plan.size() > 1) {
+    const size_t n0 = (size_t)outer * plan[0].nch * inner, n1 = plan.size() > 2 ? (size_t)outer * plan[1].nch * inner : 0;
+    int rc = tmp_buf(ctx, TMP_REDUCE, (n0 + n1) * m.S * 4, (void**)&half[0]); if (rc) return rc;
+    half[1] = half[0] + n0 * m.S;
+  }
+  const uint32_t* fin = nullptr;
+  { int rc = reduce_closing_const(ctx, mod, K, &fin); if (rc) return rc; }
+  const uint32_t* src = x;
+  for (size_t v = 0; v < plan.size(); v++) {
+    const ReduceLevel& lv = plan[v];
+    const bool final = v + 1 == plan.size();
+    uint32_t* dst = final ? out : half[v & 1];
+    int rc = launch_prod_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, fin, src, dst, lv.K, inner, lv.chunk, lv.nch, outer * lv.nch * inner, m.nwords,
+                              v == 0, final);
+    if (rc == SC_ERR_UNSUPPORTED)
+      return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: no k_prod_axis instance for configuration (G=%d, L=%d, W=%d)", m.G, m.L, m.W);
+    if (rc) return rc;
+    // one product per member past the first of a chain; the last level's product with the closing factor
+    ctx->mac_counter += (double)m.S * m.S * 2.0 * (double)outer * (double)inner * ((double)(lv.K - lv.nch) + (final ? 1.0 : 0.0));
+    src = dst;
+  }
+  return SC_OK;
 }
 
 int sc_dgk_step4(sc_ctx* ctx, int mod, int cst_g, int cst_ginv, int l, const uint32_t* beta, const uint32_t* beta_inv,

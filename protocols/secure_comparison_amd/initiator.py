@@ -493,6 +493,32 @@ class Initiator:
 
         return await alice_gather(self, table_enc, index_enc, bits, signed, kappa, index_bits, source, engine, generator, chunks)
 
+    # ---- sums along an axis on top of the sessions above (aggregate.py)
+    async def perform_secure_histogram_batch(self, index_enc: torch.Tensor, k: int, index_bits: int | None = None, kappa: int = 40, draws=None,
+                                             source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[#{q : i_q mod k == t}]] [k][B][2nw] from index_enc [m][B][2nw] as aggregate.secure_histogram_batch: the one-hot session, then
+        the local sum over the indices.  chunks > 1 is not supported (ValueError)."""
+        from .aggregate import alice_histogram
+
+        return await alice_histogram(self, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks)
+
+    async def perform_secure_majority_batch(self, label_enc: torch.Tensor, k: int, index_bits: int | None = None, kappa: int = 40,
+                                            source: str = "device", engine=None, generator=None, chunks: int = 1):
+        """([[most frequent label]], [[its count]]) from label_enc [m][B][2nw] as aggregate.secure_majority_batch: the one-hot session, the
+        local sum, then the argmax's rounds at this initiator's l (at least bits(m): ValueError); ties go to the lowest label."""
+        from .aggregate import alice_majority
+
+        return await alice_majority(self, label_enc, k, index_bits, kappa, source, engine, generator, chunks)
+
+    async def perform_secure_groupby_sum_batch(self, value_enc: torch.Tensor, index_enc: torch.Tensor, k: int, bits: int, signed: bool = False,
+                                               index_bits: int | None = None, kappa: int = 40, source: str = "device", engine=None,
+                                               generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[sum_{b : i_b mod k == t} v_b]] [k][2nw] from value_enc, index_enc [B][2nw] as aggregate.secure_groupby_sum_batch: the one-hot
+        session, a multiplication session over k B rows, then the local sum over the rows."""
+        from .aggregate import alice_groupby_sum
+
+        return await alice_groupby_sum(self, value_enc, index_enc, k, bits, signed, index_bits, kappa, source, engine, generator, chunks)
+
     async def receive_encryption_schemes(self, session_id: int = 1) -> None:
         """Receive Bob's public schemes; a pre-set scheme must match (SC/initiator.py:177-203)."""
         if self.communicator is None:

@@ -363,6 +363,29 @@ class KeyHolder:
 
         await bob_gather(self, k, m, bits, signed, kappa, index_bits, source, generator, count)
 
+    # ---- sums along an axis (aggregate.py): the key holder's existing sessions in the initiator's order
+    async def perform_secure_histogram_batch(self, k: int, m: int = 1, index_bits: int | None = None, kappa: int = 40, draws=None,
+                                             source: str = "device", generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_histogram_batch: the one-hot session for m indices per row (the sum is Alice's)."""
+        from .aggregate import bob_histogram
+
+        await bob_histogram(self, k, m, index_bits, kappa, draws, source, generator, count)
+
+    async def perform_secure_majority_batch(self, k: int, m: int, index_bits: int | None = None, kappa: int = 40, source: str = "device",
+                                            generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_majority_batch: the one-hot session, then the argmax's rounds over k counts."""
+        from .aggregate import bob_majority
+
+        await bob_majority(self, k, m, index_bits, kappa, source, generator, count)
+
+    async def perform_secure_groupby_sum_batch(self, k: int, bits: int, signed: bool = False, index_bits: int | None = None, kappa: int = 40,
+                                               source: str = "device", generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_groupby_sum_batch: the one-hot session with m = 1, then the multiplication session over
+        k count rows."""
+        from .aggregate import bob_groupby_sum
+
+        await bob_groupby_sum(self, k, bits, signed, index_bits, kappa, source, generator, count)
+
     async def _batch_session(self, tag: str, first, draws, source: str, generator, expect_count: int | None = None) -> int:
         """One (sub-)session: Bob's steps around the four message exchanges with message ids `.._{tag}`; `first` is the step-1
         message when it has been received already.  Returns the session's batch size."""
