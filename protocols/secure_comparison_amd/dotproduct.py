@@ -20,9 +20,9 @@ from dataclasses import dataclass
 
 import torch
 
+from .exchange import announce, answer, no_chunks, receive_announced
 from .multiplication import MAX_WIDTH
 from .schemes import Paillier
-from .selection import _no_chunks
 
 MAX_K = 1024        # pairs per row (csrc/sc_vm.h DOT_MAX_K)
 
@@ -223,44 +223,25 @@ def secure_squared_distance_batch(x_enc: torch.Tensor, y_enc: torch.Tensor, bits
 
 
 # ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_dot_batch) -------------------------------------------
-# `dot_1_batch_{tag}` carries the layout (kappa, wx, wy, signed, square, k; int32) and P, `dot_2_batch_{tag}` the key holder's [[D]].  The
-# key holder compares the announced layout with his own arguments before he decrypts (sc_dot_split's flag alone catches only a message
-# that is too wide for his layout).
+# the announced exchange of exchange.py under the name `dot`: the header is DotLayout.header, exactly 6 entries, P is [M][B][2nw] and the
+# answer the key holder's one [[D]] per row.
 async def alice_dot(ini, x_enc, y_enc, x_bits, y_bits, signed, square, kappa, draws, source, engine, generator, chunks):
-    from . import wire
-
-    _no_chunks(chunks)
+    no_chunks(chunks)
     if not isinstance(x_enc, torch.Tensor) or x_enc.dim() != 3:
         raise ValueError("x_enc: expected [k][B][words]")
     sid = await ini._open_batch_session(x_enc[0], x_enc[0] if square else y_enc[0], engine)
-    comm, pai, tag = ini.communicator, ini.scheme_paillier, f"session_{sid}"
+    pai, count = ini.scheme_paillier, x_enc.shape[1]
     layout = _layout(x_enc, x_bits, 0 if square else y_bits, signed, square, kappa, pai)
-    count, dev = x_enc.shape[1], x_enc.device
     draws = draws if draws is not None else draw_dot(count, layout, pai, source, generator, bob=False)
     P, plain = dot_pack(layout, x_enc, None if square else y_enc, draws, pai)
-    head = torch.tensor(layout.header, dtype=torch.int32, device=dev)
-    await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"dot_1_batch_{tag}")
-    (d_enc,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"dot_2_batch_{tag}"), dev, expect=1)
-    d_enc = wire.expect_array(d_enc, (count, pai.mod_n2.nwords), "[[D]]")
+    d_enc = await announce(ini, "dot", f"session_{sid}", layout.header, P, (count,), "[[D]]")
     return dot_finish(layout, x_enc, None if square else y_enc, d_enc, plain, pai)
 
 
 async def bob_dot(kh, k, x_bits, y_bits, signed, square, kappa, draws, source, generator, count=None):
-    from . import wire
-
     sid = await kh._open_batch_session()
-    comm, pai, tag = kh.communicator, kh.scheme_paillier, f"session_{sid}"
+    pai, tag = kh.scheme_paillier, f"session_{sid}"
     layout = DotLayout(kappa, int(x_bits), 0 if square else int(y_bits), int(k), signed, square, pai.public_key.n.bit_length())
-    head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"dot_1_batch_{tag}"), pai.engine.device, expect=2)
-    if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] != 6:
-        raise ValueError("dot: malformed layout announcement")
-    announced = [int(v) for v in head.cpu().tolist()]
-    if announced != layout.header:
-        raise ValueError(f"dot: the initiator announces (kappa, wx, wy, signed, square, k) {announced}, this key holder expects {layout.header}")
-    if count is None:
-        if not isinstance(P, torch.Tensor) or P.dim() != 3:
-            raise ValueError("dot: P is not an [M][B][words] array")
-        count = P.shape[1]
-    P = wire.expect_array(P, (layout.M, count, pai.mod_n2.nwords), "P")
+    P, count = await receive_announced(kh, "dot", tag, layout.header, "(kappa, wx, wy, signed, square, k)", range(6, 7), (layout.M,), count)
     rho = draws.rho_d if draws is not None else draw_dot(count, layout, pai, source, generator, alice=False).rho_d
-    await comm.send(kh.other_party, wire.outgoing(comm, dot_sum(layout, P, pai, rho)), msg_id=f"dot_2_batch_{tag}")
+    await answer(kh, "dot", tag, dot_sum(layout, P, pai, rho))

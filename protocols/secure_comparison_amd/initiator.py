@@ -393,8 +393,9 @@ class Initiator:
     # ---- secure selection (selection.py): the comparison session, then one selection exchange per round
     async def perform_secure_minimum_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor, draws=None, select_draws=None, kappa: int = 40,
                                            source: str = "device", engine=None, generator=None, chunks: int = 1):
-        """([[min(x, y)]], [[x <= y]]) for B pairs: perform_secure_comparison_batch's messages, then `select_1_batch_{tag}` (P) and
-        `select_2_batch_{tag}` (the key holder's products).  chunks > 1 is not supported (ValueError)."""
+        """([[min(x, y)]], [[x <= y]]) for B pairs: perform_secure_comparison_batch's messages, then the announced exchange
+        (exchange.py) `select`: header kappa and the column widths, answer the key holder's products.  Here and in every method
+        below chunks > 1 is not supported (ValueError)."""
         from .selection import alice_minmax
 
         return await alice_minmax(self, x_enc, y_enc, draws, select_draws, kappa, source, engine, generator, chunks, want_max=False)
@@ -426,7 +427,7 @@ class Initiator:
                                         engine=None, generator=None, chunks: int = 1, max_rows: int = 65536):
         """(sorted [B][k][2nw], payload [np][B][k][2nw] or None, indices [B][k][2nw] or None), as sorting.secure_sort_batch: the header
         `sort_0_session_{sid}`, then per sub-batch of the network one comparison session and one selection exchange (message ids
-        `.._session_{sid}_sort_{i}`).  chunks > 1 is not supported (ValueError)."""
+        `.._session_{sid}_sort_{i}`)."""
         from .sorting import alice_sort
 
         return await alice_sort(self, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks,
@@ -438,7 +439,7 @@ class Initiator:
         """(values [B][m][2nw], payload [np][B][m][2nw] or None, indices [B][m][2nw] or None), as sorting.secure_topk_batch; with
         only_last the value of rank m - 1 alone ([B][2nw], [np][B][2nw], [B][2nw]), as sorting.secure_kth_batch(kth = m - 1).  The
         header `topk_0_session_{sid}`, then per sub-batch of sorting.topk_network(k, m, only_last) one comparison session and one
-        selection exchange (message ids `.._session_{sid}_topk_{i}`).  chunks > 1 is not supported (ValueError)."""
+        selection exchange (message ids `.._session_{sid}_topk_{i}`)."""
         from .sorting import alice_topk
 
         return await alice_topk(self, v_enc, m, payload, payload_bits, largest, return_indices, kappa, source, engine, generator, chunks,
@@ -448,9 +449,8 @@ class Initiator:
     async def perform_secure_multiply_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor, x_bits: int, y_bits, signed: bool = False,
                                             kappa: int = 40, draws=None, source: str = "device", engine=None, generator=None,
                                             chunks: int = 1) -> torch.Tensor:
-        """[[x y_j]] as multiplication.secure_multiply_batch: `mul_1_batch_{tag}` carries an int32 header (kappa, x_bits, signed, the
-        number of columns, their widths) and P, `mul_2_batch_{tag}` the key holder's products.  chunks > 1 is not supported
-        (ValueError)."""
+        """[[x y_j]] as multiplication.secure_multiply_batch, over the announced exchange `mul`: header (kappa, x_bits, signed, the
+        number of columns, their widths), answer the key holder's products."""
         from .multiplication import alice_multiply
 
         return await alice_multiply(self, x_enc, y_enc, x_bits, y_bits, signed, kappa, draws, source, engine, generator, chunks)
@@ -468,8 +468,8 @@ class Initiator:
                                        signed: bool = False, square: bool = False, kappa: int = 40, draws=None, source: str = "device",
                                        engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
         """[[sum_j x_j y_j]] [B][2nw] from x_enc, y_enc [k][B][2nw] as dotproduct.secure_dot_batch (square: [[sum_j x_j^2]], y_enc
-        ignored): `dot_1_batch_{tag}` carries an int32 header (kappa, x_bits, y_bits, signed, square, k) and the messages P
-        [M][B][2nw], `dot_2_batch_{tag}` the key holder's one [[D]] per row.  chunks > 1 is not supported (ValueError)."""
+        ignored), over the announced exchange `dot`: header (kappa, x_bits, y_bits, signed, square, k), P [M][B][2nw], answer the key
+        holder's one [[D]] per row."""
         from .dotproduct import alice_dot
 
         return await alice_dot(self, x_enc, y_enc, x_bits, y_bits, signed, square, kappa, draws, source, engine, generator, chunks)
@@ -477,9 +477,8 @@ class Initiator:
     # ---- secure one-hot encoding and table lookup (lookup.py)
     async def perform_secure_onehot_batch(self, index_enc: torch.Tensor, k: int, index_bits: int | None = None, kappa: int = 40, draws=None,
                                           source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
-        """[[ [t == i mod k] ]] [k][B][2nw] from index_enc [B][2nw] (or [m][k][B][2nw] from [m][B][2nw]) as lookup.secure_onehot_batch:
-        `onehot_1_batch_{tag}` carries an int32 header (kappa, ib, k, m) and the messages P [M][B][2nw], `onehot_2_batch_{tag}` the key
-        holder's E [m][k][B][2nw].  chunks > 1 is not supported (ValueError)."""
+        """[[ [t == i mod k] ]] [k][B][2nw] from index_enc [B][2nw] (or [m][k][B][2nw] from [m][B][2nw]) as lookup.secure_onehot_batch,
+        over the announced exchange `onehot`: header (kappa, ib, k, m), P [M][B][2nw], answer the key holder's E [m][k][B][2nw]."""
         from .lookup import alice_onehot
 
         return await alice_onehot(self, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks)
@@ -488,7 +487,7 @@ class Initiator:
                                           kappa: int = 40, index_bits: int | None = None, source: str = "device", engine=None, generator=None,
                                           chunks: int = 1) -> torch.Tensor:
         """[[table[i_q]]] [m][B][2nw] from table_enc [k][B][2nw] and index_enc [m][B][2nw] as lookup.secure_gather_batch: a one-hot
-        session, then an inner-product session over m B rows (two round trips).  chunks > 1 is not supported (ValueError)."""
+        session, then an inner-product session over m B rows (two round trips)."""
         from .lookup import alice_gather
 
         return await alice_gather(self, table_enc, index_enc, bits, signed, kappa, index_bits, source, engine, generator, chunks)
@@ -497,7 +496,7 @@ class Initiator:
     async def perform_secure_histogram_batch(self, index_enc: torch.Tensor, k: int, index_bits: int | None = None, kappa: int = 40, draws=None,
                                              source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
         """[[#{q : i_q mod k == t}]] [k][B][2nw] from index_enc [m][B][2nw] as aggregate.secure_histogram_batch: the one-hot session, then
-        the local sum over the indices.  chunks > 1 is not supported (ValueError)."""
+        the local sum over the indices."""
         from .aggregate import alice_histogram
 
         return await alice_histogram(self, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks)

@@ -23,8 +23,8 @@ from dataclasses import dataclass
 import torch
 
 from .dotproduct import DotLayout, dot_batch, draw_dot
+from .exchange import announce, answer, no_chunks, receive_announced
 from .schemes import Paillier
-from .selection import _no_chunks
 
 MAX_K = 1024        # table length (csrc/sc_vm.h ONEHOT_MAX_K)
 MAX_M = 65536       # indices per row (csrc/sc_vm.h ONEHOT_MAX_M)
@@ -228,60 +228,36 @@ def secure_lookup_batch(table_enc: torch.Tensor, index_enc: torch.Tensor, bits: 
 
 
 # ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_onehot_batch, .perform_secure_gather_batch) --------------
-# `onehot_1_batch_{tag}` carries the layout (kappa, ib, k, m; int32) and P, `onehot_2_batch_{tag}` the key holder's E.  The key holder
-# compares the announced layout with his own arguments before he decrypts (sc_onehot_split's flag alone catches only a message that is too
-# wide for his layout).
-def check_header(head, layout: OnehotLayout) -> None:
-    """ValueError unless the announced (kappa, ib, k, m) is this key holder's own."""
-    if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] != 4:
-        raise ValueError("onehot: malformed layout announcement")
-    announced = [int(v) for v in head.cpu().tolist()]
-    if announced != layout.header:
-        raise ValueError(f"onehot: the initiator announces (kappa, ib, k, m) {announced}, this key holder expects {layout.header}")
-
-
+# the announced exchange of exchange.py under the name `onehot`: the header is OnehotLayout.header, exactly 4 entries, P is [M][B][2nw] and
+# the answer the key holder's E.
 async def alice_onehot(ini, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks):
-    from . import wire
-
-    _no_chunks(chunks)
+    no_chunks(chunks)
     planes, single = _as_planes(index_enc)
     sid = await ini._open_batch_session(planes[0], planes[0], engine)
-    comm, pai, tag = ini.communicator, ini.scheme_paillier, f"session_{sid}"
+    pai, count = ini.scheme_paillier, planes.shape[1]
     layout = _layout(planes, k, index_bits, kappa, pai)
-    count, dev = planes.shape[1], planes.device
     draws = draws if draws is not None else draw_onehot(count, layout, pai, source, generator, bob=False)
     P, rot = onehot_pack(layout, planes, draws, pai)
-    head = torch.tensor(layout.header, dtype=torch.int32, device=dev)
-    await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"onehot_1_batch_{tag}")
-    (E,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"onehot_2_batch_{tag}"), dev, expect=1)
-    E = wire.expect_array(E, (layout.m, layout.k, count, pai.mod_n2.nwords), "E")
+    E = await announce(ini, "onehot", f"session_{sid}", layout.header, P, (layout.m, layout.k, count), "E")
     out = onehot_finish(layout, E, rot, pai)
     return out[0] if single else out
 
 
 async def bob_onehot(kh, k, m, index_bits, kappa, draws, source, generator, count=None):
-    from . import wire
-
     sid = await kh._open_batch_session()
-    comm, pai, tag = kh.communicator, kh.scheme_paillier, f"session_{sid}"
+    pai, tag = kh.scheme_paillier, f"session_{sid}"
     ib = default_index_bits(max(int(k), 1)) if index_bits is None else int(index_bits)
     layout = OnehotLayout(kappa, ib, int(k), int(m), pai.public_key.n.bit_length())
-    head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"onehot_1_batch_{tag}"), pai.engine.device, expect=2)
-    check_header(head, layout)
-    if count is None:
-        if not isinstance(P, torch.Tensor) or P.dim() != 3:
-            raise ValueError("onehot: P is not an [M][B][words] array")
-        count = P.shape[1]
-    P = wire.expect_array(P, (layout.M, count, pai.mod_n2.nwords), "P")
+    P, count = await receive_announced(kh, "onehot", tag, layout.header, "(kappa, ib, k, m)", range(4, 5), (layout.M,), count)
     rho = draws.rho_e if draws is not None else draw_onehot(count, layout, pai, source, generator, alice=False).rho_e
-    await comm.send(kh.other_party, wire.outgoing(comm, onehot_answer(layout, P, pai, rho)), msg_id=f"onehot_2_batch_{tag}")
+    await answer(kh, "onehot", tag, onehot_answer(layout, P, pai, rho))
     return count
 
 
 async def alice_gather(ini, table_enc, index_enc, bits, signed, kappa, index_bits, source, engine, generator, chunks):
     from .dotproduct import alice_dot
 
-    _no_chunks(chunks)
+    no_chunks(chunks)
     table_enc = _table(table_enc)
     planes, _ = _as_planes(index_enc)
     k, B = table_enc.shape[0], table_enc.shape[1]

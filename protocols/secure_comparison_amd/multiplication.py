@@ -19,9 +19,10 @@ from dataclasses import dataclass
 import torch
 
 from .batch import secure_comparison_batch
+from .exchange import announce, answer, no_chunks, receive_announced
 from .flags import check_l
 from .schemes import DGK, Paillier
-from .selection import MAX_FIELDS, _comparison_draws, _no_chunks
+from .selection import MAX_FIELDS, _comparison_draws
 
 MAX_WIDTH = 255     # bits of one operand (csrc/sc_vm.h MUL_MAX_WIDTH)
 
@@ -104,19 +105,14 @@ class MulDraws:
 def draw_mul(count: int, layout: MulLayout, paillier: Paillier, source: str = "device", generator=None, alice: bool = True,
              bob: bool = True) -> MulDraws:
     """Both players' (or one player's) multiplication draws for `count` rows, on the device or from a seeded torch generator."""
-    from .randomness import random_bits, uniform_below
+    from .randomness import random_bits, random_columns, uniform_below
 
     e, n = paillier.engine, paillier.public_key.n
     nf = len(layout.wy)
     r_a = r_b = rho_p = rho_q = None
     if alice:
         r_a = random_bits(layout.wx + layout.kappa, (count,), e, source, generator)
-        bw = (max(layout.wy) + layout.kappa + 31) // 32
-        cols = []
-        for w in layout.wy:
-            c = random_bits(w + layout.kappa, (count,), e, source, generator)
-            cols.append(torch.nn.functional.pad(c, (0, bw - c.shape[-1])))
-        r_b = torch.stack(cols).contiguous()
+        r_b = random_columns([w + layout.kappa for w in layout.wy], (max(layout.wy) + layout.kappa + 31) // 32, count, e, source, generator)
         rho_p = uniform_below(n, count, e, source, generator, nonzero=True)
     if bob:
         rho_q = uniform_below(n, nf * count, e, source, generator, nonzero=True).reshape(nf, count, -1)
@@ -236,46 +232,26 @@ def secure_in_range_batch(x_enc: torch.Tensor, lo_enc: torch.Tensor, hi_enc: tor
 
 
 # ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{multiply,equal}_batch) -------------------------------
-# `mul_1_batch_{tag}` carries the layout (kappa, wx, signed, nf, wy.., int32) and P, `mul_2_batch_{tag}` the key holder's products.  The
-# key holder compares the announced layout with his own arguments before he decrypts (sc_mul_split's flag alone catches only a layout
-# wider than his).
-async def _alice_mul(ini, tag, layout, x_enc, y_enc, draws, source, generator, base=None, coef=1):
-    from . import wire
-
-    comm, pai = ini.communicator, ini.scheme_paillier
-    nf, count, dev = len(layout.wy), x_enc.shape[0], x_enc.device
+# the announced exchange of exchange.py under the name `mul`: the header is MulLayout.header (more than 4 + MAX_FIELDS entries are
+# malformed), the answer the key holder's products.
+async def _alice_mul(ini, tag, layout, x_enc, y_enc, draws, source, generator):
+    pai, count = ini.scheme_paillier, x_enc.shape[0]
     draws = draws if draws is not None else draw_mul(count, layout, pai, source, generator, bob=False)
     P, plain = mul_pack(layout, x_enc, y_enc, draws, pai)
-    head = torch.tensor(layout.header, dtype=torch.int32, device=dev)
-    await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"mul_1_batch_{tag}")
-    (prods,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"mul_2_batch_{tag}"), dev, expect=1)
-    prods = wire.expect_array(prods, (nf, count, pai.mod_n2.nwords), "[[A B_j]]")
-    return mul_finish(layout, x_enc, y_enc, prods, plain, pai, base, coef)
+    prods = await announce(ini, "mul", tag, layout.header, P, (len(layout.wy), count), "[[A B_j]]")
+    return mul_finish(layout, x_enc, y_enc, prods, plain, pai)
 
 
 async def _bob_mul(kh, tag, layout, count, draws, source, generator):
     """The key holder's half of one multiplication exchange: the layout check, then his products.  count None: P's own."""
-    from . import wire
-
-    comm, pai = kh.communicator, kh.scheme_paillier
-    head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"mul_1_batch_{tag}"), pai.engine.device, expect=2)
-    if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] > 4 + MAX_FIELDS:
-        raise ValueError("mul: malformed layout announcement")
-    announced = [int(v) for v in head.cpu().tolist()]
-    if announced != layout.header:
-        raise ValueError(f"mul: the initiator announces (kappa, wx, signed, columns, widths) {announced}, this key holder expects "
-                         f"{layout.header}")
-    if count is None:
-        if not isinstance(P, torch.Tensor) or P.dim() != 2:
-            raise ValueError("mul: P is not a [B][words] array")
-        count = P.shape[0]
-    P = wire.expect_array(P, (count, pai.mod_n2.nwords), "P")
+    pai = kh.scheme_paillier
+    P, count = await receive_announced(kh, "mul", tag, layout.header, "(kappa, wx, signed, columns, widths)", range(5 + MAX_FIELDS), (), count)
     rho = draws.rho_products if draws is not None else draw_mul(count, layout, pai, source, generator, alice=False).rho_products
-    await comm.send(kh.other_party, wire.outgoing(comm, mul_mult(layout, P, pai, rho)), msg_id=f"mul_2_batch_{tag}")
+    await answer(kh, "mul", tag, mul_mult(layout, P, pai, rho))
 
 
 async def alice_multiply(ini, x_enc, y_enc, x_bits, y_bits, signed, kappa, draws, source, engine, generator, chunks):
-    _no_chunks(chunks)
+    no_chunks(chunks)
     y = y_enc if y_enc.dim() == 2 else y_enc[0]
     sid = await ini._open_batch_session(x_enc, y, engine)
     layout = _layout(x_bits, y_bits, signed, kappa, ini.scheme_paillier)
@@ -289,7 +265,7 @@ async def bob_multiply(kh, x_bits, y_bits, signed, kappa, draws, source, generat
 
 
 async def alice_equal(ini, x_enc, y_enc, draws, mul_draws, kappa, source, engine, generator, chunks):
-    _no_chunks(chunks)
+    no_chunks(chunks)
     sid = await ini._open_batch_session(x_enc, y_enc, engine)
     pai, B, tag = ini.scheme_paillier, x_enc.shape[0], f"session_{sid}"
     layout = _layout(1, (1,), False, kappa, pai)

@@ -42,6 +42,15 @@ def random_bits(bits: int, lead_shape: tuple[int, ...], engine, source: str = "d
     return w
 
 
+def random_columns(bits, words: int, count: int, engine, source: str = "device", generator: torch.Generator | None = None) -> torch.Tensor:
+    """[len(bits)][count][words]: column j uniform below 2^bits[j], one random_bits call per column in order, zero-padded to `words`."""
+    cols = []
+    for b in bits:
+        c = random_bits(b, (count,), engine, source, generator)
+        cols.append(torch.nn.functional.pad(c, (0, words - c.shape[-1])))
+    return torch.stack(cols).contiguous()
+
+
 def _below_mask(cand: torch.Tensor, n: int, nonzero: bool) -> torch.Tensor:
     """bool [rows]: candidate (words, least significant first) < n (and != 0): the most significant differing word decides."""
     nw = cand.shape[-1]

@@ -18,6 +18,7 @@ from dataclasses import dataclass
 import torch
 
 from .batch import BatchDraws, BatchTrace, draw_alice, draw_bob, secure_comparison_batch
+from .exchange import announce, answer, no_chunks, receive_announced
 from .flags import check_l
 from .schemes import DGK, Paillier
 
@@ -78,6 +79,11 @@ class SelectLayout:
         """Bits of the exponents of T: r_b_j + 2^w_j < 2^(w_j + kappa + 2), r_a < 2^kappa."""
         return max(self.fbits)
 
+    @property
+    def header(self) -> list[int]:
+        """What `select_1_batch_{tag}` announces: kappa, the column widths."""
+        return [self.kappa, *self.widths]
+
 
 @dataclass
 class SelectDraws:
@@ -93,19 +99,14 @@ class SelectDraws:
 def draw_select(count: int, layout: SelectLayout, paillier: Paillier, source: str = "device", generator=None,
                 alice: bool = True, bob: bool = True) -> SelectDraws:
     """Both players' (or one player's) selection draws for `count` rows, on the device or from a seeded torch generator."""
-    from .randomness import random_bits, uniform_below
+    from .randomness import random_bits, random_columns, uniform_below
 
     e, n = paillier.engine, paillier.public_key.n
     nf = len(layout.widths)
     r_a = r_b = rho_p = rho_q = None
     if alice:
         r_a = random_bits(layout.kappa, (count,), e, source, generator)
-        bw = (max(layout.fbits) + 31) // 32
-        cols = []
-        for w in layout.widths:
-            c = random_bits(w + 1 + layout.kappa, (count,), e, source, generator)
-            cols.append(torch.nn.functional.pad(c, (0, bw - c.shape[-1])))
-        r_b = torch.stack(cols).contiguous()
+        r_b = random_columns([w + 1 + layout.kappa for w in layout.widths], (max(layout.fbits) + 31) // 32, count, e, source, generator)
         rho_p = uniform_below(n, count, e, source, generator, nonzero=True)
     if bob:
         rho_q = uniform_below(n, nf * count, e, source, generator, nonzero=True).reshape(nf, count, -1)
@@ -274,9 +275,8 @@ def secure_argmax_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, a
 
 # ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{minimum,maximum,argmin,argmax}_batch) -----------------
 # Each round is one batched comparison session (Initiator._batch_session, its messages unchanged) followed by one selection exchange:
-# `select_1_batch_{tag}` carries the layout (kappa and the column widths, int32) and P, `select_2_batch_{tag}` the key holder's
-# products.  The key holder checks the announced layout against his own kappa, l and payload widths before he decrypts, so players
-# that disagree fail loudly in either direction (sc_select_split's flag alone catches only a layout wider than the key holder's).
+# the announced exchange of exchange.py under the name `select`: the header is kappa and the column widths, the answer the key holder's
+# products.
 async def _alice_compare(ini, tag, x_enc, y_enc, draws, source, generator):
     keep = {}
     delta = await ini._batch_session(tag, x_enc, y_enc, draws, source, generator, None, keep=keep)
@@ -287,16 +287,10 @@ async def _alice_compare(ini, tag, x_enc, y_enc, draws, source, generator):
 async def _alice_exchange(ini, tag, layout, sigma, d, sd, source, generator):
     """Alice's selection exchange up to Bob's products: (products [nf][B][2nw], plain, draws) for select_finish or the sort's
     compare-exchange finish."""
-    from . import wire
-
-    comm, pai = ini.communicator, ini.scheme_paillier
-    nf, count, dev = len(layout.widths), sigma.shape[0], sigma.device
+    pai, count = ini.scheme_paillier, sigma.shape[0]
     sd = sd if sd is not None else draw_select(count, layout, pai, source, generator, bob=False)
     P, plain = select_pack(layout, sigma, d, sd, pai)
-    head = torch.tensor([layout.kappa, *layout.widths], dtype=torch.int32, device=dev)
-    await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"select_1_batch_{tag}")
-    (prods,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"select_2_batch_{tag}"), dev, expect=1)
-    prods = wire.expect_array(prods, (nf, count, pai.mod_n2.nwords), "[[a b_j]]")
+    prods = await announce(ini, "select", tag, layout.header, P, (len(layout.widths), count), "[[a b_j]]")
     return prods, plain, sd
 
 
@@ -305,15 +299,10 @@ async def _alice_select(ini, tag, layout, sigma, d, b, sd, source, generator):
     return select_finish(layout, sigma, d, b, prods, plain, sd, ini.scheme_paillier)
 
 
-def _no_chunks(chunks):
-    if int(chunks) != 1:
-        raise ValueError("secure selection: chunks > 1 is not supported")
-
-
 async def alice_minmax(ini, x_enc, y_enc, draws, select_draws, kappa, source, engine, generator, chunks, want_max):
     from .batch import draw_alice
 
-    _no_chunks(chunks)
+    no_chunks(chunks)
     sid = await ini._open_batch_session(x_enc, y_enc, engine)
     pai, dgk, l = ini.scheme_paillier, ini.scheme_dgk, ini.l_maximum_bit_length
     layout = SelectLayout(l, kappa, (), pai.public_key.n.bit_length())
@@ -327,7 +316,7 @@ async def alice_minmax(ini, x_enc, y_enc, draws, select_draws, kappa, source, en
 
 
 async def alice_argext(ini, v_enc, kappa, source, engine, generator, chunks, want_max):
-    _no_chunks(chunks)
+    no_chunks(chunks)
     if v_enc.dim() != 3:
         raise ValueError("v_enc: expected [B][k][2nw]")
     sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
@@ -348,21 +337,11 @@ async def alice_argext(ini, v_enc, kappa, source, engine, generator, chunks, wan
 
 async def _bob_select(kh, tag, layout, count, select_draws, source, generator):
     """The key holder's selection exchange after a comparison session of `count` rows: the layout check, then his products."""
-    from . import wire
-
-    comm, pai = kh.communicator, kh.scheme_paillier
-    head, P = wire.incoming(await comm.recv(kh.other_party, msg_id=f"select_1_batch_{tag}"), pai.engine.device, expect=2)
-    if not isinstance(head, torch.Tensor) or head.dim() != 1 or head.shape[0] > 1 + MAX_FIELDS:
-        raise ValueError("select: malformed layout announcement")
-    announced = [int(v) for v in head.cpu().tolist()]
-    if announced != [layout.kappa, *layout.widths]:
-        raise ValueError(f"select: the initiator announces kappa and widths {announced}, this key holder expects "
-                         f"{[layout.kappa, *layout.widths]}")
-    P = wire.expect_array(P, (count, pai.mod_n2.nwords), "P")
+    pai = kh.scheme_paillier
+    P, _ = await receive_announced(kh, "select", tag, layout.header, "kappa and widths", range(2 + MAX_FIELDS), (), count)
     rho = (select_draws.rho_products if select_draws is not None
            else draw_select(count, layout, pai, source, generator, alice=False).rho_products)
-    prods = select_mult(layout, P, pai, rho)
-    await comm.send(kh.other_party, wire.outgoing(comm, prods), msg_id=f"select_2_batch_{tag}")
+    await answer(kh, "select", tag, select_mult(layout, P, pai, rho))
 
 
 async def bob_rounds(kh, rounds, draws, select_draws, kappa, source, generator, payload_bits):

@@ -19,11 +19,13 @@ from __future__ import annotations
 
 import torch
 
+from . import wire
 from .batch import BatchDraws
+from .exchange import no_chunks
 from .flags import check_l
 from .schemes import DGK, Paillier
-from .selection import (MAX_FIELDS, SelectDraws, SelectLayout, _alice_compare, _alice_exchange, _bob_select, _compare, _no_chunks,
-                        draw_select, index_bits, select_mult, select_pack)
+from .selection import (MAX_FIELDS, SelectDraws, SelectLayout, _alice_compare, _alice_exchange, _bob_select, _compare, draw_select,
+                        index_bits, select_mult, select_pack)
 
 MAX_K = 1024        # values per row
 
@@ -243,6 +245,14 @@ def secure_compare_exchange_batch(x_enc: torch.Tensor, y_enc: torch.Tensor, l: i
 
 
 # ---- the sort in one process -------------------------------------------------------------------------------------------------------
+def _sort_layout(l, k, payload_bits, return_indices, kappa, paillier) -> SelectLayout:
+    """The layout of the key column, the payload columns and -- return_indices -- the index column of k values per row."""
+    widths = tuple(int(b) for b in payload_bits) + ((index_bits(k),) if return_indices else ())
+    if 1 + len(widths) > MAX_FIELDS:
+        raise ValueError(f"{1 + len(widths)} columns (key, payload, index): at most {MAX_FIELDS}")
+    return SelectLayout(l, kappa, widths, paillier.public_key.n.bit_length())
+
+
 def _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_rows):
     """Every check that comes before an upload or a launch; returns (layout, B, k)."""
     check_l(l)
@@ -264,10 +274,7 @@ def _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_
         raise ValueError(f"payload: expected [np][{B}][{k}][{nw2}]")
     elif payload.shape[0] != len(payload_bits):
         raise ValueError(f"payload: {payload.shape[0]} columns, {len(payload_bits)} widths in payload_bits")
-    widths = payload_bits + ((index_bits(k),) if return_indices else ())
-    if 1 + len(widths) > MAX_FIELDS:
-        raise ValueError(f"{1 + len(widths)} columns (key, payload, index): at most {MAX_FIELDS}")
-    return SelectLayout(l, kappa, widths, ap.public_key.n.bit_length()), B, k
+    return _sort_layout(l, k, payload_bits, return_indices, kappa, ap), B, k
 
 
 def _sort_buffer(v_enc, payload, return_indices, ap, B, k):
@@ -370,115 +377,99 @@ def secure_median_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, a
                             return_indices, kappa, max_rows)
 
 
-# ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_sort_batch) -----------------------------------------
-# `sort_0_session_{sid}` (int32: k, B, max_rows, kappa, the column widths) opens the sort; the key holder refuses a header that
-# differs from his own arguments and derives the schedule from it.  Sub-batch i is the unchanged comparison session and one selection
-# exchange under the tag `session_{sid}_sort_{i}`.
-async def alice_sort(ini, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks, max_rows):
-    from . import wire
-
-    _no_chunks(chunks)
+# ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{sort,topk}_batch) -----------------------------------
+# An opening message tells the key holder what he cannot derive, B; he refuses a header that differs from his own arguments in anything
+# else and derives the schedule from it.  Sub-batch i is then the unchanged comparison session and one selection exchange under the tag
+# `session_{sid}_{word}_{i}`, word = `sort` or `topk`: the key holder's work does not depend on which outputs are live.
+def _player_checks(v_enc, max_rows, chunks) -> None:
+    no_chunks(chunks)
     if not isinstance(v_enc, torch.Tensor) or v_enc.dim() != 3:
         raise ValueError("v_enc: expected [B][k][2nw]")
     if not 1 <= int(max_rows) < 1 << 31:
         raise ValueError(f"max_rows = {max_rows}: expected 1 <= max_rows < 2^31")
-    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
-    pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
-    layout, B, k = _sort_start(v_enc, l, pai, payload, payload_bits, return_indices, kappa, max_rows)
-    head = torch.tensor([k, B, int(max_rows), layout.kappa, *layout.widths], dtype=torch.int32, device=v_enc.device)
-    await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"sort_0_session_{sid}")
-    buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
-    out = buf.reshape(-1, buf.shape[-1])
-    for i, (f, g, lo, hi) in enumerate(_sort_steps(buf, B, k, int(max_rows), descending)):
-        tag = f"session_{sid}_sort_{i}"
+
+
+async def _alice_network(ini, sid, word, layout, steps, out, source, generator) -> None:
+    """Alice's compare-exchanges of `steps` (_sort_steps or _topk_steps), in place in `out`."""
+    pai = ini.scheme_paillier
+    for i, (f, g, lo, hi) in enumerate(steps):
+        tag = f"session_{sid}_{word}_{i}"
         delta, d_key = await _alice_compare(ini, tag, f[0], g[0], None, source, generator)
         d = cx_differences(pai, layout, f, g, d_key)
         products, plain, sd = await _alice_exchange(ini, tag, layout, delta, d, None, source, generator)
         cx_finish(layout, delta, d, f, g, products, plain, sd, pai, out, lo, hi)
+
+
+async def _bob_network(kh, sid, word, layout, counts, source, generator) -> None:
+    """The key holder's side of the sub-batches of `counts` (schedule_counts or topk_counts); one of another size is refused."""
+    for i, count in enumerate(counts):
+        tag = f"session_{sid}_{word}_{i}"
+        got = await kh._batch_session(tag, None, None, source, generator)
+        if got != count:
+            raise ValueError(f"{word}: sub-batch {i} carries {got} comparisons, the schedule has {count}")
+        await _bob_select(kh, tag, layout, count, None, source, generator)
+
+
+# `sort_0_session_{sid}` is int32: k, B, max_rows, kappa, the column widths.
+async def alice_sort(ini, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks, max_rows):
+    _player_checks(v_enc, max_rows, chunks)
+    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
+    pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
+    layout, B, k = _sort_start(v_enc, l, pai, payload, payload_bits, return_indices, kappa, max_rows)
+    head = torch.tensor([k, B, int(max_rows), *layout.header], dtype=torch.int32, device=v_enc.device)
+    await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"sort_0_session_{sid}")
+    buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
+    steps = _sort_steps(buf, B, k, int(max_rows), descending)
+    await _alice_network(ini, sid, "sort", layout, steps, buf.reshape(-1, buf.shape[-1]), source, generator)
     return _sort_result(buf, payload, return_indices, B, k)
 
 
 async def bob_sort(kh, k, payload_bits, return_indices, kappa, source, generator, max_rows):
-    from . import wire
-
     sid = await kh._open_batch_session()
-    comm, pai, l = kh.communicator, kh.scheme_paillier, kh.l_maximum_bit_length
+    pai = kh.scheme_paillier
     batcher_network(k)                                                   # k in range
-    widths = tuple(int(b) for b in payload_bits) + ((index_bits(k),) if return_indices else ())
-    if 1 + len(widths) > MAX_FIELDS:
-        raise ValueError(f"{1 + len(widths)} columns (key, payload, index): at most {MAX_FIELDS}")
-    layout = SelectLayout(l, kappa, widths, pai.public_key.n.bit_length())
-    (head,) = wire.incoming(await comm.recv(kh.other_party, msg_id=f"sort_0_session_{sid}"), pai.engine.device, expect=1)
+    layout = _sort_layout(kh.l_maximum_bit_length, k, payload_bits, return_indices, kappa, pai)
+    (head,) = wire.incoming(await kh.communicator.recv(kh.other_party, msg_id=f"sort_0_session_{sid}"), pai.engine.device, expect=1)
     if not isinstance(head, torch.Tensor) or head.dim() != 1 or not 5 <= head.shape[0] <= 4 + MAX_FIELDS:
         raise ValueError("sort: malformed header")
     hk, B, mr, *rest = [int(v) for v in head.cpu().tolist()]
-    mine = [k, int(max_rows), layout.kappa, *layout.widths]
+    mine = [k, int(max_rows), *layout.header]
     if [hk, mr, *rest] != mine:
         raise ValueError(f"sort: the initiator announces k, max_rows, kappa and widths {[hk, mr, *rest]}, this key holder expects {mine}")
     if B < 0:
         raise ValueError(f"sort: the initiator announces B = {B}")
-    for i, count in enumerate(schedule_counts(k, B, mr)):
-        tag = f"session_{sid}_sort_{i}"
-        got = await kh._batch_session(tag, None, None, source, generator)
-        if got != count:
-            raise ValueError(f"sort: sub-batch {i} carries {got} comparisons, the schedule has {count}")
-        await _bob_select(kh, tag, layout, count, None, source, generator)
+    await _bob_network(kh, sid, "sort", layout, schedule_counts(k, B, mr), source, generator)
 
 
-# ---- top-m between the two players (Initiator / KeyHolder.perform_secure_topk_batch) -----------------------------------------------
-# `topk_0_session_{sid}` (int32: k, m, only_last, B, max_rows, kappa, the column widths) opens the run; the key holder refuses a header
-# that differs from his own arguments and derives the schedule from it (topk_counts).  Sub-batch i is the unchanged comparison session
-# and one selection exchange under the tag `session_{sid}_topk_{i}`: the key holder's work does not depend on which outputs are live.
+# `topk_0_session_{sid}` is int32: k, m, only_last, B, max_rows, kappa, the column widths.
 async def alice_topk(ini, v_enc, m, payload, payload_bits, largest, return_indices, kappa, source, engine, generator, chunks, max_rows,
                      only_last):
-    from . import wire
-
-    _no_chunks(chunks)
-    if not isinstance(v_enc, torch.Tensor) or v_enc.dim() != 3:
-        raise ValueError("v_enc: expected [B][k][2nw]")
-    if not 1 <= int(max_rows) < 1 << 31:
-        raise ValueError(f"max_rows = {max_rows}: expected 1 <= max_rows < 2^31")
+    _player_checks(v_enc, max_rows, chunks)
     only_last = bool(only_last)
     sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
     pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
     layout, B, k, m = _topk_start(v_enc, m, l, pai, payload, payload_bits, return_indices, kappa, max_rows)
-    head = torch.tensor([k, m, int(only_last), B, int(max_rows), layout.kappa, *layout.widths], dtype=torch.int32, device=v_enc.device)
+    head = torch.tensor([k, m, int(only_last), B, int(max_rows), *layout.header], dtype=torch.int32, device=v_enc.device)
     await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"topk_0_session_{sid}")
     buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
-    out = buf.reshape(-1, buf.shape[-1])
-    for i, (f, g, lo, hi) in enumerate(_topk_steps(buf, B, k, m, only_last, int(max_rows), largest)):
-        tag = f"session_{sid}_topk_{i}"
-        delta, d_key = await _alice_compare(ini, tag, f[0], g[0], None, source, generator)
-        d = cx_differences(pai, layout, f, g, d_key)
-        products, plain, sd = await _alice_exchange(ini, tag, layout, delta, d, None, source, generator)
-        cx_finish(layout, delta, d, f, g, products, plain, sd, pai, out, lo, hi)
+    steps = _topk_steps(buf, B, k, m, only_last, int(max_rows), largest)
+    await _alice_network(ini, sid, "topk", layout, steps, buf.reshape(-1, buf.shape[-1]), source, generator)
     return _topk_result(buf, payload, return_indices, B, k, m, only_last)
 
 
 async def bob_topk(kh, k, m, payload_bits, return_indices, kappa, only_last, source, generator, max_rows):
-    from . import wire
-
     sid = await kh._open_batch_session()
-    comm, pai, l = kh.communicator, kh.scheme_paillier, kh.l_maximum_bit_length
-    only_last = bool(only_last)
+    pai, only_last = kh.scheme_paillier, bool(only_last)
     topk_network(k, m, only_last)                                        # k and m in range
-    widths = tuple(int(b) for b in payload_bits) + ((index_bits(k),) if return_indices else ())
-    if 1 + len(widths) > MAX_FIELDS:
-        raise ValueError(f"{1 + len(widths)} columns (key, payload, index): at most {MAX_FIELDS}")
-    layout = SelectLayout(l, kappa, widths, pai.public_key.n.bit_length())
-    (head,) = wire.incoming(await comm.recv(kh.other_party, msg_id=f"topk_0_session_{sid}"), pai.engine.device, expect=1)
+    layout = _sort_layout(kh.l_maximum_bit_length, k, payload_bits, return_indices, kappa, pai)
+    (head,) = wire.incoming(await kh.communicator.recv(kh.other_party, msg_id=f"topk_0_session_{sid}"), pai.engine.device, expect=1)
     if not isinstance(head, torch.Tensor) or head.dim() != 1 or not 7 <= head.shape[0] <= 6 + MAX_FIELDS:
         raise ValueError("topk: malformed header")
     hk, hm, hol, B, mr, *rest = [int(v) for v in head.cpu().tolist()]
-    mine = [k, int(m), int(only_last), int(max_rows), layout.kappa, *layout.widths]
+    mine = [k, int(m), int(only_last), int(max_rows), *layout.header]
     if [hk, hm, hol, mr, *rest] != mine:
         raise ValueError(f"topk: the initiator announces k, m, only_last, max_rows, kappa and widths {[hk, hm, hol, mr, *rest]}, "
                          f"this key holder expects {mine}")
     if B < 0:
         raise ValueError(f"topk: the initiator announces B = {B}")
-    for i, count in enumerate(topk_counts(k, int(m), only_last, B, mr)):
-        tag = f"session_{sid}_topk_{i}"
-        got = await kh._batch_session(tag, None, None, source, generator)
-        if got != count:
-            raise ValueError(f"topk: sub-batch {i} carries {got} comparisons, the schedule has {count}")
-        await _bob_select(kh, tag, layout, count, None, source, generator)
+    await _bob_network(kh, sid, "topk", layout, topk_counts(k, int(m), only_last, B, mr), source, generator)

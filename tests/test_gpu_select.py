@@ -289,3 +289,80 @@ def test_players_refuse_a_different_kappa(engine, keys):
     assert isinstance(got_a, Exception)          # the initiator never gets products back
     with pytest.raises(ValueError):
         asyncio.run(alice.perform_secure_minimum_batch(x_t, x_t, chunks=2, engine=engine))
+
+
+# ---- the four families on one pair ---------------------------------------------------------------------------------------------------
+class _Recorder:
+    """An endpoint that keeps the message ids both players send, in order, in the shared `ids`."""
+
+    def __init__(self, inner, ids):
+        self.inner, self.ids, self.device_tensors = inner, ids, inner.device_tensors
+
+    async def send(self, party, message, msg_id=None):
+        self.ids.append(msg_id)
+        await self.inner.send(party, message, msg_id=msg_id)
+
+    async def recv(self, party, msg_id=None):
+        return await self.inner.recv(party, msg_id=msg_id)
+
+
+# Launches of the interpreter kernels (the sum of engine.launch_counts()) of minimum, multiply, dot and one-hot at B = 3 on the 1024-bit
+# key, both players on one engine, once every key, table and modulus exists: the figures of the commit before the families shared
+# exchange.py.  The host's exchange code decides none of them, so they hold exactly.
+LAUNCHES = [62, 27, 33, 23]
+
+
+def test_players_all_families_on_one_pair(engine, keys):
+    """Minimum, one-column multiplication, inner product (k = 3 pairs of 200-bit operands: pairs of 482 bits, g = 2, M = 2 messages per
+    row) and one-hot (k = 3, m = 2) in sequence on one Initiator / KeyHolder pair, twice: the message ids are those of the CPU transcript
+    (tests/test_exchange_cpu.py) around the session's own, every result decrypts to plain Python's, and the second pass launches exactly
+    LAUNCHES kernels per call."""
+    import asyncio
+
+    from protocols.secure_comparison_amd import DotLayout
+    from test_exchange_cpu import TRANSCRIPT
+
+    sk, ap, bp, alice, bob = _two_players(engine, keys, 16)
+    ids = []
+    alice.communicator, bob.communicator = _Recorder(alice.communicator, ids), _Recorder(bob.communicator, ids)
+    B, k_dot, bits, k_hot, m_hot = 3, 3, 200, 3, 2
+    assert DotLayout(40, bits, bits, k_dot, nbits=sk.n.bit_length()).M == 2
+    rng = random.Random(2027)
+    nw2 = ap.mod_n2.nwords
+    up = lambda vals: engine.upload([model.enc(sk, v) for v in vals], nw2)  # noqa: E731
+    dec = lambda t: engine.download(bp.decrypt_raw_batch(t.reshape(-1, nw2).contiguous()))  # noqa: E731
+    xs, ys = [7, 65535, rng.getrandbits(16)], [7, 0, rng.getrandbits(16)]
+    us = [[rng.getrandbits(bits) for _ in range(B)] for _ in range(k_dot)]
+    vs = [[rng.getrandbits(bits) for _ in range(B)] for _ in range(k_dot)]
+    idx = [[0, 2, 1], [1, 3, 2]]                                     # [m][B]; 3 is at or above k: marks 3 mod 3
+    x_t, y_t = up(xs), up(ys)
+    u_t, v_t = torch.stack([up(r) for r in us]).contiguous(), torch.stack([up(r) for r in vs]).contiguous()
+    i_t = torch.stack([up(r) for r in idx]).contiguous()
+    total = lambda: sum(engine.launch_counts().values())  # noqa: E731
+
+    async def both(a, b):
+        before = total()
+        out, _ = await asyncio.gather(a, b)
+        return out, total() - before
+
+    async def run():
+        return [await both(alice.perform_secure_minimum_batch(x_t, y_t, engine=engine), bob.perform_secure_minimum_batch()),
+                await both(alice.perform_secure_multiply_batch(x_t, y_t, 16, 16, engine=engine), bob.perform_secure_multiply_batch(16, 16)),
+                await both(alice.perform_secure_dot_batch(u_t, v_t, bits, bits, engine=engine), bob.perform_secure_dot_batch(k_dot, bits, bits)),
+                await both(alice.perform_secure_onehot_batch(i_t, k_hot, engine=engine), bob.perform_secure_onehot_batch(k_hot, m_hot))]
+
+    want_ids = []
+    for sid, family in enumerate(["select", "mul", "dot", "onehot"] * 2, start=1):
+        want_ids.append(f"schemes_batch_session_{sid}")
+        if family == "select":
+            want_ids += [f"step_{s}_batch_session_{sid}" for s in ("1", "4b", "4i", "5")]
+        want_ids += [e[1].replace("session_1", f"session_{sid}") for e in TRANSCRIPT[family][1] if e[1].startswith(family + "_")]
+    for _ in range(2):
+        ((mn, le), n_min), (prod, n_mul), (dot, n_dot), (hot, n_hot) = asyncio.run(run())
+        assert dec(mn) == [min(x, y) for x, y in zip(xs, ys)] and dec(le) == [int(x <= y) for x, y in zip(xs, ys)]
+        assert dec(prod) == [x * y for x, y in zip(xs, ys)]
+        assert dec(dot) == [sum(us[j][b] * vs[j][b] for j in range(k_dot)) for b in range(B)]
+        assert dec(hot) == [int(t == idx[q][b] % k_hot) for q in range(m_hot) for t in range(k_hot) for b in range(B)]
+    print("launches per call (minimum, multiply, dot, one-hot):", [n_min, n_mul, n_dot, n_hot])
+    assert ids == want_ids
+    assert [n_min, n_mul, n_dot, n_hot] == LAUNCHES
