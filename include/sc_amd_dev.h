@@ -60,7 +60,8 @@ int sc_ctx_stats(sc_ctx* ctx, uint64_t* out, int n);
  * to keys_out / counts_out (either may be NULL with cap 0); *n_out = the number of instances launched so far, which may exceed
  * `cap`.  The key names the template instance:
  *   bits 0..7 L, bits 8..15 G, bits 16..23 W (limb bits), bit 24 NEG1, bit 25 STAMP, bit 26 DIG, bit 27 kind (0 k_vm, 1 k_pvm),
- *   bit 28 k_prod_axis (sc_modprod_axis; bits 24..27 zero);
+ *   bit 28 k_prod_axis (sc_modprod_axis, and the totals of sc_modscan_axis; bits 24..27 zero);
+ *   bit 29 k_scan_axis (sc_modscan_axis; bits 24..28 zero);
  * STAMP and DIG are always 0 for k_vm.  For tests and tools: which instance a call landed on is host policy no result shows. */
 int sc_ctx_launch_counts(sc_ctx* ctx, uint32_t* keys_out, uint64_t* counts_out, int cap, int* n_out);
 /* The constants behind the automatic policies, measured once per device and process when the first secret key is created (about
@@ -174,6 +175,20 @@ int sc_modinv(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint32_t* out_dptr, 
  * configuration; one without an instance (one-lane (1,18), 28-bit limbs, modulus multiples) is SC_ERR_ARG and the message names the
  * configuration.  Launches are counted in sc_ctx_launch_counts under the key  L | G << 8 | 29 << 16 | 1 << 28. */
 int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out_dptr);
+/* The running product along one axis, inclusive: x viewed as [outer][K][inner][nwords] canonical residues,
+ * out[o][j][i] = prod_{j' <= j} x[o][j'][i] mod n, canonical, in the shape of x.  Every position is an output, so nothing may drift:
+ * the dedicated kernel k_scan_axis keeps the running prefix as the canonical residue it has just stored and pays two Montgomery
+ * products per member (prefix * R^(e+2) / R, then * member / R, for a member that carries R^-e), with no conversion launch before and
+ * no reduction launch after.  One launch, one chain per (o, i), when outer * inner chains fill the chip's resident group slots or K is
+ * no longer than one chunk (sc_modprod_axis' chunk rule, sc_ctx_set_reduce_chunk included); otherwise reduce-then-scan: the totals of
+ * the full chunks by one k_prod_axis level (limb form, drift R^-(chunk - 1), absorbed by the next level's constant), their inclusive
+ * scan by the same plan, and one k_scan_axis launch in which chunk q starts from prefix q - 1.  All on the context's stream, no host
+ * round trip; totals and prefixes live in one grow-only temporary; the level constants share sc_modprod_axis' table of R^e mod n.
+ * Operands must be canonical, as for sc_modprod_axis, and the argument checks are that call's: null pointers, K >= 1,
+ * outer * K * inner * nwords <= 2^40 words, `out` must not overlap `x`, an empty outer or inner is SC_OK, a modulus without an
+ * instance is SC_ERR_ARG.  Launches are counted in sc_ctx_launch_counts under  L | G << 8 | 29 << 16 | 1 << 29  (the totals' under
+ * bit 28). */
+int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out_dptr);
 
 /* ---- Paillier pieces that are not plain residue products --------------------------------------- */
 /* out[i] = 1 + m[i] * N mod N^2 (g = N+1 encryption without randomness: unsafe_encrypt(..) of

@@ -1,6 +1,7 @@
 """MI355X-native batched secure comparison (DGK/Veugen protocol): the Paillier / DGK arithmetic underneath
 Initiator.step_* and KeyHolder.step_* as hand-written HIP kernels behind a C ABI (libsc_amd.so)."""
-from .aggregate import (secure_groupby_count_batch, secure_groupby_sum_batch, secure_histogram_batch, secure_majority_batch, sum_planes_batch,
+from .aggregate import (cumsum_planes_batch, cumsum_rows_batch, secure_cdf_batch, secure_groupby_count_batch, secure_groupby_sum_batch,
+                        secure_histogram_batch, secure_histogram_median_batch, secure_majority_batch, secure_quantile_batch, sum_planes_batch,
                         sum_rows_batch)
 from .communicator import Communicator, InMemoryCommunicator, StreamCommunicator
 from .dotproduct import (DotDraws, DotLayout, draw_dot, secure_dot_batch, secure_squared_distance_batch, secure_sum_squares_batch)
@@ -14,7 +15,8 @@ from .selection import secure_argmax_batch, secure_argmin_batch, secure_maximum_
 from .sorting import secure_kth_batch, secure_median_batch, secure_sort_batch, secure_topk_batch
 from .utils import from_bits, to_bits
 
-__all__ = ["sum_planes_batch", "sum_rows_batch", "secure_histogram_batch", "secure_majority_batch", "secure_groupby_count_batch",
+__all__ = ["sum_planes_batch", "sum_rows_batch", "cumsum_planes_batch", "cumsum_rows_batch", "secure_cdf_batch", "secure_quantile_batch",
+           "secure_histogram_median_batch", "secure_histogram_batch", "secure_majority_batch", "secure_groupby_count_batch",
            "secure_groupby_sum_batch", "Communicator", "InMemoryCommunicator", "StreamCommunicator", "Initiator", "KeyHolder", "from_bits", "to_bits", "Paillier", "PaillierCiphertext", "DGK",
            "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch",
            "secure_sort_batch", "secure_topk_batch", "secure_kth_batch", "secure_median_batch", "MulLayout", "MulDraws", "draw_mul",

@@ -1,4 +1,5 @@
-"""Sums of encrypted arrays along an axis, and the histogram, majority vote and group-by that follow from them.
+"""Sums and running sums of encrypted arrays along an axis, and the histogram, majority vote, group-by, cumulative distribution and
+quantile that follow from them.
 
 The sum of Paillier ciphertexts is their product modulo N^2.  sum_planes_batch / sum_rows_batch run it along one axis of an array with the
 dedicated kernel k_prod_axis (sc_paillier_sum_axis, include/sc_amd.h): a tree of chains of at most 32 members, one Montgomery product per
@@ -9,6 +10,11 @@ The two-party operations add no protocol of their own.  secure_histogram_batch i
 of a row, secure_majority_batch the argmax (selection.py) of that histogram, secure_groupby_count_batch / secure_groupby_sum_batch the
 one-hot encoding (times the value: multiplication.py) summed over the rows.  Their draws are the one-hot's, the multiplication's and the
 comparison's, in that order.
+
+cumsum_planes_batch / cumsum_rows_batch are the running sums along the same two axes with the kernel k_scan_axis
+(sc_paillier_cumsum_axis): two products per member, one launch when the array is wide enough across the axis, reduce-then-scan otherwise.
+secure_cdf_batch is the histogram followed by the running sum over its bins, secure_quantile_batch counts the bins whose cumulative count
+does not exceed the wanted rank with one comparison batch: the one-hot's draws, then the comparison's.
 """
 from __future__ import annotations
 
@@ -40,6 +46,29 @@ def reduce_plan(outer: int, K: int, inner: int, resident_groups: int, forced: in
         if nch == 1:
             return levels
         K = nch
+
+
+def scan_plan(outer: int, K: int, inner: int, resident_groups: int, forced: int = 0) -> list[tuple[str, int, int, int]]:
+    """The launches (kind, K, chunk, chains) of sc_modscan_axis in order, as scan_plan in csrc/sc_lib.hip decides them.  Direct -- one
+    "scan" launch, one chain per (outer, inner) running the whole K -- when outer * inner chains fill `resident_groups` group slots
+    (num_cu * 8 * 64 / G) by themselves or K is no longer than one chunk of reduce_plan's rule; otherwise blocked: a "totals" launch
+    (k_prod_axis) over the ceil(K / chunk) - 1 full chunks that are followed by another, the launches of the scan of those totals by the
+    same rule, and one seeded "scan" launch with a chain per chunk.  `forced` (2 .. 32, Engine.set_reduce_chunk) is the chunk length
+    of every level and blocks every level longer than itself."""
+    outer, K, inner, forced = int(outer), int(K), int(inner), int(forced)
+    if K < 1 or outer < 1 or inner < 1 or resident_groups < 1:
+        raise ValueError("scan_plan: expected positive sizes")
+    if forced != 0 and not 2 <= forced <= MAX_CHUNK:
+        raise ValueError(f"forced chunk {forced}: expected 0 or 2 .. {MAX_CHUNK}")
+    down, up = [], []
+    while True:
+        c = forced if forced else min(MAX_CHUNK, max(MIN_CHUNK, -(-outer * K * inner // resident_groups)))
+        if (not forced and outer * inner >= resident_groups) or K <= c:
+            return down + [("scan", K, K, outer * inner)] + up[::-1]
+        nch = -(-K // c)
+        down.append(("totals", K, c, outer * (nch - 1) * inner))
+        up.append(("scan", K, c, outer * nch * inner))
+        K = nch - 1
 
 
 def _rerandomize(out: torch.Tensor, paillier: Paillier, rho: torch.Tensor | None) -> torch.Tensor:
@@ -90,6 +119,49 @@ def sum_rows_batch(x_enc: torch.Tensor, paillier: Paillier, segment: int | None 
     return _rerandomize(out.reshape(shape), paillier, rho)
 
 
+def _shift_exclusive(inc: torch.Tensor, outer: int, K: int, inner: int) -> torch.Tensor:
+    """The exclusive scan from the inclusive one: one position later along the axis, the residue 1 (the unrandomized [[0]]) first."""
+    v = inc.reshape(outer, K, inner, inc.shape[-1])
+    out = torch.empty_like(v)
+    out[:, 1:] = v[:, :-1]
+    out[:, 0] = 0
+    out[:, 0, :, 0] = 1
+    return out
+
+
+def cumsum_planes_batch(x_enc: torch.Tensor, paillier: Paillier, exclusive: bool = False, rho: torch.Tensor | None = None) -> torch.Tensor:
+    """[[sum_{j' <= j} x[j'][b]]] for x_enc [k][B][2nw] -> [k][B][2nw]: the running sum over the planes, geometry (outer, K, inner) =
+    (1, k, B).  exclusive: [[sum_{j' < j}]] instead, plane 0 the residue 1 (the unrandomized [[0]]).  The result is a deterministic
+    function of the inputs: pass rho [k][B][nw] before handing it on; it re-randomizes every output."""
+    x = _cipher_array(x_enc, 3, "x_enc")
+    if x.dim() != 3 or x.shape[0] < 1:
+        raise ValueError("x_enc: expected [k][B][words] with k >= 1")
+    k, B, _ = x.shape
+    out = paillier.engine.paillier_cumsum_axis(paillier.key, x, 1, k, B)
+    if exclusive:
+        out = _shift_exclusive(out, 1, k, B)
+    return _rerandomize(out.reshape(x.shape), paillier, rho)
+
+
+def cumsum_rows_batch(x_enc: torch.Tensor, paillier: Paillier, segment: int | None = None, exclusive: bool = False,
+                      rho: torch.Tensor | None = None) -> torch.Tensor:
+    """[[sum_{b' <= b} x[..][b']]] over the rows of every plane of x_enc [..., B][2nw] -> the same shape; with `segment` the running sum
+    starts again every `segment` rows (segment must divide B: ValueError).  Geometry (planes * B / segment, segment, 1).  exclusive:
+    [[sum_{b' < b}]] instead, the first row of every scan the residue 1 (the unrandomized [[0]]) -- the offsets of a group-by.  The
+    result is a deterministic function of the inputs: pass rho (one [nw] row per output) before handing it on; it re-randomizes every
+    output."""
+    x = _cipher_array(x_enc, 2, "x_enc")
+    B, w = x.shape[-2], x.shape[-1]
+    if B < 1:
+        raise ValueError("x_enc: expected at least one row")
+    seg = check_segment(B, segment)
+    scans = x.numel() // (seg * w)
+    out = paillier.engine.paillier_cumsum_axis(paillier.key, x, scans, seg, 1)
+    if exclusive:
+        out = _shift_exclusive(out, scans, seg, 1)
+    return _rerandomize(out.reshape(x.shape), paillier, rho)
+
+
 # ---- histogram, majority, group-by ------------------------------------------------------------------------------------------------
 def secure_histogram_batch(index_enc: torch.Tensor, k: int, alice_paillier: Paillier, bob_paillier: Paillier, index_bits: int | None = None,
                            kappa: int = 40, draws: OnehotDraws | None = None, rho: torch.Tensor | None = None) -> torch.Tensor:
@@ -121,6 +193,79 @@ def secure_majority_batch(label_enc: torch.Tensor, k: int, alice_paillier: Paill
     counts = hist.permute(1, 0, 2).contiguous()                                           # [B][k][2nw]
     top, label = secure_argmax_batch(counts, count_bits(planes.shape[0]), alice_paillier, alice_dgk, bob_paillier, bob_dgk, kappa)
     return label, top
+
+
+# ---- cumulative distribution, quantile ---------------------------------------------------------------------------------------------
+def secure_cdf_batch(index_enc: torch.Tensor, k: int, alice_paillier: Paillier, bob_paillier: Paillier, index_bits: int | None = None,
+                     kappa: int = 40, draws: OnehotDraws | None = None, rho: torch.Tensor | None = None) -> torch.Tensor:
+    """[[#{q : i_q mod k <= t}]], t < k, for B rows of m encrypted indices each: index_enc [m][B][2nw] -> [k][B][2nw].  The histogram
+    (one round trip), then the running sum over its k bins; the last plane is [[m]].  rho [k][B][nw] re-randomizes every output."""
+    hist = secure_histogram_batch(index_enc, k, alice_paillier, bob_paillier, index_bits, kappa, draws)
+    return cumsum_planes_batch(hist, alice_paillier, rho=rho)
+
+
+def check_rank(kth, m: int, B: int, words: int):
+    """The rank argument of secure_quantile_batch over m values per row: a public integer 0 <= kth < m, or [B][words] encrypted ranks
+    (returned as they are); ValueError otherwise, and when a count of up to m does not fit the comparison's 255 bits."""
+    if count_bits(m) > 255:
+        raise ValueError(f"m = {m}: counts of {count_bits(m)} bits exceed the comparison's 255")
+    if isinstance(kth, torch.Tensor):
+        if kth.dim() != 2 or tuple(kth.shape) != (B, words):
+            raise ValueError(f"kth: expected an integer or [{B}][{words}] encrypted ranks")
+        return kth.contiguous()
+    if isinstance(kth, bool) or not isinstance(kth, int):
+        raise ValueError(f"kth = {kth!r}: expected an integer or encrypted ranks")
+    if not 0 <= kth < m:
+        raise ValueError(f"kth = {kth}: expected 0 .. {m - 1}")
+    return kth
+
+
+def _rank_rows(kth, planes: int, B: int, paillier: Paillier) -> torch.Tensor:
+    """[[kth]] for `planes` x B comparison rows, [planes * B][2nw]: the public rank unrandomized, the encrypted one repeated per plane."""
+    engine, nw = paillier.engine, paillier.mod_n.nwords
+    if isinstance(kth, torch.Tensor):
+        return kth.unsqueeze(0).expand(planes, B, kth.shape[-1]).reshape(planes * B, -1).contiguous()
+    return paillier.encrypt_raw_batch(engine.upload([kth] * (planes * B), nw))
+
+
+def _zero_rows(B: int, paillier: Paillier) -> torch.Tensor:
+    return paillier.encrypt_raw_batch(paillier.engine.upload([0] * B, paillier.mod_n.nwords))
+
+
+def secure_quantile_batch(index_enc: torch.Tensor, k: int, kth, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
+                          index_bits: int | None = None, kappa: int = 40, draws: OnehotDraws | None = None, comparison_draws=None) -> torch.Tensor:
+    """[[the bin of rank kth]] among the m binned values i_q mod k of every row (0 = the smallest, 0 <= kth < m, as secure_kth_batch counts):
+    index_enc [m][B][2nw] -> [B][2nw].  kth: a public integer, or [B][2nw] encrypted ranks, one per row.  The cumulative distribution
+    (secure_cdf_batch), then the answer #{t < k - 1 : cdf_t <= kth}: one comparison batch over (k - 1) B rows with l = bits(m) and the sum
+    of its bits over the planes; the last plane of the distribution is m and is never compared, and k = 1 runs no comparison and returns
+    [[0]].  ValueError, before any launch, for a public kth outside 0 .. m - 1, a kth that is neither an integer nor [B][2nw], and
+    bits(m) > 255.  Draws: the one-hot's (`draws`), then the comparison's (`comparison_draws`, a batch.BatchDraws over (k - 1) B rows)."""
+    from .batch import secure_comparison_batch
+    from .selection import _comparison_draws
+
+    planes, _ = _as_planes(index_enc)
+    m, B, w = planes.shape
+    kth = check_rank(kth, m, B, w)
+    layout = _onehot_layout(planes, k, index_bits, kappa, alice_paillier)                 # the fit rule, before any launch
+    cdf = secure_cdf_batch(planes, k, alice_paillier, bob_paillier, index_bits, kappa, draws)
+    kk = layout.k
+    if kk == 1:
+        return _zero_rows(B, alice_paillier)
+    l, rows = count_bits(m), (kk - 1) * B
+    x = cdf[:kk - 1].reshape(rows, w).contiguous()
+    y = _rank_rows(kth, kk - 1, B, alice_paillier)
+    cd = comparison_draws if comparison_draws is not None else _comparison_draws(rows, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk)
+    bits = secure_comparison_batch(x, y, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, cd)
+    return sum_planes_batch(bits.reshape(kk - 1, B, w), alice_paillier)
+
+
+def secure_histogram_median_batch(index_enc: torch.Tensor, k: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier,
+                                  bob_dgk: DGK, index_bits: int | None = None, kappa: int = 40, draws: OnehotDraws | None = None,
+                                  comparison_draws=None) -> torch.Tensor:
+    """The lower median bin of every row: secure_quantile_batch with kth = (m - 1) // 2, as secure_median_batch chooses it."""
+    planes, _ = _as_planes(index_enc)
+    return secure_quantile_batch(planes, k, (planes.shape[0] - 1) // 2, alice_paillier, alice_dgk, bob_paillier, bob_dgk, index_bits, kappa,
+                                 draws, comparison_draws)
 
 
 def secure_groupby_count_batch(index_enc: torch.Tensor, k: int, alice_paillier: Paillier, bob_paillier: Paillier, index_bits: int | None = None,
@@ -176,7 +321,7 @@ def secure_groupby_sum_batch(value_enc: torch.Tensor, index_enc: torch.Tensor, k
     return sum_rows_batch(products.reshape(k, B, w), alice_paillier, rho=rho)
 
 
-# ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{histogram,majority,groupby_sum}_batch) ------------------
+# ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{histogram,majority,groupby_sum,cdf,quantile}_batch) -----
 # Sequences of the existing sessions -- one-hot, multiplication, the argmax's rounds -- with Alice's local sums in between: no message
 # id of their own and none changed.
 async def alice_histogram(ini, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks):
@@ -243,3 +388,37 @@ async def bob_groupby_sum(kh, k, bits, signed, index_bits, kappa, source, genera
     count = await bob_onehot(kh, k, 1, index_bits, kappa, None, source, generator, count)
     mul = groupby_sum_layout(bits, count, signed, kappa, kh.scheme_paillier)
     await bob_multiply(kh, bits, mul.wy[0], signed, kappa, None, source, generator, int(k) * count)
+
+
+async def alice_cdf(ini, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks):
+    hist = await alice_histogram(ini, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks)
+    return cumsum_planes_batch(hist, ini.scheme_paillier)
+
+
+async def bob_cdf(kh, k, m, index_bits, kappa, draws, source, generator, count=None):
+    return await bob_histogram(kh, k, m, index_bits, kappa, draws, source, generator, count)
+
+
+async def alice_quantile(ini, index_enc, k, kth, index_bits, kappa, source, engine, generator, chunks):
+    planes, _ = _as_planes(index_enc)
+    m, B, w = planes.shape
+    kth = check_rank(kth, m, B, w)
+    if ini.l_maximum_bit_length < count_bits(m):
+        raise ValueError(f"l = {ini.l_maximum_bit_length}: counts of up to {m} need {count_bits(m)} bits")
+    cdf = await alice_cdf(ini, planes, k, index_bits, kappa, None, source, engine, generator, chunks)
+    pai, kk = ini.scheme_paillier, cdf.shape[0]
+    if kk == 1:
+        return _zero_rows(B, pai)
+    x = cdf[:kk - 1].reshape((kk - 1) * B, w).contiguous()
+    bits = await ini.perform_secure_comparison_batch(x, _rank_rows(kth, kk - 1, B, pai), None, source, engine, generator)
+    return sum_planes_batch(bits.reshape(kk - 1, B, w), pai)
+
+
+async def bob_quantile(kh, k, m, index_bits, kappa, source, generator, count=None):
+    if count_bits(m) > 255:
+        raise ValueError(f"m = {m}: counts of {count_bits(m)} bits exceed the comparison's 255")
+    if kh.l_maximum_bit_length < count_bits(m):
+        raise ValueError(f"l = {kh.l_maximum_bit_length}: counts of up to {m} need {count_bits(m)} bits")
+    await bob_histogram(kh, k, m, index_bits, kappa, None, source, generator, count)
+    if int(k) > 1:
+        await kh.perform_secure_comparison_batch(None, source, generator)

@@ -1,8 +1,8 @@
 """Build libsc_amd.so (hipcc, gfx950) in-tree.  Used by __graft_entry__.build() and by hand.
 
-The library is twelve translation units: the host side (csrc/sc_lib.hip, no device code), the instances of the two interpreter
+The library is thirteen translation units: the host side (csrc/sc_lib.hip, no device code), the instances of the two interpreter
 kernels in three parts each (csrc/sc_launch_vm.hip / sc_launch_pvm.hip with -DSC_PART=0/1/2) and the remaining kernels
-(csrc/sc_launch_misc.hip; the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
+(csrc/sc_launch_misc.hip; the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip, the running product in csrc/sc_launch_scan.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
 so a change of host logic or policy costs seconds and a kernel change only the parts that hold that kernel.
 """
 from __future__ import annotations
@@ -27,7 +27,7 @@ UNITS = [("sc_lib", "sc_lib.hip", [])] + \
         [(f"sc_launch_pvm{p}", "sc_launch_pvm.hip", [f"-DSC_PART={p}"]) for p in range(3)] + \
         [("sc_launch_misc", "sc_launch_misc.hip", []), ("sc_launch_mul", "sc_launch_mul.hip", []),
          ("sc_launch_dot", "sc_launch_dot.hip", []), ("sc_launch_lookup", "sc_launch_lookup.hip", []),
-         ("sc_launch_reduce", "sc_launch_reduce.hip", [])]
+         ("sc_launch_reduce", "sc_launch_reduce.hip", []), ("sc_launch_scan", "sc_launch_scan.hip", [])]
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
     os.path.join(INCLUDE, "sc_amd.h"), os.path.join(INCLUDE, "sc_amd_dev.h")]
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)

@@ -1,7 +1,7 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
 // (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
-// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip and sc_launch_reduce.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip and sc_launch_scan.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -252,6 +252,8 @@ constexpr uint32_t launch_key(bool pvm, int G, int L, int W, bool neg1, bool sta
 }
 // the key of a k_prod_axis instance there: bit 28 set, L, G and W where the interpreters have them
 constexpr uint32_t reduce_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 28); }
+// ... and of a k_scan_axis instance: bit 29 set
+constexpr uint32_t scan_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 29); }
 // sc_launch_vm.hip / sc_launch_pvm.hip, parts 0 .. 2: launch the instance (G, L, W, NEG1[, STAMP]) of the interpreter on the context's
 // stream (grid, scratch arena and occupancy handled there); SC_ERR_UNSUPPORTED when the instance lives in another part
 int launch_vm_part0(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);
@@ -293,6 +295,10 @@ int launch_onehot_rotate(hipStream_t stream, const uint32_t* E, const int32_t* r
 // (G, L, W) has no instance
 int launch_prod_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* fin, const uint32_t* src, uint32_t* dst, uint64_t K,
                      uint64_t inner, uint32_t chunk, uint64_t nch, uint64_t nchains, int nwords, bool in_words, bool final);
+// sc_launch_scan.hip: one launch of the running product along an axis (k_scan_axis) on the context's stream; `seed` may be null;
+// SC_ERR_UNSUPPORTED when (G, L, W) has no instance
+int launch_scan_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* lift, const uint32_t* src, const uint32_t* seed,
+                     uint32_t* dst, uint64_t K, uint64_t inner, uint64_t chunk, uint64_t nch, uint64_t nchains, int nwords, bool in_words);
 // sc_launch_misc.hip again
 int launch_rng_bits(hipStream_t stream, const sc::RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count);
 int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, const uint32_t* d_n, int nbits, int nw, int nonzero, uint32_t* out, uint64_t count);

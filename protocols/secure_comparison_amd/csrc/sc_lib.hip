@@ -167,7 +167,7 @@ inline bool small_enough_to_fork(const sc_ctx* ctx, const Mod& m, uint64_t count
   return (count + per_wave - 1) / per_wave <= (uint64_t)ctx->num_cu * 4 / (uint64_t)ctx->chip_share;
 }
 
-enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_REDUCE = 6, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
+enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_REDUCE = 6, TMP_SCAN = 7, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
 
 // A u64 accumulator array of the context that is ZERO whenever no step is using it: cleared when it is (re)allocated, reset by its
 // reader afterwards (OP_TAKEFLAG).  The zero tests of step 4j OR their verdicts into it; no clearing launch inside a step.
@@ -1338,6 +1338,100 @@ int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
     // one product per member past the first of a chain; the last level's product with the closing factor
     ctx->mac_counter += (double)m.S * m.S * 2.0 * (double)outer * (double)inner * ((double)(lv.K - lv.nch) + (final ? 1.0 : 0.0));
     src = dst;
+  }
+  return SC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// running product along an axis: reduce-then-scan over k_prod_axis and k_scan_axis (sc_launch_scan.hip)
+// ------------------------------------------------------------------------------------------------
+// One level of the blocked scan: K members per scan in chunks of `chunk`, nch = ceil(K / chunk) of them; `members` original members
+// stand behind one member of this level (1 at the top), which therefore carries the drift R^-(members - 1).  A blocked level hands the
+// totals of its nch - 1 full chunks to the next level; the last level is direct: one chain per scan, no seed.
+struct ScanLevel { uint64_t K; uint64_t chunk; uint64_t nch; uint64_t members; bool blocked; };
+// Direct when the outer * inner scans fill every resident group slot by themselves, or K is no longer than one chunk; blocked
+// otherwise, with reduce_plan's chunk length.  A forced chunk length blocks every level longer than itself.
+// protocols/secure_comparison_amd/aggregate.py::scan_plan mirrors this for the tests.
+static std::vector<ScanLevel> scan_plan(uint64_t outer, uint64_t K, uint64_t inner, uint64_t resident_groups, int forced) {
+  std::vector<ScanLevel> lv;
+  uint64_t members = 1;
+  for (;;) {
+    const uint64_t total = outer * K * inner;
+    const uint64_t c = forced ? (uint64_t)forced : std::min<uint64_t>(32, std::max<uint64_t>(4, (total + resident_groups - 1) / resident_groups));
+    if ((!forced && outer * inner >= resident_groups) || K <= c) {
+      lv.push_back(ScanLevel{K, K, 1, members, false});
+      return lv;
+    }
+    const uint64_t nch = (K + c - 1) / c;
+    lv.push_back(ScanLevel{K, c, nch, members, true});
+    members *= c;
+    K = nch - 1;
+  }
+}
+
+int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out) {
+  if (!valid_mod(ctx, mod) || !x || !out) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: bad argument");
+  if (K < 1) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: K must be at least 1");
+  const Mod& m = ctx->mods[mod];
+  {
+    // outer * K * inner * nwords <= 2^40 words, checked factor by factor so that no product wraps
+    const uint64_t LIM = 1ull << 40;
+    uint64_t words = (uint64_t)m.nwords;
+    for (uint64_t f : {K, outer, inner}) {
+      if (f != 0 && words > LIM / f) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: outer * K * inner * nwords exceeds 2^40 words");
+      words *= f;
+    }
+  }
+  if (outer == 0 || inner == 0) return SC_OK;
+  {
+    const size_t bytes = (size_t)outer * K * inner * m.nwords * 4;
+    const char *xb = (const char*)x, *ob = (const char*)out;
+    if (xb < ob + bytes && ob < xb + bytes) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: out overlaps x (in-place scan is not supported)");
+  }
+  if (m.W != 29 || m.G < 2 || m.small_c != 0)
+    return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: no k_scan_axis instance for configuration (G=%d, L=%d, W=%d%s)", m.G, m.L, m.W, m.small_c ? ", NEG1" : "");
+  const std::vector<ScanLevel> plan = scan_plan(outer, K, inner, (uint64_t)ctx->num_cu * 8 * (64 / m.G), ctx->reduce_chunk);
+  const size_t D = plan.size() - 1;                  // blocked levels
+  // level v < D keeps, in one temporary, the totals of its full chunks (limb form) and their prefixes (word form), outer * K_(v+1) * inner each
+  std::vector<uint32_t*> totals(D, nullptr), prefix(D, nullptr);
+  if (D) {
+    size_t need = 0;
+    for (size_t v = 0; v < D; v++) need += (size_t)outer * plan[v + 1].K * inner * ((size_t)m.S + m.nwords);
+    uint32_t* buf = nullptr;
+    int rc = tmp_buf(ctx, TMP_SCAN, need * 4, (void**)&buf); if (rc) return rc;
+    for (size_t v = 0; v < D; v++) {
+      const size_t cnt = (size_t)outer * plan[v + 1].K * inner;
+      totals[v] = buf; buf += cnt * m.S;
+      prefix[v] = buf; buf += cnt * m.nwords;
+    }
+  }
+  // the level constants R^(members + 1).  A full table of constants is emptied while one is built, which would orphan those fetched
+  // before it in this call: a second pass, which finds the few of them in a table just emptied, takes the pointers.
+  std::vector<const uint32_t*> lift(plan.size(), nullptr);
+  for (int pass = 0; pass < 2; pass++)
+    for (size_t v = 0; v < plan.size(); v++) { int rc = reduce_closing_const(ctx, mod, plan[v].members + 1, &lift[v]); if (rc) return rc; }
+  const uint32_t* dummy_fin = lift[0];               // a level that is not final reads S limbs of it and uses none
+  auto unsupported = [&]() { return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: no k_scan_axis instance for configuration (G=%d, L=%d, W=%d)", m.G, m.L, m.W); };
+  // down: the totals of every blocked level's full chunks, one product per member past the first of a chunk
+  for (size_t v = 0; v < D; v++) {
+    const ScanLevel& lv = plan[v];
+    const uint32_t* src = v == 0 ? x : totals[v - 1];
+    int rc = launch_prod_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, dummy_fin, src, totals[v], lv.K, inner, (uint32_t)lv.chunk, lv.nch - 1, outer * (lv.nch - 1) * inner,
+                              m.nwords, v == 0, false);
+    if (rc == SC_ERR_UNSUPPORTED) return unsupported();
+    if (rc) return rc;
+    ctx->mac_counter += (double)m.S * m.S * 2.0 * (double)outer * (double)inner * (double)(lv.nch - 1) * (double)(lv.chunk - 1);
+  }
+  // up: the direct scan of the deepest level, then every blocked level seeded with the prefixes of the level below it
+  for (size_t v = D + 1; v-- > 0;) {
+    const ScanLevel& lv = plan[v];
+    const uint32_t* src = v == 0 ? x : totals[v - 1];
+    uint32_t* dst = v == 0 ? out : prefix[v - 1];
+    int rc = launch_scan_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, lift[v], src, lv.blocked ? prefix[v] : nullptr, dst, lv.K, inner, lv.chunk, lv.nch,
+                              outer * lv.nch * inner, m.nwords, v == 0);
+    if (rc == SC_ERR_UNSUPPORTED) return unsupported();
+    if (rc) return rc;
+    ctx->mac_counter += (double)m.S * m.S * 2.0 * 2.0 * (double)outer * (double)inner * (double)lv.K;
   }
   return SC_OK;
 }

@@ -538,6 +538,29 @@ class Engine:
         self._check(self.lib.sc_paillier_sum_axis(self.ctx, key.id, self._ptr(c), outer, K, inner, self._ptr(out)))
         return out
 
+    def _scan_args(self, x: torch.Tensor, outer: int, K: int, inner: int, nwords: int, out: torch.Tensor | None):
+        outer, K, inner = int(outer), int(K), int(inner)
+        if min(outer, K, inner) < 0:
+            raise ValueError("outer, K, inner: expected non-negative sizes")
+        self._arr(x, "x", outer * K * inner, nwords)
+        return outer, K, inner, self._out(out, outer * K * inner, nwords)
+
+    def modscan_axis(self, mod: Modulus, x: torch.Tensor, outer: int, K: int, inner: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The inclusive running product along the middle axis of x viewed as [outer][K][inner][nwords]: [outer * K * inner][nwords]
+        (sc_modscan_axis)."""
+        outer, K, inner, out = self._scan_args(x, outer, K, inner, mod.nwords, out)
+        self._sync_stream()
+        self._check(self.lib.sc_modscan_axis(self.ctx, mod.id, self._ptr(x), outer, K, inner, self._ptr(out)))
+        return out
+
+    def paillier_cumsum_axis(self, key: PaillierKey, c: torch.Tensor, outer: int, K: int, inner: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The inclusive running homomorphic sum along the middle axis of c viewed as [outer][K][inner][2nw]: [outer * K * inner][2nw]
+        (sc_paillier_cumsum_axis)."""
+        outer, K, inner, out = self._scan_args(c, outer, K, inner, key.mod_n2.nwords, out)
+        self._sync_stream()
+        self._check(self.lib.sc_paillier_cumsum_axis(self.ctx, key.id, self._ptr(c), outer, K, inner, self._ptr(out)))
+        return out
+
     def set_reduce_chunk(self, c: int) -> None:
         """Chunk length of the axis product's tree (sc_ctx_set_reduce_chunk): 0 automatic, 2 .. 32 that length at every level."""
         self._check(self.lib.sc_ctx_set_reduce_chunk(self.ctx, int(c)))
@@ -1335,7 +1358,7 @@ class Engine:
 
     def launch_counts(self) -> dict:
         """{(kind, G, L, W, neg1, stamp, dig): launches} per compiled interpreter instance since the context was created
-        (sc_ctx_launch_counts); kind is "vm", "pvm" or "reduce" (k_prod_axis)."""
+        (sc_ctx_launch_counts); kind is "vm", "pvm", "reduce" (k_prod_axis) or "scan" (k_scan_axis)."""
         n = C.c_int()
         self._check(self.lib.sc_ctx_launch_counts(self.ctx, None, None, 0, C.byref(n)))
         cap = max(1, n.value)
@@ -1343,7 +1366,7 @@ class Engine:
         self._check(self.lib.sc_ctx_launch_counts(self.ctx, keys, counts, cap, C.byref(n)))
         out = {}
         for k, v in zip(keys[:n.value], counts[:n.value]):
-            out[("reduce" if k >> 28 & 1 else "pvm" if k >> 27 & 1 else "vm", k >> 8 & 0xff, k & 0xff, k >> 16 & 0xff, bool(k >> 24 & 1), bool(k >> 25 & 1), bool(k >> 26 & 1))] = int(v)
+            out[("scan" if k >> 29 & 1 else "reduce" if k >> 28 & 1 else "pvm" if k >> 27 & 1 else "vm", k >> 8 & 0xff, k & 0xff, k >> 16 & 0xff, bool(k >> 24 & 1), bool(k >> 25 & 1), bool(k >> 26 & 1))] = int(v)
         return out
 
     def set_chip_share(self, contexts: int) -> None:

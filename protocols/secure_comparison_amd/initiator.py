@@ -509,6 +509,23 @@ class Initiator:
 
         return await alice_majority(self, label_enc, k, index_bits, kappa, source, engine, generator, chunks)
 
+    async def perform_secure_cdf_batch(self, index_enc: torch.Tensor, k: int, index_bits: int | None = None, kappa: int = 40, draws=None,
+                                       source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[#{q : i_q mod k <= t}]] [k][B][2nw] from index_enc [m][B][2nw] as aggregate.secure_cdf_batch: the one-hot session, then the
+        local sum over the indices and the local running sum over the bins."""
+        from .aggregate import alice_cdf
+
+        return await alice_cdf(self, index_enc, k, index_bits, kappa, draws, source, engine, generator, chunks)
+
+    async def perform_secure_quantile_batch(self, index_enc: torch.Tensor, k: int, kth, index_bits: int | None = None, kappa: int = 40,
+                                            source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[the bin of rank kth]] [B][2nw] from index_enc [m][B][2nw] as aggregate.secure_quantile_batch (kth a public integer or [B][2nw]
+        encrypted ranks): the one-hot session, the local sums, then one comparison session over (k - 1) B rows at this initiator's l (at
+        least bits(m): ValueError) and the local sum of its bits.  k = 1 opens no comparison session."""
+        from .aggregate import alice_quantile
+
+        return await alice_quantile(self, index_enc, k, kth, index_bits, kappa, source, engine, generator, chunks)
+
     async def perform_secure_groupby_sum_batch(self, value_enc: torch.Tensor, index_enc: torch.Tensor, k: int, bits: int, signed: bool = False,
                                                index_bits: int | None = None, kappa: int = 40, source: str = "device", engine=None,
                                                generator=None, chunks: int = 1) -> torch.Tensor:

@@ -378,6 +378,20 @@ class KeyHolder:
 
         await bob_majority(self, k, m, index_bits, kappa, source, generator, count)
 
+    async def perform_secure_cdf_batch(self, k: int, m: int = 1, index_bits: int | None = None, kappa: int = 40, draws=None,
+                                       source: str = "device", generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_cdf_batch: the one-hot session for m indices per row (the sums are Alice's)."""
+        from .aggregate import bob_cdf
+
+        await bob_cdf(self, k, m, index_bits, kappa, draws, source, generator, count)
+
+    async def perform_secure_quantile_batch(self, k: int, m: int, index_bits: int | None = None, kappa: int = 40, source: str = "device",
+                                            generator=None, count: int | None = None) -> None:
+        """Bob's side of Initiator.perform_secure_quantile_batch: the one-hot session, then -- unless k = 1 -- one comparison session."""
+        from .aggregate import bob_quantile
+
+        await bob_quantile(self, k, m, index_bits, kappa, source, generator, count)
+
     async def perform_secure_groupby_sum_batch(self, k: int, bits: int, signed: bool = False, index_bits: int | None = None, kappa: int = 40,
                                                source: str = "device", generator=None, count: int | None = None) -> None:
         """Bob's side of Initiator.perform_secure_groupby_sum_batch: the one-hot session with m = 1, then the multiplication session over
