@@ -24,23 +24,32 @@ from .lookup import OnehotDraws, _as_planes, _layout as _onehot_layout, draw_one
 from .multiplication import MulDraws, MulLayout, draw_mul, mul_batch
 from .schemes import DGK, Paillier
 
-MIN_CHUNK, MAX_CHUNK = 4, 32        # automatic chunk lengths of a level (reduce_plan in csrc/sc_lib.hip)
+MIN_CHUNK, MAX_CHUNK = 4, 32        # automatic chunk lengths of a level (axis_chunk in csrc/sc_axis_plan.h)
+
+
+def _axis_chunk(total: int, resident_groups: int, forced: int) -> int:
+    """The chunk length of a level of `total` members, as axis_chunk in csrc/sc_axis_plan.h: the shortest of 4 .. 32 members whose chains
+    still fill `resident_groups` group slots (num_cu * 8 * 64 / G), or `forced` (2 .. 32, Engine.set_reduce_chunk) at every level."""
+    return forced if forced else min(MAX_CHUNK, max(MIN_CHUNK, -(-total // resident_groups)))
+
+
+def _plan_args(name: str, outer: int, K: int, inner: int, resident_groups: int, forced: int) -> tuple[int, int, int, int]:
+    outer, K, inner, forced = int(outer), int(K), int(inner), int(forced)
+    if K < 1 or outer < 1 or inner < 1 or resident_groups < 1:
+        raise ValueError(f"{name}: expected positive sizes")
+    if forced != 0 and not 2 <= forced <= MAX_CHUNK:
+        raise ValueError(f"forced chunk {forced}: expected 0 or 2 .. {MAX_CHUNK}")
+    return outer, K, inner, forced
 
 
 def reduce_plan(outer: int, K: int, inner: int, resident_groups: int, forced: int = 0) -> list[tuple[int, int, int]]:
-    """The levels (K, chunk, chains per output) of sc_modprod_axis' tree, as reduce_plan in csrc/sc_lib.hip computes them: a level cuts
-    the K members of an output into ceil(K / chunk) chains and hands that many partials to the next level, until one is left.  chunk: the
-    shortest of 4 .. 32 members whose chains still fill `resident_groups` group slots (num_cu * 8 * 64 / G), or `forced` (2 .. 32,
-    Engine.set_reduce_chunk) at every level; never more than K."""
-    outer, K, inner, forced = int(outer), int(K), int(inner), int(forced)
-    if K < 1 or outer < 1 or inner < 1 or resident_groups < 1:
-        raise ValueError("reduce_plan: expected positive sizes")
-    if forced != 0 and not 2 <= forced <= MAX_CHUNK:
-        raise ValueError(f"forced chunk {forced}: expected 0 or 2 .. {MAX_CHUNK}")
+    """The levels (K, chunk, chains per output) of sc_modprod_axis' tree, as reduce_plan in csrc/sc_axis_plan.h computes them: a level
+    cuts the K members of an output into ceil(K / chunk) chains and hands that many partials to the next level, until one is left.
+    chunk: axis_chunk's, never more than K."""
+    outer, K, inner, forced = _plan_args("reduce_plan", outer, K, inner, resident_groups, forced)
     levels = []
     while True:
-        c = forced if forced else min(MAX_CHUNK, max(MIN_CHUNK, -(-outer * K * inner // resident_groups)))
-        c = min(c, K)
+        c = min(_axis_chunk(outer * K * inner, resident_groups, forced), K)
         nch = -(-K // c)
         levels.append((K, c, nch))
         if nch == 1:
@@ -49,20 +58,16 @@ def reduce_plan(outer: int, K: int, inner: int, resident_groups: int, forced: in
 
 
 def scan_plan(outer: int, K: int, inner: int, resident_groups: int, forced: int = 0) -> list[tuple[str, int, int, int]]:
-    """The launches (kind, K, chunk, chains) of sc_modscan_axis in order, as scan_plan in csrc/sc_lib.hip decides them.  Direct -- one
-    "scan" launch, one chain per (outer, inner) running the whole K -- when outer * inner chains fill `resident_groups` group slots
-    (num_cu * 8 * 64 / G) by themselves or K is no longer than one chunk of reduce_plan's rule; otherwise blocked: a "totals" launch
+    """The launches (kind, K, chunk, chains) of sc_modscan_axis in order, as scan_plan in csrc/sc_axis_plan.h decides them.  Direct --
+    one "scan" launch, one chain per (outer, inner) running the whole K -- when outer * inner chains fill `resident_groups` group slots
+    (num_cu * 8 * 64 / G) by themselves or K is no longer than one chunk of axis_chunk's rule; otherwise blocked: a "totals" launch
     (k_prod_axis) over the ceil(K / chunk) - 1 full chunks that are followed by another, the launches of the scan of those totals by the
     same rule, and one seeded "scan" launch with a chain per chunk.  `forced` (2 .. 32, Engine.set_reduce_chunk) is the chunk length
     of every level and blocks every level longer than itself."""
-    outer, K, inner, forced = int(outer), int(K), int(inner), int(forced)
-    if K < 1 or outer < 1 or inner < 1 or resident_groups < 1:
-        raise ValueError("scan_plan: expected positive sizes")
-    if forced != 0 and not 2 <= forced <= MAX_CHUNK:
-        raise ValueError(f"forced chunk {forced}: expected 0 or 2 .. {MAX_CHUNK}")
+    outer, K, inner, forced = _plan_args("scan_plan", outer, K, inner, resident_groups, forced)
     down, up = [], []
     while True:
-        c = forced if forced else min(MAX_CHUNK, max(MIN_CHUNK, -(-outer * K * inner // resident_groups)))
+        c = _axis_chunk(outer * K * inner, resident_groups, forced)
         if (not forced and outer * inner >= resident_groups) or K <= c:
             return down + [("scan", K, K, outer * inner)] + up[::-1]
         nch = -(-K // c)
@@ -84,14 +89,12 @@ def _cipher_array(x_enc, min_dim: int, name: str) -> torch.Tensor:
     return x_enc.contiguous()
 
 
-def sum_planes_batch(x_enc: torch.Tensor, paillier: Paillier, rho: torch.Tensor | None = None) -> torch.Tensor:
-    """[[sum_j x[j][b]]] for x_enc [k][B][2nw] -> [B][2nw]: the sum over the planes, geometry (outer, K, inner) = (1, k, B).
-    rho [B][nw] (optional) re-randomizes the result."""
+def _planes_geometry(x_enc) -> tuple[torch.Tensor, tuple[int, int, int]]:
+    """x_enc [k][B][words], k >= 1, contiguous, and its geometry (outer, K, inner) = (1, k, B) along the planes."""
     x = _cipher_array(x_enc, 3, "x_enc")
     if x.dim() != 3 or x.shape[0] < 1:
         raise ValueError("x_enc: expected [k][B][words] with k >= 1")
-    k, B, _ = x.shape
-    return _rerandomize(paillier.engine.paillier_sum_axis(paillier.key, x, 1, k, B), paillier, rho)
+    return x, (1, x.shape[0], x.shape[1])
 
 
 def check_segment(B: int, segment: int | None) -> int:
@@ -104,43 +107,51 @@ def check_segment(B: int, segment: int | None) -> int:
     return segment
 
 
-def sum_rows_batch(x_enc: torch.Tensor, paillier: Paillier, segment: int | None = None, rho: torch.Tensor | None = None) -> torch.Tensor:
-    """[[sum_b x[..][b]]] over the rows of every plane of x_enc [..., B][2nw] -> [...][2nw]; with `segment` one total per run of `segment`
-    consecutive rows -> [..., B / segment][2nw] (segment must divide B: ValueError).  Geometry (planes * B / segment, segment, 1).
-    rho (one [nw] row per result, optional) re-randomizes the results."""
+def _rows_geometry(x_enc, segment: int | None) -> tuple[torch.Tensor, tuple[int, int, int]]:
+    """x_enc [..., B][words], B >= 1, contiguous, and its geometry (planes * B / segment, segment, 1) along the rows."""
     x = _cipher_array(x_enc, 2, "x_enc")
     B, w = x.shape[-2], x.shape[-1]
     if B < 1:
         raise ValueError("x_enc: expected at least one row")
     seg = check_segment(B, segment)
-    planes = x.numel() // (B * w)
-    out = paillier.engine.paillier_sum_axis(paillier.key, x, planes * (B // seg), seg, 1)
-    shape = tuple(x.shape[:-2]) + (() if segment is None else (B // seg,)) + (w,)
+    return x, (x.numel() // (seg * w), seg, 1)
+
+
+def sum_planes_batch(x_enc: torch.Tensor, paillier: Paillier, rho: torch.Tensor | None = None) -> torch.Tensor:
+    """[[sum_j x[j][b]]] for x_enc [k][B][2nw] -> [B][2nw]: the sum over the planes, geometry (outer, K, inner) = (1, k, B).
+    rho [B][nw] (optional) re-randomizes the result."""
+    x, geometry = _planes_geometry(x_enc)
+    return _rerandomize(paillier.engine.paillier_sum_axis(paillier.key, x, *geometry), paillier, rho)
+
+
+def sum_rows_batch(x_enc: torch.Tensor, paillier: Paillier, segment: int | None = None, rho: torch.Tensor | None = None) -> torch.Tensor:
+    """[[sum_b x[..][b]]] over the rows of every plane of x_enc [..., B][2nw] -> [...][2nw]; with `segment` one total per run of `segment`
+    consecutive rows -> [..., B / segment][2nw] (segment must divide B: ValueError).  Geometry (planes * B / segment, segment, 1).
+    rho (one [nw] row per result, optional) re-randomizes the results."""
+    x, geometry = _rows_geometry(x_enc, segment)
+    out = paillier.engine.paillier_sum_axis(paillier.key, x, *geometry)
+    shape = tuple(x.shape[:-2]) + (() if segment is None else (x.shape[-2] // geometry[1],)) + (x.shape[-1],)
     return _rerandomize(out.reshape(shape), paillier, rho)
 
 
-def _shift_exclusive(inc: torch.Tensor, outer: int, K: int, inner: int) -> torch.Tensor:
-    """The exclusive scan from the inclusive one: one position later along the axis, the residue 1 (the unrandomized [[0]]) first."""
-    v = inc.reshape(outer, K, inner, inc.shape[-1])
-    out = torch.empty_like(v)
-    out[:, 1:] = v[:, :-1]
-    out[:, 0] = 0
-    out[:, 0, :, 0] = 1
-    return out
+def _cumsum(x: torch.Tensor, geometry: tuple[int, int, int], paillier: Paillier, exclusive: bool, rho: torch.Tensor | None) -> torch.Tensor:
+    """The running sum of x along the middle axis of `geometry`, in the shape of x.  The exclusive one is the inclusive one a position
+    later along the axis, the residue 1 (the unrandomized [[0]]) first."""
+    out = paillier.engine.paillier_cumsum_axis(paillier.key, x, *geometry)
+    if exclusive:
+        v = out.reshape(*geometry, out.shape[-1])
+        out = torch.empty_like(v)
+        out[:, 1:] = v[:, :-1]
+        out[:, 0] = 0
+        out[:, 0, :, 0] = 1
+    return _rerandomize(out.reshape(x.shape), paillier, rho)
 
 
 def cumsum_planes_batch(x_enc: torch.Tensor, paillier: Paillier, exclusive: bool = False, rho: torch.Tensor | None = None) -> torch.Tensor:
     """[[sum_{j' <= j} x[j'][b]]] for x_enc [k][B][2nw] -> [k][B][2nw]: the running sum over the planes, geometry (outer, K, inner) =
     (1, k, B).  exclusive: [[sum_{j' < j}]] instead, plane 0 the residue 1 (the unrandomized [[0]]).  The result is a deterministic
     function of the inputs: pass rho [k][B][nw] before handing it on; it re-randomizes every output."""
-    x = _cipher_array(x_enc, 3, "x_enc")
-    if x.dim() != 3 or x.shape[0] < 1:
-        raise ValueError("x_enc: expected [k][B][words] with k >= 1")
-    k, B, _ = x.shape
-    out = paillier.engine.paillier_cumsum_axis(paillier.key, x, 1, k, B)
-    if exclusive:
-        out = _shift_exclusive(out, 1, k, B)
-    return _rerandomize(out.reshape(x.shape), paillier, rho)
+    return _cumsum(*_planes_geometry(x_enc), paillier, exclusive, rho)
 
 
 def cumsum_rows_batch(x_enc: torch.Tensor, paillier: Paillier, segment: int | None = None, exclusive: bool = False,
@@ -150,16 +161,7 @@ def cumsum_rows_batch(x_enc: torch.Tensor, paillier: Paillier, segment: int | No
     [[sum_{b' < b}]] instead, the first row of every scan the residue 1 (the unrandomized [[0]]) -- the offsets of a group-by.  The
     result is a deterministic function of the inputs: pass rho (one [nw] row per output) before handing it on; it re-randomizes every
     output."""
-    x = _cipher_array(x_enc, 2, "x_enc")
-    B, w = x.shape[-2], x.shape[-1]
-    if B < 1:
-        raise ValueError("x_enc: expected at least one row")
-    seg = check_segment(B, segment)
-    scans = x.numel() // (seg * w)
-    out = paillier.engine.paillier_cumsum_axis(paillier.key, x, scans, seg, 1)
-    if exclusive:
-        out = _shift_exclusive(out, scans, seg, 1)
-    return _rerandomize(out.reshape(x.shape), paillier, rho)
+    return _cumsum(*_rows_geometry(x_enc, segment), paillier, exclusive, rho)
 
 
 # ---- histogram, majority, group-by ------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
 // (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
-// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip and sc_launch_scan.hip; sc_lib.hip (+ sc_families.h, sc_schemes.h) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip and sc_launch_scan.hip (the
+// last two share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
+// the HIP-free plans and checks of the two axis entries) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -234,7 +236,7 @@ struct sc_ctx {
   uint64_t* stamps = nullptr;                               // sc_clock_probe: the next (4,18,neg1) pair launch runs its stamping twin
   uint32_t stamp_grid = 0;                                  // ... and reports its grid size here
   int reduce_chunk = 0;                                     // sc_ctx_set_reduce_chunk: 0 automatic, 2 .. 32 the chunk length of every level
-  // (mod, K) -> limbs of R^K mod n, sc_modprod_axis' closing factor: the device copy and the pinned host buffer it is filled from (bounded)
+  // (mod, e) -> limbs of R^e mod n (mont_power_limbs): the device copy and the pinned host buffer it is filled from (bounded)
   std::map<std::pair<int, uint64_t>, std::pair<uint32_t*, uint32_t*>> reduce_consts;
 };
 

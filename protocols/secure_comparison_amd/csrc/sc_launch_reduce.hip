@@ -3,6 +3,7 @@
 // instance the registers of its index arithmetic, and the interpreter objects stay exactly what they were.
 #include "sc_internal.h"
 #include "sc_device.h"
+#include "sc_launch_axis.h"
 
 using namespace sc;
 
@@ -87,42 +88,13 @@ __global__ void __launch_bounds__(64, 2) k_prod_axis(const ReduceArgs a) {
 
 }  // namespace sc
 
-namespace {
-
-template <int G, int L>
-int launch_prod_axis_cfg(sc_ctx* ctx, const ReduceArgs& a) {
-  const int key = 10000 * G + 10 * L + 1000000 * 29 + 5;     // (occ_cache is shared with the interpreters: their keys end in 0 or 1)
-  auto it = ctx->occ_cache.find(key);
-  int occ;
-  if (it == ctx->occ_cache.end()) {
-    int nb = 0;
-    HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_prod_axis<G, L>, 64, 0));
-    occ = std::max(1, std::min(nb, 16));
-    ctx->occ_cache[key] = occ;
-  } else {
-    occ = it->second;
-  }
-  constexpr int NG = 64 / G;
-  const uint64_t need = (a.nchains + NG - 1) / NG, maxb = (uint64_t)ctx->num_cu * occ;
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min(need, maxb));
-  hipLaunchKernelGGL((k_prod_axis<G, L>), dim3(grid), dim3(64), 0, ctx->stream, a);
-  ctx->launch_counts[sc_host::reduce_launch_key(G, L)]++;
-  HIPCHK(ctx, hipGetLastError());
-  return SC_OK;
-}
-
-}  // namespace
-
-// every multi-lane configuration with 29-bit limbs a modulus can have as its own (kConfigs)
-#define SC_REDUCE_INSTANCES(X) X(2, 18) X(2, 27) X(4, 14) X(4, 18) X(4, 27) X(8, 14) X(8, 18) X(8, 27) X(16, 14) X(16, 18)
-
 int sc_host::launch_prod_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* fin, const uint32_t* src, uint32_t* dst,
                               uint64_t K, uint64_t inner, uint32_t chunk, uint64_t nch, uint64_t nchains, int nwords, bool in_words, bool final) {
   ReduceArgs a;
   a.modctx = modctx; a.fin = fin; a.src = src; a.dst = dst; a.K = K; a.inner = inner; a.nch = nch; a.nchains = nchains;
   a.n0inv = n0inv; a.chunk = chunk; a.nwords = (uint32_t)nwords; a.in_words = in_words ? 1u : 0u; a.final = final ? 1u : 0u;
-#define SC_REDUCE_CASE(GG, LL) if (W == 29 && G == GG && L == LL) return launch_prod_axis_cfg<GG, LL>(ctx, a);
-  SC_REDUCE_INSTANCES(SC_REDUCE_CASE)
+#define SC_REDUCE_CASE(GG, LL) if (W == 29 && G == GG && L == LL) return launch_axis<reduce_launch_key(GG, LL)>(ctx, k_prod_axis<GG, LL>, 64 / GG, nchains, a);
+  SC_AXIS_INSTANCES(SC_REDUCE_CASE)
 #undef SC_REDUCE_CASE
   return SC_ERR_UNSUPPORTED;
 }

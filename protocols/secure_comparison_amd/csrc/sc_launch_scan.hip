@@ -3,6 +3,7 @@
 // exactly what they were.
 #include "sc_internal.h"
 #include "sc_device.h"
+#include "sc_launch_axis.h"
 
 using namespace sc;
 
@@ -93,43 +94,14 @@ __global__ void __launch_bounds__(64, 2) k_scan_axis(const ScanArgs a) {
 
 }  // namespace sc
 
-namespace {
-
-template <int G, int L>
-int launch_scan_axis_cfg(sc_ctx* ctx, const ScanArgs& a) {
-  const int key = 10000 * G + 10 * L + 1000000 * 29 + 6;     // (occ_cache is shared: the interpreters' keys end in 0 or 1, k_prod_axis' in 5)
-  auto it = ctx->occ_cache.find(key);
-  int occ;
-  if (it == ctx->occ_cache.end()) {
-    int nb = 0;
-    HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_scan_axis<G, L>, 64, 0));
-    occ = std::max(1, std::min(nb, 16));
-    ctx->occ_cache[key] = occ;
-  } else {
-    occ = it->second;
-  }
-  constexpr int NG = 64 / G;
-  const uint64_t need = (a.nchains + NG - 1) / NG, maxb = (uint64_t)ctx->num_cu * occ;
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min(need, maxb));
-  hipLaunchKernelGGL((k_scan_axis<G, L>), dim3(grid), dim3(64), 0, ctx->stream, a);
-  ctx->launch_counts[sc_host::scan_launch_key(G, L)]++;
-  HIPCHK(ctx, hipGetLastError());
-  return SC_OK;
-}
-
-}  // namespace
-
-// the instances of k_prod_axis (SC_REDUCE_INSTANCES in sc_launch_reduce.hip): every multi-lane configuration with 29-bit limbs
-#define SC_SCAN_INSTANCES(X) X(2, 18) X(2, 27) X(4, 14) X(4, 18) X(4, 27) X(8, 14) X(8, 18) X(8, 27) X(16, 14) X(16, 18)
-
 int sc_host::launch_scan_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* lift, const uint32_t* src,
                               const uint32_t* seed, uint32_t* dst, uint64_t K, uint64_t inner, uint64_t chunk, uint64_t nch, uint64_t nchains, int nwords,
                               bool in_words) {
   ScanArgs a;
   a.modctx = modctx; a.lift = lift; a.src = src; a.seed = seed; a.dst = dst; a.K = K; a.inner = inner; a.nch = nch; a.nchains = nchains;
   a.n0inv = n0inv; a.chunk = chunk; a.nwords = (uint32_t)nwords; a.in_words = in_words ? 1u : 0u;
-#define SC_SCAN_CASE(GG, LL) if (W == 29 && G == GG && L == LL) return launch_scan_axis_cfg<GG, LL>(ctx, a);
-  SC_SCAN_INSTANCES(SC_SCAN_CASE)
+#define SC_SCAN_CASE(GG, LL) if (W == 29 && G == GG && L == LL) return launch_axis<scan_launch_key(GG, LL)>(ctx, k_scan_axis<GG, LL>, 64 / GG, nchains, a);
+  SC_AXIS_INSTANCES(SC_SCAN_CASE)
 #undef SC_SCAN_CASE
   return SC_ERR_UNSUPPORTED;
 }

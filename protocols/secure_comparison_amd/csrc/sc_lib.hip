@@ -2,6 +2,7 @@
 // Builds the micro-programs (sc_vm.h) for each batched operation and queues the launches; the kernels themselves are instantiated in
 // the sc_launch_*.hip translation units (sc_internal.h), so this file holds no device code.
 #include "sc_internal.h"
+#include "sc_axis_plan.h"
 
 #include <functional>
 #include <type_traits>
@@ -21,6 +22,7 @@ int fail(sc_ctx* ctx, int code, const char* fmt, ...) {
 namespace {
 
 void free_scheme_keys(void* p);   // sc_schemes.h
+Big big_powmod(const Big& base, const Big& e, const Big& m);
 
 // every allocation selects the context's device first: the caller may have switched the thread's current device
 int dev_alloc(sc_ctx* ctx, size_t bytes, void** out) {
@@ -1228,62 +1230,77 @@ int sc_modinv(sc_ctx* ctx, int mod, const uint32_t* x, uint32_t* out, uint64_t c
 }
 
 // ------------------------------------------------------------------------------------------------
-// product along an axis: a tree of k_prod_axis levels (sc_launch_reduce.hip)
+// product and running product along an axis: what sc_modprod_axis and sc_modscan_axis share (sc_axis_plan.h holds the plans)
 // ------------------------------------------------------------------------------------------------
-// One level: K members per output in chains of `chunk` (the last one of an output may be shorter), nch = ceil(K / chunk) partials.
-struct ReduceLevel { uint64_t K; uint32_t chunk; uint64_t nch; };
-// Chunk length as in modinv_rec: a chain is sequential, so a level's latency is its chunk length while the tree's work (one product
-// per member, plus one per partial) hardly depends on it.  The shortest chunks of at least 4 and at most 32 members that still fill
-// every resident group slot of the chip at this level; `forced` (sc_ctx_set_reduce_chunk) overrides that at every level.  A level
-// never cuts finer than its K.  protocols/secure_comparison_amd/aggregate.py::reduce_plan mirrors this for the tests.
-static std::vector<ReduceLevel> reduce_plan(uint64_t outer, uint64_t K, uint64_t inner, uint64_t resident_groups, int forced) {
-  std::vector<ReduceLevel> lv;
-  for (;;) {
-    const uint64_t total = outer * K * inner;
-    uint64_t c = forced ? (uint64_t)forced : std::min<uint64_t>(32, std::max<uint64_t>(4, (total + resident_groups - 1) / resident_groups));
-    c = std::min(c, K);
-    const uint64_t nch = (K + c - 1) / c;
-    lv.push_back(ReduceLevel{K, (uint32_t)c, nch});
-    if (nch == 1) return lv;
-    K = nch;
-  }
+// An entry point, its kernel and what an in-place call would be: the words in which the two entries' messages differ.
+struct AxisEntry { const char *name, *kernel, *in_place; };
+static const AxisEntry kProdAxis = {"sc_modprod_axis", "k_prod_axis", "reduction"}, kScanAxis = {"sc_modscan_axis", "k_scan_axis", "scan"};
+
+static int no_axis_instance(sc_ctx* ctx, const AxisEntry& e, const Mod& m) {
+  return fail(ctx, SC_ERR_ARG, "%s: no %s instance for configuration (G=%d, L=%d, W=%d%s)", e.name, e.kernel, m.G, m.L, m.W, m.small_c ? ", NEG1" : "");
 }
 
-// The closing factor of a reduction over K members: the limbs of R^K mod n, by square and multiply on the host, once per (modulus, K).
-// It reaches the device by a copy on the context's stream out of a pinned host buffer that lives as long as the entry, so the call
-// does not wait for the stream.  The context keeps at most REDUCE_CONSTS_MAX of them: a caller who sums over ever new K does not grow
-// device memory; only when the table is full does a call wait for the stream, to free it and start again.
+// Every refusal of the two entries, in one order and before anything is launched or allocated: context, modulus and pointers; then
+// axis_verdict's; then a configuration without an instance.  out_rows: the numbers `out` holds.  *run is false where SC_OK means
+// an empty array: nothing to do.
+static int axis_check(sc_ctx* ctx, const AxisEntry& e, int mod, const uint32_t* x, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out,
+                      uint64_t out_rows, bool* run) {
+  *run = false;
+  if (!valid_mod(ctx, mod) || !x || !out) return fail(ctx, SC_ERR_ARG, "%s: bad argument", e.name);
+  const Mod& m = ctx->mods[mod];
+  switch (axis_verdict((uint64_t)m.nwords, outer, K, inner, out_rows, (uintptr_t)x, (uintptr_t)out)) {
+    case AXIS_NO_MEMBER: return fail(ctx, SC_ERR_ARG, "%s: K must be at least 1", e.name);
+    case AXIS_TOO_LARGE: return fail(ctx, SC_ERR_ARG, "%s: outer * K * inner * nwords exceeds 2^40 words", e.name);
+    case AXIS_EMPTY: return SC_OK;
+    case AXIS_OVERLAP: return fail(ctx, SC_ERR_ARG, "%s: out overlaps x (in-place %s is not supported)", e.name, e.in_place);
+    case AXIS_RUN: break;
+  }
+  if (m.W != 29 || m.G < 2 || m.small_c != 0) return no_axis_instance(ctx, e, m);
+  *run = true;
+  return SC_OK;
+}
+
+// The group slots of the chip that axis_chunk fills: 8 resident waves per CU, 64 / G groups each.
+static uint64_t resident_groups(const sc_ctx* ctx, const Mod& m) { return (uint64_t)ctx->num_cu * 8 * (64 / m.G); }
+
+// The limbs of R^e mod n for every exponent of `exps`, on the device, into out_limbs[0 .. exps.size()): sc_modprod_axis' closing factor
+// R^K, sc_modscan_axis' level constants.  Each is built by square and multiply on the host, once per (modulus, e), and reaches the device by a copy on the context's
+// stream out of a pinned host buffer that lives as long as the entry, so the call does not wait for the stream.  The context keeps at
+// most REDUCE_CONSTS_MAX of them: a caller who sums over ever new K does not grow device memory.  Only when the table cannot take all
+// that a call is missing does the call wait for the stream, to empty the table once before it builds any of them: the pointers of one
+// call stay valid together.  A call asks for one exponent per level, and an array of at most 2^40 words has at most 41: a blocked level
+// has K > chunk >= 2 and leaves fewer than K / 2 members to the next one.  More than the table holds is refused.
 static const size_t REDUCE_CONSTS_MAX = 64;
 static void free_reduce_consts(sc_ctx* ctx) {
   for (auto& kv : ctx->reduce_consts) { (void)hipFree(kv.second.first); (void)hipHostFree(kv.second.second); }
   ctx->reduce_consts.clear();
 }
-static int reduce_closing_const(sc_ctx* ctx, int mod, uint64_t K, const uint32_t** out_limbs) {
-  auto it = ctx->reduce_consts.find({mod, K});
-  if (it == ctx->reduce_consts.end()) {
-    const Mod& m = ctx->mods[mod];
-    auto mulmod = [&](const Big& a, const Big& b) { Big q, r; big_divmod(big_mul(a, b), m.n, &q, &r); return r; };
-    Big one(m.nwords, 0); one[0] = 1;
-    Big base = big_shl_mod(one, m.n, m.W * m.S), v = one;
-    for (uint64_t e = K; e; e >>= 1) {
-      if (e & 1) v = mulmod(v, base);
-      if (e > 1) base = mulmod(base, base);
-    }
-    const std::vector<uint32_t> limbs = to_limbs(v, m.S, m.W);
-    const size_t bytes = limbs.size() * 4;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (ctx->reduce_consts.size() >= REDUCE_CONSTS_MAX) {
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      free_reduce_consts(ctx);
-    }
-    uint32_t *d = nullptr, *h = nullptr;
-    HIPCHK(ctx, hipMalloc((void**)&d, bytes));
-    if (hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipFree(d); return fail(ctx, SC_ERR_HIP, "sc_modprod_axis: hipHostMalloc failed"); }
-    memcpy(h, limbs.data(), bytes);
-    it = ctx->reduce_consts.emplace(std::make_pair(mod, K), std::make_pair(d, h)).first;
-    HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+static int mont_power_limbs(sc_ctx* ctx, int mod, const std::vector<uint64_t>& exps, const uint32_t** out_limbs) {
+  const Mod& m = ctx->mods[mod];
+  if (exps.size() > REDUCE_CONSTS_MAX) return fail(ctx, SC_ERR_HIP, "%zu constants R^e in one call (internal error)", exps.size());
+  size_t missing = 0;
+  for (uint64_t e : exps) missing += !ctx->reduce_consts.count({mod, e});     // (an exponent given twice counts twice: emptied early, no more)
+  if (missing) HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->reduce_consts.size() + missing > REDUCE_CONSTS_MAX) {
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    free_reduce_consts(ctx);
   }
-  *out_limbs = it->second.first;
+  for (uint64_t e0 : exps) {
+    auto it = ctx->reduce_consts.find({mod, e0});
+    if (it == ctx->reduce_consts.end()) {
+      Big one(m.nwords, 0); one[0] = 1;
+      const Big v = big_powmod(big_shl_mod(one, m.n, m.W * m.S), Big{(uint32_t)e0, (uint32_t)(e0 >> 32)}, m.n);
+      const std::vector<uint32_t> limbs = to_limbs(v, m.S, m.W);
+      const size_t bytes = limbs.size() * 4;
+      uint32_t *d = nullptr, *h = nullptr;
+      HIPCHK(ctx, hipMalloc((void**)&d, bytes));
+      if (hipHostMalloc((void**)&h, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipFree(d); return fail(ctx, SC_ERR_HIP, "sc_modprod_axis: hipHostMalloc failed"); }
+      memcpy(h, limbs.data(), bytes);
+      it = ctx->reduce_consts.emplace(std::make_pair(mod, e0), std::make_pair(d, h)).first;
+      HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *out_limbs++ = it->second.first;
+  }
   return SC_OK;
 }
 
@@ -1293,28 +1310,12 @@ int sc_ctx_set_reduce_chunk(sc_ctx* ctx, int c) {
   return SC_OK;
 }
 
+// product along an axis: a tree of k_prod_axis levels (sc_launch_reduce.hip)
 int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out) {
-  if (!valid_mod(ctx, mod) || !x || !out) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: bad argument");
-  if (K < 1) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: K must be at least 1");
+  bool run;
+  { int rc = axis_check(ctx, kProdAxis, mod, x, outer, K, inner, out, outer * inner, &run); if (rc || !run) return rc; }
   const Mod& m = ctx->mods[mod];
-  {
-    // outer * K * inner * nwords <= 2^40 words, checked factor by factor so that no product wraps
-    const uint64_t LIM = 1ull << 40;
-    uint64_t words = (uint64_t)m.nwords;
-    for (uint64_t f : {K, outer, inner}) {
-      if (f != 0 && words > LIM / f) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: outer * K * inner * nwords exceeds 2^40 words");
-      words *= f;
-    }
-  }
-  if (outer == 0 || inner == 0) return SC_OK;
-  {
-    const size_t xbytes = (size_t)outer * K * inner * m.nwords * 4, obytes = (size_t)outer * inner * m.nwords * 4;
-    const char *xb = (const char*)x, *ob = (const char*)out;
-    if (xb < ob + obytes && ob < xb + xbytes) return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: out overlaps x (in-place reduction is not supported)");
-  }
-  if (m.W != 29 || m.G < 2 || m.small_c != 0)
-    return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: no k_prod_axis instance for configuration (G=%d, L=%d, W=%d%s)", m.G, m.L, m.W, m.small_c ? ", NEG1" : "");
-  const std::vector<ReduceLevel> plan = reduce_plan(outer, K, inner, (uint64_t)ctx->num_cu * 8 * (64 / m.G), ctx->reduce_chunk);
+  const std::vector<ReduceLevel> plan = reduce_plan(outer, K, inner, resident_groups(ctx, m), ctx->reduce_chunk);
   // partials: level v writes outer * nch_v * inner numbers in limb form; levels alternate between the two halves of one temporary
   // (sizes shrink from level to level, so the first two decide)
   uint32_t* half[2] = {nullptr, nullptr};
@@ -1323,8 +1324,8 @@ int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
     int rc = tmp_buf(ctx, TMP_REDUCE, (n0 + n1) * m.S * 4, (void**)&half[0]); if (rc) return rc;
     half[1] = half[0] + n0 * m.S;
   }
-  const uint32_t* fin = nullptr;
-  { int rc = reduce_closing_const(ctx, mod, K, &fin); if (rc) return rc; }
+  const uint32_t* fin = nullptr;                     // the closing factor R^K
+  { int rc = mont_power_limbs(ctx, mod, {K}, &fin); if (rc) return rc; }
   const uint32_t* src = x;
   for (size_t v = 0; v < plan.size(); v++) {
     const ReduceLevel& lv = plan[v];
@@ -1332,8 +1333,7 @@ int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
     uint32_t* dst = final ? out : half[v & 1];
     int rc = launch_prod_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, fin, src, dst, lv.K, inner, lv.chunk, lv.nch, outer * lv.nch * inner, m.nwords,
                               v == 0, final);
-    if (rc == SC_ERR_UNSUPPORTED)
-      return fail(ctx, SC_ERR_ARG, "sc_modprod_axis: no k_prod_axis instance for configuration (G=%d, L=%d, W=%d)", m.G, m.L, m.W);
+    if (rc == SC_ERR_UNSUPPORTED) return no_axis_instance(ctx, kProdAxis, m);
     if (rc) return rc;
     // one product per member past the first of a chain; the last level's product with the closing factor
     ctx->mac_counter += (double)m.S * m.S * 2.0 * (double)outer * (double)inner * ((double)(lv.K - lv.nch) + (final ? 1.0 : 0.0));
@@ -1342,55 +1342,12 @@ int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
   return SC_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
 // running product along an axis: reduce-then-scan over k_prod_axis and k_scan_axis (sc_launch_scan.hip)
-// ------------------------------------------------------------------------------------------------
-// One level of the blocked scan: K members per scan in chunks of `chunk`, nch = ceil(K / chunk) of them; `members` original members
-// stand behind one member of this level (1 at the top), which therefore carries the drift R^-(members - 1).  A blocked level hands the
-// totals of its nch - 1 full chunks to the next level; the last level is direct: one chain per scan, no seed.
-struct ScanLevel { uint64_t K; uint64_t chunk; uint64_t nch; uint64_t members; bool blocked; };
-// Direct when the outer * inner scans fill every resident group slot by themselves, or K is no longer than one chunk; blocked
-// otherwise, with reduce_plan's chunk length.  A forced chunk length blocks every level longer than itself.
-// protocols/secure_comparison_amd/aggregate.py::scan_plan mirrors this for the tests.
-static std::vector<ScanLevel> scan_plan(uint64_t outer, uint64_t K, uint64_t inner, uint64_t resident_groups, int forced) {
-  std::vector<ScanLevel> lv;
-  uint64_t members = 1;
-  for (;;) {
-    const uint64_t total = outer * K * inner;
-    const uint64_t c = forced ? (uint64_t)forced : std::min<uint64_t>(32, std::max<uint64_t>(4, (total + resident_groups - 1) / resident_groups));
-    if ((!forced && outer * inner >= resident_groups) || K <= c) {
-      lv.push_back(ScanLevel{K, K, 1, members, false});
-      return lv;
-    }
-    const uint64_t nch = (K + c - 1) / c;
-    lv.push_back(ScanLevel{K, c, nch, members, true});
-    members *= c;
-    K = nch - 1;
-  }
-}
-
 int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out) {
-  if (!valid_mod(ctx, mod) || !x || !out) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: bad argument");
-  if (K < 1) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: K must be at least 1");
+  bool run;
+  { int rc = axis_check(ctx, kScanAxis, mod, x, outer, K, inner, out, outer * K * inner, &run); if (rc || !run) return rc; }
   const Mod& m = ctx->mods[mod];
-  {
-    // outer * K * inner * nwords <= 2^40 words, checked factor by factor so that no product wraps
-    const uint64_t LIM = 1ull << 40;
-    uint64_t words = (uint64_t)m.nwords;
-    for (uint64_t f : {K, outer, inner}) {
-      if (f != 0 && words > LIM / f) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: outer * K * inner * nwords exceeds 2^40 words");
-      words *= f;
-    }
-  }
-  if (outer == 0 || inner == 0) return SC_OK;
-  {
-    const size_t bytes = (size_t)outer * K * inner * m.nwords * 4;
-    const char *xb = (const char*)x, *ob = (const char*)out;
-    if (xb < ob + bytes && ob < xb + bytes) return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: out overlaps x (in-place scan is not supported)");
-  }
-  if (m.W != 29 || m.G < 2 || m.small_c != 0)
-    return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: no k_scan_axis instance for configuration (G=%d, L=%d, W=%d%s)", m.G, m.L, m.W, m.small_c ? ", NEG1" : "");
-  const std::vector<ScanLevel> plan = scan_plan(outer, K, inner, (uint64_t)ctx->num_cu * 8 * (64 / m.G), ctx->reduce_chunk);
+  const std::vector<ScanLevel> plan = scan_plan(outer, K, inner, resident_groups(ctx, m), ctx->reduce_chunk);
   const size_t D = plan.size() - 1;                  // blocked levels
   // level v < D keeps, in one temporary, the totals of its full chunks (limb form) and their prefixes (word form), outer * K_(v+1) * inner each
   std::vector<uint32_t*> totals(D, nullptr), prefix(D, nullptr);
@@ -1405,20 +1362,21 @@ int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
       prefix[v] = buf; buf += cnt * m.nwords;
     }
   }
-  // the level constants R^(members + 1).  A full table of constants is emptied while one is built, which would orphan those fetched
-  // before it in this call: a second pass, which finds the few of them in a table just emptied, takes the pointers.
+  // the level constants R^(members + 1), all from one fetch
+  std::vector<uint64_t> exps;
+  for (const ScanLevel& lv : plan) exps.push_back(lv.members + 1);
   std::vector<const uint32_t*> lift(plan.size(), nullptr);
-  for (int pass = 0; pass < 2; pass++)
-    for (size_t v = 0; v < plan.size(); v++) { int rc = reduce_closing_const(ctx, mod, plan[v].members + 1, &lift[v]); if (rc) return rc; }
-  const uint32_t* dummy_fin = lift[0];               // a level that is not final reads S limbs of it and uses none
-  auto unsupported = [&]() { return fail(ctx, SC_ERR_ARG, "sc_modscan_axis: no k_scan_axis instance for configuration (G=%d, L=%d, W=%d)", m.G, m.L, m.W); };
+  { int rc = mont_power_limbs(ctx, mod, exps, lift.data()); if (rc) return rc; }
+  // k_prod_axis stages S limbs of `fin` at every level and multiplies by them at a final one only: the totals' levels, none of them
+  // final, get S limbs that exist
+  const uint32_t* const unused_fin = lift[0];
   // down: the totals of every blocked level's full chunks, one product per member past the first of a chunk
   for (size_t v = 0; v < D; v++) {
     const ScanLevel& lv = plan[v];
     const uint32_t* src = v == 0 ? x : totals[v - 1];
-    int rc = launch_prod_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, dummy_fin, src, totals[v], lv.K, inner, (uint32_t)lv.chunk, lv.nch - 1, outer * (lv.nch - 1) * inner,
+    int rc = launch_prod_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, unused_fin, src, totals[v], lv.K, inner, (uint32_t)lv.chunk, lv.nch - 1, outer * (lv.nch - 1) * inner,
                               m.nwords, v == 0, false);
-    if (rc == SC_ERR_UNSUPPORTED) return unsupported();
+    if (rc == SC_ERR_UNSUPPORTED) return no_axis_instance(ctx, kScanAxis, m);
     if (rc) return rc;
     ctx->mac_counter += (double)m.S * m.S * 2.0 * (double)outer * (double)inner * (double)(lv.nch - 1) * (double)(lv.chunk - 1);
   }
@@ -1429,7 +1387,7 @@ int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
     uint32_t* dst = v == 0 ? out : prefix[v - 1];
     int rc = launch_scan_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, lift[v], src, lv.blocked ? prefix[v] : nullptr, dst, lv.K, inner, lv.chunk, lv.nch,
                               outer * lv.nch * inner, m.nwords, v == 0);
-    if (rc == SC_ERR_UNSUPPORTED) return unsupported();
+    if (rc == SC_ERR_UNSUPPORTED) return no_axis_instance(ctx, kScanAxis, m);
     if (rc) return rc;
     ctx->mac_counter += (double)m.S * m.S * 2.0 * 2.0 * (double)outer * (double)inner * (double)lv.K;
   }

@@ -517,49 +517,36 @@ class Engine:
         self._check(rc)
         return out
 
-    def _axis_args(self, x: torch.Tensor, outer: int, K: int, inner: int, nwords: int, out: torch.Tensor | None):
+    def _axis_call(self, entry, handle: int, nwords: int, x: torch.Tensor, outer: int, K: int, inner: int, scan: bool,
+                   out: torch.Tensor | None) -> torch.Tensor:
+        """One call of an axis entry point of the library (`handle`: its modulus or key) on x viewed as [outer][K][inner][nwords]: a
+        result per (outer, inner), or per member when `scan`."""
         outer, K, inner = int(outer), int(K), int(inner)
         if min(outer, K, inner) < 0:
             raise ValueError("outer, K, inner: expected non-negative sizes")
         self._arr(x, "x", outer * K * inner, nwords)
-        return outer, K, inner, self._out(out, outer * inner, nwords)
+        out = self._out(out, outer * (K if scan else 1) * inner, nwords)
+        self._sync_stream()
+        self._check(entry(self.ctx, handle, self._ptr(x), outer, K, inner, self._ptr(out)))
+        return out
 
     def modprod_axis(self, mod: Modulus, x: torch.Tensor, outer: int, K: int, inner: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The product along the middle axis of x viewed as [outer][K][inner][nwords]: [outer * inner][nwords] (sc_modprod_axis)."""
-        outer, K, inner, out = self._axis_args(x, outer, K, inner, mod.nwords, out)
-        self._sync_stream()
-        self._check(self.lib.sc_modprod_axis(self.ctx, mod.id, self._ptr(x), outer, K, inner, self._ptr(out)))
-        return out
+        return self._axis_call(self.lib.sc_modprod_axis, mod.id, mod.nwords, x, outer, K, inner, False, out)
 
     def paillier_sum_axis(self, key: PaillierKey, c: torch.Tensor, outer: int, K: int, inner: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The homomorphic sum along the middle axis of c viewed as [outer][K][inner][2nw]: [outer * inner][2nw] (sc_paillier_sum_axis)."""
-        outer, K, inner, out = self._axis_args(c, outer, K, inner, key.mod_n2.nwords, out)
-        self._sync_stream()
-        self._check(self.lib.sc_paillier_sum_axis(self.ctx, key.id, self._ptr(c), outer, K, inner, self._ptr(out)))
-        return out
-
-    def _scan_args(self, x: torch.Tensor, outer: int, K: int, inner: int, nwords: int, out: torch.Tensor | None):
-        outer, K, inner = int(outer), int(K), int(inner)
-        if min(outer, K, inner) < 0:
-            raise ValueError("outer, K, inner: expected non-negative sizes")
-        self._arr(x, "x", outer * K * inner, nwords)
-        return outer, K, inner, self._out(out, outer * K * inner, nwords)
+        return self._axis_call(self.lib.sc_paillier_sum_axis, key.id, key.mod_n2.nwords, c, outer, K, inner, False, out)
 
     def modscan_axis(self, mod: Modulus, x: torch.Tensor, outer: int, K: int, inner: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The inclusive running product along the middle axis of x viewed as [outer][K][inner][nwords]: [outer * K * inner][nwords]
         (sc_modscan_axis)."""
-        outer, K, inner, out = self._scan_args(x, outer, K, inner, mod.nwords, out)
-        self._sync_stream()
-        self._check(self.lib.sc_modscan_axis(self.ctx, mod.id, self._ptr(x), outer, K, inner, self._ptr(out)))
-        return out
+        return self._axis_call(self.lib.sc_modscan_axis, mod.id, mod.nwords, x, outer, K, inner, True, out)
 
     def paillier_cumsum_axis(self, key: PaillierKey, c: torch.Tensor, outer: int, K: int, inner: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """The inclusive running homomorphic sum along the middle axis of c viewed as [outer][K][inner][2nw]: [outer * K * inner][2nw]
         (sc_paillier_cumsum_axis)."""
-        outer, K, inner, out = self._scan_args(c, outer, K, inner, key.mod_n2.nwords, out)
-        self._sync_stream()
-        self._check(self.lib.sc_paillier_cumsum_axis(self.ctx, key.id, self._ptr(c), outer, K, inner, self._ptr(out)))
-        return out
+        return self._axis_call(self.lib.sc_paillier_cumsum_axis, key.id, key.mod_n2.nwords, c, outer, K, inner, True, out)
 
     def set_reduce_chunk(self, c: int) -> None:
         """Chunk length of the axis product's tree (sc_ctx_set_reduce_chunk): 0 automatic, 2 .. 32 that length at every level."""

@@ -1,24 +1,32 @@
 """Plain-Python reference of the product along an axis (sc_modprod_axis) and of its level plan, and the table of compiled k_prod_axis
-instances the GPU tier runs.  No torch at import."""
+and k_scan_axis instances the GPU tier runs.  No torch at import."""
 from __future__ import annotations
 
 import os
 import re
 
-# every k_prod_axis<G, L> csrc/sc_launch_reduce.hip compiles; tests/test_gpu_aggregate.py runs one parametrised case per row and
-# tests/test_aggregate_cpu.py compares this table with the source
+# every k_prod_axis<G, L> and k_scan_axis<G, L> that csrc/sc_launch_reduce.hip and csrc/sc_launch_scan.hip compile, from the one list in
+# csrc/sc_launch_axis.h; tests/test_gpu_aggregate.py and tests/test_gpu_scan.py run one parametrised case per row and
+# tests/test_aggregate_cpu.py and tests/test_scan_cpu.py compare this table with the source
 INSTANCES = [(2, 18), (2, 27), (4, 14), (4, 18), (4, 27), (8, 14), (8, 18), (8, 27), (16, 14), (16, 18)]
 
-SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "protocols", "secure_comparison_amd", "csrc",
-                      "sc_launch_reduce.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "protocols", "secure_comparison_amd", "csrc")
+SOURCE = os.path.join(CSRC, "sc_launch_axis.h")
+UNITS = [os.path.join(CSRC, "sc_launch_reduce.hip"), os.path.join(CSRC, "sc_launch_scan.hip")]
 
 
 def compiled_instances(text: str) -> list[tuple[int, int]]:
-    """The (G, L) pairs of the SC_REDUCE_INSTANCES list of the launcher source."""
-    m = re.search(r"#define\s+SC_REDUCE_INSTANCES\(X\)(.*)", text)
+    """The (G, L) pairs of the SC_AXIS_INSTANCES list of the launchers' shared header."""
+    m = re.search(r"#define\s+SC_AXIS_INSTANCES\(X\)(.*)", text)
     if not m:
-        raise ValueError("SC_REDUCE_INSTANCES not found")
+        raise ValueError("SC_AXIS_INSTANCES not found")
     return [(int(g), int(l)) for g, l in re.findall(r"X\(\s*(\d+)\s*,\s*(\d+)\s*\)", m.group(1))]
+
+
+def units_share_the_list() -> bool:
+    """Both launch units include the shared header and neither defines an instance list of its own."""
+    texts = [open(u).read() for u in UNITS]
+    return all('#include "sc_launch_axis.h"' in t and not re.search(r"#define\s+SC_\w*INSTANCES", t) for t in texts)
 
 
 def missing_rows(text: str, table=None) -> list[tuple[int, int]]:

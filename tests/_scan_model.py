@@ -1,30 +1,8 @@
 """Plain-Python reference of the running product along an axis (sc_modscan_axis), a launch-by-launch count of its plan that walks the
-members one by one, and the table of compiled k_scan_axis instances the GPU tier runs.  No torch at import."""
+members one by one; the table of compiled k_scan_axis instances is k_prod_axis' (tests/_reduce_model.py).  No torch at import."""
 from __future__ import annotations
 
-import os
-import re
-
-# every k_scan_axis<G, L> csrc/sc_launch_scan.hip compiles; tests/test_gpu_scan.py runs one parametrised case per row and
-# tests/test_scan_cpu.py compares this table with the source
-INSTANCES = [(2, 18), (2, 27), (4, 14), (4, 18), (4, 27), (8, 14), (8, 18), (8, 27), (16, 14), (16, 18)]
-
-SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "protocols", "secure_comparison_amd", "csrc",
-                      "sc_launch_scan.hip")
-
-
-def compiled_instances(text: str) -> list[tuple[int, int]]:
-    """The (G, L) pairs of the SC_SCAN_INSTANCES list of the launcher source."""
-    m = re.search(r"#define\s+SC_SCAN_INSTANCES\(X\)(.*)", text)
-    if not m:
-        raise ValueError("SC_SCAN_INSTANCES not found")
-    return [(int(g), int(l)) for g, l in re.findall(r"X\(\s*(\d+)\s*,\s*(\d+)\s*\)", m.group(1))]
-
-
-def missing_rows(text: str, table=None) -> list[tuple[int, int]]:
-    """Compiled instances without a row in `table` (default: INSTANCES)."""
-    table = INSTANCES if table is None else table
-    return [c for c in compiled_instances(text) if c not in table]
+from _reduce_model import INSTANCES, SOURCE, compiled_instances, missing_rows, units_share_the_list  # noqa: F401
 
 
 def scan_axis(n: int, x: list[int], outer: int, K: int, inner: int) -> list[int]:

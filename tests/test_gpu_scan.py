@@ -186,6 +186,38 @@ def test_argument_checks_launch_nothing(n2world):
     assert eng.download(buf) == [3] * 8 + [3, 3, 9, 9] * 2
 
 
+def test_constant_table_turns_over_inside_one_scan(keys):
+    """The context keeps 64 constants R^e.  On a fresh context, sums over K = 10 .. 71 leave 62 of them; a scan at a forced chunk of 2
+    over K = 28 then needs the four exponents 2, 3, 5, 9 in one call, which the table cannot take beside the 62: it is emptied during that
+    call's fetch.  Every result before, in and after that call is the model's, and the launches are the plan's (in _run)."""
+    from protocols.secure_comparison_amd.engine import Engine
+
+    sk = oracle_paillier(keys, 1024)
+    eng = Engine()
+    try:
+        mod, n, cfg = eng.modulus(sk.n2), sk.n2, M.first_fit(sk.n2.bit_length())
+        assert cfg == (4, 18)
+        rng = random.Random("scan-constants")
+        ops = [rng.randrange(1, n) for _ in range(71 * 2)]
+        rows = eng.upload(ops, mod.nwords)
+        sum_of = lambda K, forced=0: A._run(eng, mod, cfg, rows[:2 * K], 1, K, 2, f"sum/{K}", forced=forced)  # noqa: E731
+        for K in range(10, 72):                                   # 62 distinct exponents
+            A._assert_rows(f"sum/{K}", sum_of(K), R.prod_axis(n, ops[:2 * K], 1, K, 2))
+        K = 28
+        expect = S.scan_axis(n, ops[:2 * K], 1, K, 2)
+        try:
+            eng.set_reduce_chunk(2)
+            plan = _plan(eng, cfg[0], 1, K, 2, 2)
+            assert S.count(plan, "scan") == 4 and S.count(plan, "totals") == 3            # members 1, 2, 4, 8 behind a level's member
+            A._assert_rows("scan/turnover", _run(eng, mod, cfg, rows[:2 * K], 1, K, 2, "scan/turnover", forced=2), expect)
+            A._assert_rows("sum/10 again", sum_of(10, 2), R.prod_axis(n, ops[:20], 1, 10, 2))
+            A._assert_rows("scan/again", _run(eng, mod, cfg, rows[:2 * K], 1, K, 2, "scan/again", forced=2), expect)
+        finally:
+            eng.set_reduce_chunk(0)
+    finally:
+        eng.close()
+
+
 def test_mac_counter_counts_two_products_per_member(n2world):
     eng, sk, mod, cfg = n2world
     s2 = (cfg[0] * cfg[1]) ** 2 * 2.0

@@ -94,6 +94,8 @@ def test_every_compiled_instance_has_a_row():
     from protocols.secure_comparison_amd.build import UNITS
 
     assert ("sc_launch_scan", "sc_launch_scan.hip", []) in UNITS and len(UNITS) == 13
+    assert ("sc_launch_reduce", "sc_launch_reduce.hip", []) in UNITS
+    assert S.units_share_the_list()                                                         # one list, in the header both units include
 
 
 def test_symbols_are_exported_and_bound():
