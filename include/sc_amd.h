@@ -110,6 +110,12 @@ int sc_paillier_sum_axis(sc_ctx* ctx, int key, const uint32_t* c_dptr, uint64_t 
  * encryption of the sum of the first j + 1 plaintexts.  sc_modscan_axis (sc_amd_dev.h) in the key's N^2 context, with its argument
  * checks; deterministic like sc_paillier_sum_axis, so re-randomize what is handed on. */
 int sc_paillier_cumsum_axis(sc_ctx* ctx, int key, const uint32_t* c_dptr, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out_dptr);
+/* A public linear map over ciphertexts along one axis: w_host [J][K] unsigned 64-bit weights on the host (free to reuse on return),
+ * out[o][j][i] = prod_{k < K} c[o][k][i]^w[j][k] mod N^2, [outer][J][inner][2 nwords] -- an encryption of sum_k w[j][k] m[o][k][i]
+ * (mod N).  sc_modlin_axis (sc_amd_dev.h) in the key's N^2 context, with its argument checks (K, J <= 1024, no zero size); deterministic
+ * like sc_paillier_sum_axis, so re-randomize what is handed on.  Negative weights: negate the ciphertext (invert it modulo N^2). */
+int sc_paillier_linear_axis(sc_ctx* ctx, int key, const uint32_t* c_dptr, uint64_t outer, uint64_t K, uint64_t inner, const uint64_t* w_host,
+                            uint64_t J, uint32_t* out_dptr);
 /* DGK key (`DGK.from_security_parameter`, SC/keyholder.py:161-166): public (n, g, h, u, t) and optionally secret (p, q, v_p, v_q); randomizer_bits = width of the exponent r of h^r ([ext]
  * ~2.5 t), window = fixed-base window of the tables for h, 1 .. 24 (2^window rows of the modulus's limb size per window: 6 GB
  * at 20, 82 GB at 24 for a 2048-bit n and 400-bit r; the key holder's half-size tables stop at 20).  table_src_ctx / table_src_key (nullable /

@@ -62,6 +62,7 @@ int sc_ctx_stats(sc_ctx* ctx, uint64_t* out, int n);
  *   bits 0..7 L, bits 8..15 G, bits 16..23 W (limb bits), bit 24 NEG1, bit 25 STAMP, bit 26 DIG, bit 27 kind (0 k_vm, 1 k_pvm),
  *   bit 28 k_prod_axis (sc_modprod_axis, and the totals of sc_modscan_axis; bits 24..27 zero);
  *   bit 29 k_scan_axis (sc_modscan_axis; bits 24..28 zero);
+ *   bit 30 k_lin_axis (sc_modlin_axis; bits 24..29 zero), with bit 24 its lifting launch k_lin_lift (bits 25..29 zero);
  * STAMP and DIG are always 0 for k_vm.  For tests and tools: which instance a call landed on is host policy no result shows. */
 int sc_ctx_launch_counts(sc_ctx* ctx, uint32_t* keys_out, uint64_t* counts_out, int cap, int* n_out);
 /* The constants behind the automatic policies, measured once per device and process when the first secret key is created (about
@@ -189,6 +190,21 @@ int sc_modprod_axis(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint64_t outer
  * instance is SC_ERR_ARG.  Launches are counted in sc_ctx_launch_counts under  L | G << 8 | 29 << 16 | 1 << 29  (the totals' under
  * bit 28). */
 int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint64_t outer, uint64_t K, uint64_t inner, uint32_t* out_dptr);
+/* Linear maps with public weights along one axis: x viewed as [outer][K][inner][nwords] canonical residues, w_host [J][K] unsigned
+ * 64-bit weights on the host, out[o][j][i] = prod_{k < K} x[o][k][i]^w[j][k] mod n, [outer][J][inner][nwords] canonical.  Two launches
+ * on the context's stream: k_lin_lift takes every member once to Montgomery form (one product with R^2; limb form, in a grow-only
+ * temporary), then the dedicated kernel k_lin_axis runs one chain per output: the K bases of an output share one squaring chain (Straus),
+ * from the Montgomery one, for every bit of the row's widest weight from the top one squaring -- none while the accumulator is still R
+ * -- and one product per member whose weight has that bit, then one reduction pass and the canonical residue.  All groups of a wave
+ * work on the same row j, so the weight bits are wave-uniform.  An all-zero row gives the residue 1, a row with a single weight 1 the
+ * member itself.  The weights and the bit length of every row's widest one are copied to the device through a pinned buffer of the
+ * context: w_host is free to reuse on return, and the call does not wait for the stream (only for the previous call's copy, should
+ * it still be under way).  Operands must be canonical.  Checked before anything is launched or allocated (SC_ERR_ARG, the message names
+ * the quantity): null pointers; outer, K, inner, J >= 1; K, J <= 1024; outer * K * inner * nwords and outer * J * inner * nwords <=
+ * 2^40 words; `out` must not overlap `x`; a modulus without an instance (sc_modprod_axis' rule, the message names G=, L=, W=).
+ * Launches are counted in sc_ctx_launch_counts under  L | G << 8 | 29 << 16 | 1 << 30, the lifting launch's with bit 24 as well. */
+int sc_modlin_axis(sc_ctx* ctx, int mod, const uint32_t* x_dptr, uint64_t outer, uint64_t K, uint64_t inner, const uint64_t* w_host, uint64_t J,
+                   uint32_t* out_dptr);
 
 /* ---- Paillier pieces that are not plain residue products --------------------------------------- */
 /* out[i] = 1 + m[i] * N mod N^2 (g = N+1 encryption without randomness: unsafe_encrypt(..) of

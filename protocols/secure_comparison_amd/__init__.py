@@ -7,6 +7,7 @@ from .communicator import Communicator, InMemoryCommunicator, StreamCommunicator
 from .dotproduct import (DotDraws, DotLayout, draw_dot, secure_dot_batch, secure_squared_distance_batch, secure_sum_squares_batch)
 from .initiator import AlicePlain, Initiator
 from .keyholder import BobPlain, KeyHolder
+from .linear import linear_planes_batch, linear_rows_batch
 from .lookup import OnehotDraws, OnehotLayout, draw_onehot, secure_gather_batch, secure_lookup_batch, secure_onehot_batch
 from .multiplication import (MulDraws, MulLayout, draw_mul, secure_and_batch, secure_equal_batch, secure_in_range_batch, secure_multiply_batch,
                              secure_or_batch, secure_xor_batch)
@@ -15,7 +16,7 @@ from .selection import secure_argmax_batch, secure_argmin_batch, secure_maximum_
 from .sorting import secure_kth_batch, secure_median_batch, secure_sort_batch, secure_topk_batch
 from .utils import from_bits, to_bits
 
-__all__ = ["sum_planes_batch", "sum_rows_batch", "cumsum_planes_batch", "cumsum_rows_batch", "secure_cdf_batch", "secure_quantile_batch",
+__all__ = ["linear_planes_batch", "linear_rows_batch", "sum_planes_batch", "sum_rows_batch", "cumsum_planes_batch", "cumsum_rows_batch", "secure_cdf_batch", "secure_quantile_batch",
            "secure_histogram_median_batch", "secure_histogram_batch", "secure_majority_batch", "secure_groupby_count_batch",
            "secure_groupby_sum_batch", "Communicator", "InMemoryCommunicator", "StreamCommunicator", "Initiator", "KeyHolder", "from_bits", "to_bits", "Paillier", "PaillierCiphertext", "DGK",
            "DGKCiphertext", "AlicePlain", "BobPlain", "secure_minimum_batch", "secure_maximum_batch", "secure_argmin_batch", "secure_argmax_batch",

@@ -13,7 +13,7 @@ SYMBOLS = [
     "sc_malloc", "sc_free", "sc_memcpy_h2d", "sc_memcpy_d2h",
     "sc_mod_create", "sc_mod_words", "sc_exp_create", "sc_const_create", "sc_fbt_create", "sc_fbt_import", "sc_fbt_bytes",
     "sc_modmul", "sc_modmul_const", "sc_modmul_const_sel", "sc_modexp_shared", "sc_modexp_shared_sq", "sc_modexp_var_sq", "sc_mod_supports_sq", "sc_modexp_shared_isone", "sc_modexp_shared_isone_any", "sc_fixedbase_pow", "sc_modexp_var", "sc_modexp_var_scatter",
-    "sc_modinv", "sc_modprod_axis", "sc_modscan_axis", "sc_ctx_set_reduce_chunk", "sc_paillier_sum_axis", "sc_paillier_cumsum_axis", "sc_paillier_encrypt_raw", "sc_paillier_encrypt_raw_neg", "sc_paillier_l_mul", "sc_crt_combine", "sc_plain_alice", "sc_plain_bob", "sc_select_prep", "sc_select_split", "sc_select_finish_cx", "sc_mul_prep", "sc_mul_split", "sc_dot_prep", "sc_dot_split", "sc_dgk_step4",
+    "sc_modinv", "sc_modprod_axis", "sc_modscan_axis", "sc_modlin_axis", "sc_ctx_set_reduce_chunk", "sc_paillier_sum_axis", "sc_paillier_cumsum_axis", "sc_paillier_linear_axis", "sc_paillier_encrypt_raw", "sc_paillier_encrypt_raw_neg", "sc_paillier_l_mul", "sc_crt_combine", "sc_plain_alice", "sc_plain_bob", "sc_select_prep", "sc_select_split", "sc_select_finish_cx", "sc_mul_prep", "sc_mul_split", "sc_dot_prep", "sc_dot_split", "sc_dgk_step4",
     "sc_paillier_key_create", "sc_paillier_key_mods", "sc_paillier_encrypt", "sc_paillier_randomize", "sc_paillier_decrypt",
     "sc_dgk_key_create", "sc_dgk_key_info", "sc_dgk_randomize", "sc_dgk_encrypt_bits_randomized", "sc_dgk_is_zero", "sc_dgk_any_zero",
     "sc_initiator_step1", "sc_keyholder_step2_4b", "sc_initiator_step4", "sc_initiator_step4i", "sc_keyholder_step4j_5", "sc_initiator_step67",
@@ -87,6 +87,8 @@ def load() -> C.CDLL:
         "sc_paillier_sum_axis": (i32, [vp, i32, vp, u64, u64, u64, vp]),
         "sc_modscan_axis": (i32, [vp, i32, vp, u64, u64, u64, vp]),
         "sc_paillier_cumsum_axis": (i32, [vp, i32, vp, u64, u64, u64, vp]),
+        "sc_modlin_axis": (i32, [vp, i32, vp, u64, u64, u64, vp, u64, vp]),
+        "sc_paillier_linear_axis": (i32, [vp, i32, vp, u64, u64, u64, vp, u64, vp]),
         "sc_paillier_encrypt_raw": (i32, [vp, i32, i32, vp, i32, vp, u64]),
         "sc_paillier_encrypt_raw_neg": (i32, [vp, i32, i32, vp, i32, vp, u64]),
         "sc_paillier_l_mul": (i32, [vp, i32, i32, vp, i32, vp, u64]),

@@ -1,8 +1,8 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
 // (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
-// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip and sc_launch_scan.hip (the
-// last two share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
+// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip, sc_launch_scan.hip and
+// sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
 // the HIP-free plans and checks of the two axis entries) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -238,6 +238,10 @@ struct sc_ctx {
   int reduce_chunk = 0;                                     // sc_ctx_set_reduce_chunk: 0 automatic, 2 .. 32 the chunk length of every level
   // (mod, e) -> limbs of R^e mod n (mont_power_limbs): the device copy and the pinned host buffer it is filled from (bounded)
   std::map<std::pair<int, uint64_t>, std::pair<uint32_t*, uint32_t*>> reduce_consts;
+  // sc_modlin_axis: the pinned host buffer its weights are copied to the device from (grow-only), and the event of the last such copy
+  void* lin_host = nullptr;
+  size_t lin_host_bytes = 0;
+  hipEvent_t lin_copied = nullptr;
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return sc_host::fail(ctx, SC_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
@@ -256,6 +260,8 @@ constexpr uint32_t launch_key(bool pvm, int G, int L, int W, bool neg1, bool sta
 constexpr uint32_t reduce_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 28); }
 // ... and of a k_scan_axis instance: bit 29 set
 constexpr uint32_t scan_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 29); }
+// ... and of a k_lin_axis instance: bit 30 set; with bit 24 its lifting launch k_lin_lift
+constexpr uint32_t lin_launch_key(int G, int L, bool lift) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 30) | (lift ? 1u << 24 : 0u); }
 // sc_launch_vm.hip / sc_launch_pvm.hip, parts 0 .. 2: launch the instance (G, L, W, NEG1[, STAMP]) of the interpreter on the context's
 // stream (grid, scratch arena and occupancy handled there); SC_ERR_UNSUPPORTED when the instance lives in another part
 int launch_vm_part0(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);
@@ -301,6 +307,11 @@ int launch_prod_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, u
 // SC_ERR_UNSUPPORTED when (G, L, W) has no instance
 int launch_scan_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* lift, const uint32_t* src, const uint32_t* seed,
                      uint32_t* dst, uint64_t K, uint64_t inner, uint64_t chunk, uint64_t nch, uint64_t nchains, int nwords, bool in_words);
+// sc_launch_lin.hip: the lifting launch (k_lin_lift: `count` members, words -> limbs of x R) and the linear map itself (k_lin_axis: w
+// and rowbits on the device) on the context's stream; SC_ERR_UNSUPPORTED when (G, L, W) has no instance
+int launch_lin_lift(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* src, uint32_t* dst, uint64_t count, int nwords);
+int launch_lin_axis(sc_ctx* ctx, int G, int L, int W, const uint32_t* modctx, uint32_t n0inv, const uint32_t* lifted, const uint64_t* w, const uint32_t* rowbits,
+                    uint32_t* dst, uint64_t outer, uint64_t K, uint64_t inner, uint64_t J, int nwords);
 // sc_launch_misc.hip again
 int launch_rng_bits(hipStream_t stream, const sc::RngKey& key, uint64_t call, int bits, int nw, uint32_t* out, uint64_t count);
 int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, const uint32_t* d_n, int nbits, int nw, int nonzero, uint32_t* out, uint64_t count);

@@ -169,7 +169,7 @@ inline bool small_enough_to_fork(const sc_ctx* ctx, const Mod& m, uint64_t count
   return (count + per_wave - 1) / per_wave <= (uint64_t)ctx->num_cu * 4 / (uint64_t)ctx->chip_share;
 }
 
-enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_REDUCE = 6, TMP_SCAN = 7, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
+enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_REDUCE = 6, TMP_SCAN = 7, TMP_LIN = 8, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
 
 // A u64 accumulator array of the context that is ZERO whenever no step is using it: cleared when it is (re)allocated, reset by its
 // reader afterwards (OP_TAKEFLAG).  The zero tests of step 4j OR their verdicts into it; no clearing launch inside a step.
@@ -607,6 +607,8 @@ void sc_ctx_destroy(sc_ctx* ctx) {
   for (auto& kv : ctx->tmp) if (kv.second.first) (void)hipFree(kv.second.first);
   for (auto& kv : ctx->reduce_consts) { (void)hipFree(kv.second.first); (void)hipHostFree(kv.second.second); }
   for (int* h : ctx->status_host) if (h) (void)hipHostFree(h);
+  if (ctx->lin_host) (void)hipHostFree(ctx->lin_host);
+  if (ctx->lin_copied) (void)hipEventDestroy(ctx->lin_copied);
   if (ctx->switch_event) (void)hipEventDestroy(ctx->switch_event);
   if (ctx->comm) (void)sc_comm_destroy(ctx);
   if (ctx->scheme_keys) free_scheme_keys(ctx->scheme_keys);
@@ -1391,6 +1393,70 @@ int sc_modscan_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uin
     if (rc) return rc;
     ctx->mac_counter += (double)m.S * m.S * 2.0 * 2.0 * (double)outer * (double)inner * (double)lv.K;
   }
+  return SC_OK;
+}
+
+// linear maps with public weights along an axis: one k_lin_lift and one k_lin_axis launch (sc_launch_lin.hip)
+static const AxisEntry kLinAxis = {"sc_modlin_axis", "k_lin_axis", "linear map"};
+static const uint64_t LIN_MAX = 1024;     // K and J of one call
+
+int sc_modlin_axis(sc_ctx* ctx, int mod, const uint32_t* x, uint64_t outer, uint64_t K, uint64_t inner, const uint64_t* w_host, uint64_t J, uint32_t* out) {
+  if (!valid_mod(ctx, mod) || !x || !out || !w_host) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: bad argument");
+  if (outer == 0) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: outer must be at least 1");
+  if (inner == 0) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: inner must be at least 1");
+  if (J == 0) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: J must be at least 1");
+  if (K > LIN_MAX) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: K = %llu exceeds %llu", (unsigned long long)K, (unsigned long long)LIN_MAX);
+  if (J > LIN_MAX) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: J = %llu exceeds %llu", (unsigned long long)J, (unsigned long long)LIN_MAX);
+  {                                          // the output's size: outer * J * inner * nwords <= 2^40 words, factor by factor (the input's: axis_check)
+    uint64_t words = (uint64_t)ctx->mods[mod].nwords * J;
+    for (uint64_t f : {outer, inner}) {
+      if (words > (1ull << 40) / f) return fail(ctx, SC_ERR_ARG, "sc_modlin_axis: outer * J * inner * nwords exceeds 2^40 words");
+      words *= f;
+    }
+  }
+  bool run;
+  { int rc = axis_check(ctx, kLinAxis, mod, x, outer, K, inner, out, outer * J * inner, &run); if (rc || !run) return rc; }
+  const Mod& m = ctx->mods[mod];
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // one grow-only temporary: the lifted members [outer][K][inner][S], the weights [J][K] (64 bits each, 8-byte aligned), rowbits [J]
+  const size_t members = (size_t)outer * K * inner, lift_words = (members * m.S + 1) & ~(size_t)1, w_bytes = (size_t)J * K * 8, rb_bytes = (size_t)J * 4;
+  uint32_t* buf = nullptr;
+  { int rc = tmp_buf(ctx, TMP_LIN, lift_words * 4 + w_bytes + rb_bytes, (void**)&buf); if (rc) return rc; }
+  uint32_t* const d_lift = buf;
+  uint64_t* const d_w = (uint64_t*)(buf + lift_words);
+  uint32_t* const d_rb = (uint32_t*)(d_w + J * K);
+  // The weights leave through a pinned buffer of the context, so that the copy is queued on the stream and the caller's array is free on
+  // return; the buffer is written again only after the previous call's copy has left it.
+  if (ctx->lin_copied) HIPCHK(ctx, hipEventSynchronize(ctx->lin_copied));
+  else HIPCHK(ctx, hipEventCreateWithFlags(&ctx->lin_copied, hipEventDisableTiming));
+  if (ctx->lin_host_bytes < w_bytes + rb_bytes) {
+    if (ctx->lin_host) { HIPCHK(ctx, hipHostFree(ctx->lin_host)); ctx->lin_host = nullptr; ctx->lin_host_bytes = 0; }
+    const size_t want = w_bytes + rb_bytes + (w_bytes + rb_bytes) / 8 + 256;
+    HIPCHK(ctx, hipHostMalloc(&ctx->lin_host, want, hipHostMallocDefault));
+    ctx->lin_host_bytes = want;
+  }
+  uint64_t* const h_w = (uint64_t*)ctx->lin_host;
+  uint32_t* const h_rb = (uint32_t*)(h_w + J * K);
+  memcpy(h_w, w_host, w_bytes);
+  double sqrs = 0, muls = 0;                 // per (o, i): what the chains of the J rows cost
+  for (uint64_t j = 0; j < J; j++) {
+    uint64_t top = 0;
+    for (uint64_t k = 0; k < K; k++) { top |= w_host[j * K + k]; muls += __builtin_popcountll(w_host[j * K + k]); }
+    h_rb[j] = top ? 64u - (uint32_t)__builtin_clzll(top) : 0u;
+    sqrs += h_rb[j] ? h_rb[j] - 1 : 0;
+  }
+  HIPCHK(ctx, hipMemcpyAsync(d_w, h_w, w_bytes + rb_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipEventRecord(ctx->lin_copied, ctx->stream));
+  int rc = launch_lin_lift(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, x, d_lift, members, m.nwords);
+  if (rc == SC_ERR_UNSUPPORTED) return no_axis_instance(ctx, kLinAxis, m);
+  if (rc) return rc;
+  rc = launch_lin_axis(ctx, m.G, m.L, m.W, m.d_ctx, m.n0inv, d_lift, d_w, d_rb, out, outer, K, inner, J, m.nwords);
+  if (rc == SC_ERR_UNSUPPORTED) return no_axis_instance(ctx, kLinAxis, m);
+  if (rc) return rc;
+  // one product per member (the lift); per output its squarings (half the multiply-adds of a product's a * b part), its products and the
+  // closing reduction pass
+  const double S2 = (double)m.S * m.S, pairs = (double)outer * (double)inner;
+  ctx->mac_counter += S2 * 2.0 * (double)members + pairs * S2 * (1.5 * sqrs + 2.0 * muls + 1.0 * (double)J);
   return SC_OK;
 }
 

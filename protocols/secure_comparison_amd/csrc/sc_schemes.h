@@ -269,6 +269,13 @@ int sc_paillier_cumsum_axis(sc_ctx* ctx, int key, const uint32_t* c, uint64_t ou
   return sc_modscan_axis(ctx, k->mod_n2, c, outer, K, inner, out);
 }
 
+int sc_paillier_linear_axis(sc_ctx* ctx, int key, const uint32_t* c, uint64_t outer, uint64_t K, uint64_t inner, const uint64_t* w_host, uint64_t J,
+                            uint32_t* out) {
+  const PaillierKey* k = paillier_key(ctx, key);
+  if (!k) return fail(ctx, SC_ERR_ARG, "sc_paillier_linear_axis: bad key");
+  return sc_modlin_axis(ctx, k->mod_n2, c, outer, K, inner, w_host, J, out);
+}
+
 int sc_paillier_decrypt(sc_ctx* ctx, int key, const uint32_t* c, uint32_t* out, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   const PaillierKey* kp = paillier_key(ctx, key);

@@ -548,6 +548,35 @@ class Engine:
         (sc_paillier_cumsum_axis)."""
         return self._axis_call(self.lib.sc_paillier_cumsum_axis, key.id, key.mod_n2.nwords, c, outer, K, inner, True, out)
 
+    def _lin_call(self, entry, handle: int, nwords: int, x: torch.Tensor, outer: int, K: int, inner: int, weights, out: torch.Tensor | None) -> torch.Tensor:
+        """One call of a linear-map entry point of the library on x viewed as [outer][K][inner][nwords] with the public weights
+        [J][K] (rows of Python ints, 0 <= w < 2^64): [outer * J * inner][nwords]."""
+        outer, K, inner = int(outer), int(K), int(inner)
+        if min(outer, K, inner) < 0:
+            raise ValueError("outer, K, inner: expected non-negative sizes")
+        rows = [[int(v) for v in row] for row in weights]
+        J = len(rows)
+        if any(len(row) != K for row in rows):
+            raise ValueError(f"weights: expected rows of {K} weights")
+        if any(not 0 <= v < 1 << 64 for row in rows for v in row):
+            raise ValueError("weights: expected 0 <= w < 2^64")
+        self._arr(x, "x", outer * K * inner, nwords)
+        out = self._out(out, outer * J * inner, nwords)
+        w = (C.c_uint64 * max(1, J * K))(*[v for row in rows for v in row])
+        self._sync_stream()
+        self._check(entry(self.ctx, handle, self._ptr(x), outer, K, inner, w, J, self._ptr(out)))
+        return out
+
+    def modlin_axis(self, mod: Modulus, x: torch.Tensor, outer: int, K: int, inner: int, weights, out: torch.Tensor | None = None) -> torch.Tensor:
+        """out[o][j][i] = prod_k x[o][k][i]^weights[j][k] mod n for x viewed as [outer][K][inner][nwords]: [outer * J * inner][nwords]
+        (sc_modlin_axis)."""
+        return self._lin_call(self.lib.sc_modlin_axis, mod.id, mod.nwords, x, outer, K, inner, weights, out)
+
+    def paillier_linear_axis(self, key: PaillierKey, c: torch.Tensor, outer: int, K: int, inner: int, weights,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+        """[[sum_k weights[j][k] m[o][k][i]]] for c viewed as [outer][K][inner][2nw]: [outer * J * inner][2nw] (sc_paillier_linear_axis)."""
+        return self._lin_call(self.lib.sc_paillier_linear_axis, key.id, key.mod_n2.nwords, c, outer, K, inner, weights, out)
+
     def set_reduce_chunk(self, c: int) -> None:
         """Chunk length of the axis product's tree (sc_ctx_set_reduce_chunk): 0 automatic, 2 .. 32 that length at every level."""
         self._check(self.lib.sc_ctx_set_reduce_chunk(self.ctx, int(c)))
@@ -1345,7 +1374,8 @@ class Engine:
 
     def launch_counts(self) -> dict:
         """{(kind, G, L, W, neg1, stamp, dig): launches} per compiled interpreter instance since the context was created
-        (sc_ctx_launch_counts); kind is "vm", "pvm", "reduce" (k_prod_axis) or "scan" (k_scan_axis)."""
+        (sc_ctx_launch_counts); kind is "vm", "pvm", "reduce" (k_prod_axis), "scan" (k_scan_axis), "lin" (k_lin_axis) or "lift"
+        (k_lin_lift; its bit 24 is part of the kind, not a neg1 flag)."""
         n = C.c_int()
         self._check(self.lib.sc_ctx_launch_counts(self.ctx, None, None, 0, C.byref(n)))
         cap = max(1, n.value)
@@ -1353,6 +1383,9 @@ class Engine:
         self._check(self.lib.sc_ctx_launch_counts(self.ctx, keys, counts, cap, C.byref(n)))
         out = {}
         for k, v in zip(keys[:n.value], counts[:n.value]):
+            if k >> 30 & 1:
+                out[("lift" if k >> 24 & 1 else "lin", k >> 8 & 0xff, k & 0xff, k >> 16 & 0xff, False, False, False)] = int(v)
+                continue
             out[("scan" if k >> 29 & 1 else "reduce" if k >> 28 & 1 else "pvm" if k >> 27 & 1 else "vm", k >> 8 & 0xff, k & 0xff, k >> 16 & 0xff, bool(k >> 24 & 1), bool(k >> 25 & 1), bool(k >> 26 & 1))] = int(v)
         return out
 
