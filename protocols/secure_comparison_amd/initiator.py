@@ -426,8 +426,8 @@ class Initiator:
                                         descending: bool = False, return_indices: bool = False, kappa: int = 40, source: str = "device",
                                         engine=None, generator=None, chunks: int = 1, max_rows: int = 65536):
         """(sorted [B][k][2nw], payload [np][B][k][2nw] or None, indices [B][k][2nw] or None), as sorting.secure_sort_batch: the header
-        `sort_0_session_{sid}`, then per sub-batch of the network one comparison session and one selection exchange (message ids
-        `.._session_{sid}_sort_{i}`)."""
+        `sort_0_session_{sid}`, then per sub-batch of sorting.topk_network(k, k) -- the sort is top-m with m = k -- one comparison
+        session and one selection exchange (message ids `.._session_{sid}_sort_{i}`)."""
         from .sorting import alice_sort
 
         return await alice_sort(self, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks,

@@ -305,7 +305,7 @@ class KeyHolder:
     async def perform_secure_sort_batch(self, k: int, payload_bits=(), return_indices: bool = False, kappa: int = 40, source: str = "device",
                                         generator=None, max_rows: int = 65536) -> None:
         """Bob's side of Initiator.perform_secure_sort_batch over k values per row: the initiator's header must announce this k,
-        max_rows, kappa and these column widths; the schedule follows from it (sorting.sort_schedule)."""
+        max_rows, kappa and these column widths; the schedule follows from it (sorting.schedule_counts: top-m's with m = k)."""
         from .sorting import bob_sort
 
         await bob_sort(self, k, payload_bits, return_indices, kappa, source, generator, max_rows)
@@ -314,7 +314,7 @@ class KeyHolder:
                                         only_last: bool = False, source: str = "device", generator=None, max_rows: int = 65536) -> None:
         """Bob's side of Initiator.perform_secure_topk_batch for the m smallest (or largest) of k values per row: the initiator's
         header must announce this k, m, only_last, max_rows, kappa and these column widths; the schedule follows from it
-        (sorting.topk_schedule), and a sub-batch of another size is refused."""
+        (sorting.topk_counts), and a sub-batch of another size is refused."""
         from .sorting import bob_topk
 
         await bob_topk(self, k, m, payload_bits, return_indices, kappa, only_last, source, generator, max_rows)

@@ -13,7 +13,8 @@ lo = F and hi = G: a comparator never exchanges equal keys, in either direction.
 
 The m smallest (or largest) of k, one order statistic and the median run the same compare-exchange over a truncated network,
 topk_network(k, m, only_last): the comparators the wanted outputs depend on, with a flag per output that says whether anything
-reads it again; a dead output is handed the row past the buffer's end and is not written.
+reads it again; a dead output is handed the row past the buffer's end and is not written.  The sort is that path
+with m = k, where topk_network returns batcher_network(k) with every flag true: schedule, steps, runner and player halves are one.
 """
 from __future__ import annotations
 
@@ -51,41 +52,6 @@ def batcher_network(k: int) -> list[list[tuple[int, int]]]:
             q //= 2
         p *= 2
     return layers
-
-
-def sort_schedule(k: int, B: int, max_rows: int) -> list[tuple[list[tuple[int, int]], list[tuple[int, int]]]]:
-    """The schedule both players follow: per layer, (its comparators, its sub-batches).  A layer's B * len(layer) comparisons are
-    numbered t = c * B + b (comparator c, row b) and cut into [start, stop) ranges of at most max_rows; each range is one comparison
-    and one compare-exchange selection."""
-    if int(max_rows) < 1:
-        raise ValueError(f"max_rows = {max_rows}: expected >= 1")
-    out = []
-    for layer in batcher_network(k):
-        total = B * len(layer)
-        out.append((layer, [(a, min(a + max_rows, total)) for a in range(0, total, max_rows)]))
-    return out
-
-
-def schedule_counts(k: int, B: int, max_rows: int) -> list[int]:
-    """The comparisons of every sub-batch, in order (what the key holder needs of the schedule)."""
-    return [b - a for _, cuts in sort_schedule(k, B, max_rows) for a, b in cuts]
-
-
-def _sort_steps(buf: torch.Tensor, B: int, k: int, max_rows: int, descending: bool):
-    """Yields (F [nf][count][2nw], G, lo rows, hi rows) per sub-batch of the schedule; the rows are int64 [nf][count] flat rows of
-    buf [nf][B k][2nw] seen as [nf B k][2nw].  F and G are gathered copies and a layer's comparators are disjoint, so the outputs of
-    one sub-batch go straight into buf: no later sub-batch of the layer reads a row it writes."""
-    nf, rows, _ = buf.shape
-    dev = buf.device
-    col = (torch.arange(nf, dtype=torch.int64, device=dev) * rows).unsqueeze(1)
-    base = torch.arange(B, dtype=torch.int64, device=dev) * k
-    for layer, cuts in sort_schedule(k, B, max_rows):
-        ij = torch.tensor(layer, dtype=torch.int64, device=dev)
-        ri, rj = (ij[:, 0:1] + base).reshape(-1), (ij[:, 1:2] + base).reshape(-1)
-        fr, gr = (rj, ri) if descending else (ri, rj)
-        for a, b in cuts:
-            f_rows, g_rows = fr[a:b], gr[a:b]
-            yield (buf.index_select(1, f_rows), buf.index_select(1, g_rows), (col + f_rows).contiguous(), (col + g_rows).contiguous())
 
 
 # ---- the truncated network: the m smallest of k, or the m-th smallest alone (DESIGN.md §8d) ----------------------------------------
@@ -165,27 +131,48 @@ def topk_network(k: int, m: int, only_last: bool = False) -> list[list[tuple[int
     return _relayer(best, k)
 
 
-def topk_schedule(k: int, m: int, only_last: bool, B: int, max_rows: int):
-    """sort_schedule for topk_network(k, m, only_last): per layer, (its comparators (i, j, keep_i, keep_j), its sub-batches [start,
-    stop) of at most max_rows of the layer's B * len(layer) comparisons t = c * B + b).  Live and dead outputs share a sub-batch."""
+# ---- the schedule (pure Python: both players derive the same one) -------------------------------------------------------------------
+def _cut(layers: list, B: int, max_rows: int) -> list:
+    """The schedule both players follow: per layer, (the layer, its sub-batches).  A layer's B * len(layer) comparisons are numbered
+    t = c * B + b (comparator c, row b) and cut into [start, stop) ranges of at most max_rows; each range is one comparison and one
+    compare-exchange selection, and live and dead outputs share it.  The one place that checks max_rows >= 1."""
     if int(max_rows) < 1:
         raise ValueError(f"max_rows = {max_rows}: expected >= 1")
-    out = []
-    for layer in topk_network(k, m, only_last):
-        total = B * len(layer)
-        out.append((layer, [(a, min(a + max_rows, total)) for a in range(0, total, max_rows)]))
-    return out
+    return [(layer, [(a, min(a + max_rows, B * len(layer))) for a in range(0, B * len(layer), max_rows)]) for layer in layers]
+
+
+def _counts(layers: list, B: int, max_rows: int) -> list[int]:
+    """The comparisons of every sub-batch, in order (what the key holder needs of the schedule)."""
+    return [b - a for _, cuts in _cut(layers, B, max_rows) for a, b in cuts]
+
+
+def sort_schedule(k: int, B: int, max_rows: int) -> list[tuple[list[tuple[int, int]], list[tuple[int, int]]]]:
+    """The schedule of the sort: per layer of batcher_network(k), (its comparators (i, j), its sub-batches)."""
+    return _cut(batcher_network(k), B, max_rows)
+
+
+def schedule_counts(k: int, B: int, max_rows: int) -> list[int]:
+    """topk_counts of the sort, m = k."""
+    return topk_counts(k, k, False, B, max_rows)
+
+
+def topk_schedule(k: int, m: int, only_last: bool, B: int, max_rows: int):
+    """The schedule of topk_network(k, m, only_last): per layer, (its comparators (i, j, keep_i, keep_j), its sub-batches)."""
+    return _cut(topk_network(k, m, only_last), B, max_rows)
 
 
 def topk_counts(k: int, m: int, only_last: bool, B: int, max_rows: int) -> list[int]:
-    """The comparisons of every sub-batch of topk_schedule, in order (what the key holder needs of it)."""
-    return [b - a for _, cuts in topk_schedule(k, m, only_last, B, max_rows) for a, b in cuts]
+    """The comparisons of every sub-batch of topk_schedule, in order."""
+    return _counts(topk_network(k, m, only_last), B, max_rows)
 
 
 def _topk_steps(buf: torch.Tensor, B: int, k: int, m: int, only_last: bool, max_rows: int, largest: bool):
-    """_sort_steps over topk_schedule: (F, G, lo rows, hi rows) per sub-batch, where a dead output's row is nf * B * k, the number of
-    rows of buf: sc_select_finish_cx writes no row at or past out_rows, so the dead position keeps a ciphertext nothing reads again.
-    largest: F is the value at j and G the one at i, so the larger value goes to i and keep_i belongs to hi."""
+    """Yields (F [nf][count][2nw], G, lo rows, hi rows) per sub-batch of topk_schedule(k, m, only_last, B, max_rows); a sort passes
+    m = k.  The rows are int64 [nf][count] flat rows of buf [nf][B k][2nw] seen as [nf B k][2nw].  F and G are gathered copies and
+    a layer's comparators are disjoint, so the outputs of one sub-batch go straight into buf: no later sub-batch of the layer reads
+    a row it writes.  A dead output's row is nf * B * k, the number of rows of buf: sc_select_finish_cx writes no row at or past
+    out_rows, so the dead position keeps a ciphertext nothing reads again.  largest (the sort: descending): F is the value at j and
+    G the one at i, so the larger value goes to i and keep_i belongs to hi."""
     nf, rows, _ = buf.shape
     dev = buf.device
     dead = nf * rows
@@ -244,7 +231,7 @@ def secure_compare_exchange_batch(x_enc: torch.Tensor, y_enc: torch.Tensor, l: i
     return out[0, 0], out[1, 0]
 
 
-# ---- the sort in one process -------------------------------------------------------------------------------------------------------
+# ---- the sort, top-m and the k-th order statistic in one process: one path, the sort is m = k ---------------------------------------
 def _sort_layout(l, k, payload_bits, return_indices, kappa, paillier) -> SelectLayout:
     """The layout of the key column, the payload columns and -- return_indices -- the index column of k values per row."""
     widths = tuple(int(b) for b in payload_bits) + ((index_bits(k),) if return_indices else ())
@@ -253,11 +240,10 @@ def _sort_layout(l, k, payload_bits, return_indices, kappa, paillier) -> SelectL
     return SelectLayout(l, kappa, widths, paillier.public_key.n.bit_length())
 
 
-def _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_rows):
-    """Every check that comes before an upload or a launch; returns (layout, B, k)."""
+def _start(v_enc, m, l, ap, payload, payload_bits, return_indices, kappa, max_rows):
+    """Every check that comes before an upload or a launch; returns (layout, B, k, m).  m None is the sort: m = k."""
     check_l(l)
-    if int(max_rows) < 1:
-        raise ValueError(f"max_rows = {max_rows}: expected >= 1")
+    _cut((), 0, max_rows)                                                # max_rows >= 1
     if not isinstance(v_enc, torch.Tensor) or v_enc.dim() != 3:
         raise ValueError("v_enc: expected [B][k][2nw]")
     B, k, words = v_enc.shape
@@ -274,7 +260,12 @@ def _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_
         raise ValueError(f"payload: expected [np][{B}][{k}][{nw2}]")
     elif payload.shape[0] != len(payload_bits):
         raise ValueError(f"payload: {payload.shape[0]} columns, {len(payload_bits)} widths in payload_bits")
-    return _sort_layout(l, k, payload_bits, return_indices, kappa, ap), B, k
+    layout = _sort_layout(l, k, payload_bits, return_indices, kappa, ap)
+    if m is None:
+        m = k
+    elif isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= k:
+        raise ValueError(f"m = {m}: expected an integer, 1 <= m <= k = {k}")
+    return layout, B, k, int(m)
 
 
 def _sort_buffer(v_enc, payload, return_indices, ap, B, k):
@@ -289,49 +280,20 @@ def _sort_buffer(v_enc, payload, return_indices, ap, B, k):
     return torch.stack(cols).contiguous()
 
 
-def _sort_result(buf, payload, return_indices, B, k):
+def _result(buf, payload, return_indices, B, k, m, only_last):
+    """The first m positions of every row of the columns of buf, or -- only_last -- position m - 1 alone.  With m = k these are
+    buf's own rows, anything less is a copy."""
     nw2 = buf.shape[-1]
-    pay = None if payload is None else buf[1:1 + payload.shape[0]].reshape(payload.shape[0], B, k, nw2)
-    idx = buf[-1].reshape(B, k, nw2) if return_indices else None
-    return buf[0].reshape(B, k, nw2), pay, idx
-
-
-def secure_sort_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
-                      payload: torch.Tensor | None = None, payload_bits=(), descending: bool = False, return_indices: bool = False,
-                      kappa: int = 40, max_rows: int = 65536):
-    """Sort k values per row, v_enc [B][k][2nw] (0 <= v < 2^l): (sorted [B][k][2nw], payload [np][B][k][2nw] or None, indices
-    [B][k][2nw] or None).  Payload columns (payload_bits[c] bits wide) and the original positions (return_indices) travel with
-    their key.  Every layer of the network is cut into sub-batches of at most max_rows comparisons, each one comparison and one
-    compare-exchange selection.  Equal keys are never exchanged; the sort is not stable."""
-    ap = alice_paillier
-    layout, B, k = _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_rows)
-    buf = _sort_buffer(v_enc, payload, return_indices, ap, B, k)
-    out = buf.reshape(-1, buf.shape[-1])
-    for f, g, lo, hi in _sort_steps(buf, B, k, int(max_rows), descending):
-        _cx_batch(layout, l, f, g, ap, alice_dgk, bob_paillier, bob_dgk, out=out, lo_index=lo, hi_index=hi)
-    return _sort_result(buf, payload, return_indices, B, k)
-
-
-# ---- top-m and the k-th order statistic in one process -----------------------------------------------------------------------------
-def _topk_start(v_enc, m, l, ap, payload, payload_bits, return_indices, kappa, max_rows):
-    """_sort_start and 1 <= m <= k; returns (layout, B, k, m)."""
-    layout, B, k = _sort_start(v_enc, l, ap, payload, payload_bits, return_indices, kappa, max_rows)
-    if isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= k:
-        raise ValueError(f"m = {m}: expected an integer, 1 <= m <= k = {k}")
-    return layout, B, k, int(m)
-
-
-def _topk_result(buf, payload, return_indices, B, k, m, only_last):
-    """The first m positions of every row, or -- only_last -- position m - 1 alone, as copies."""
-    key, pay, idx = _sort_result(buf, payload, return_indices, B, k)
     cut = (lambda t: t[..., m - 1, :].contiguous()) if only_last else (lambda t: t[..., :m, :].contiguous())
-    return cut(key), None if pay is None else cut(pay), None if idx is None else cut(idx)
+    pay = None if payload is None else cut(buf[1:1 + payload.shape[0]].reshape(payload.shape[0], B, k, nw2))
+    idx = cut(buf[-1].reshape(B, k, nw2)) if return_indices else None
+    return cut(buf[0].reshape(B, k, nw2)), pay, idx
 
 
 def _topk_buffer(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, largest, return_indices, kappa, max_rows):
     """The checks and the network over the columns [nf][B k][2nw] in place; returns that buffer: the results sit in the first m
     positions of every row, every other position holds whatever its last live output -- or the input -- left there."""
-    layout, B, k, m = _topk_start(v_enc, m, l, ap, payload, payload_bits, return_indices, kappa, max_rows)
+    layout, B, k, m = _start(v_enc, m, l, ap, payload, payload_bits, return_indices, kappa, max_rows)
     buf = _sort_buffer(v_enc, payload, return_indices, ap, B, k)
     out = buf.reshape(-1, buf.shape[-1])
     for f, g, lo, hi in _topk_steps(buf, B, k, m, only_last, int(max_rows), largest):
@@ -341,7 +303,20 @@ def _topk_buffer(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, 
 
 def _topk_run(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, largest, return_indices, kappa, max_rows):
     buf = _topk_buffer(v_enc, m, only_last, l, ap, ad, bp, bd, payload, payload_bits, largest, return_indices, kappa, max_rows)
-    return _topk_result(buf, payload, return_indices, v_enc.shape[0], v_enc.shape[1], int(m), only_last)
+    B, k = v_enc.shape[:2]
+    return _result(buf, payload, return_indices, B, k, k if m is None else int(m), only_last)
+
+
+def secure_sort_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
+                      payload: torch.Tensor | None = None, payload_bits=(), descending: bool = False, return_indices: bool = False,
+                      kappa: int = 40, max_rows: int = 65536):
+    """Sort k values per row, v_enc [B][k][2nw] (0 <= v < 2^l): (sorted [B][k][2nw], payload [np][B][k][2nw] or None, indices
+    [B][k][2nw] or None).  Payload columns (payload_bits[c] bits wide) and the original positions (return_indices) travel with
+    their key.  Every layer of the network is cut into sub-batches of at most max_rows comparisons, each one comparison and one
+    compare-exchange selection.  Equal keys are never exchanged; the sort is not stable.  The path is secure_topk_batch's with
+    m = k: topk_network(k, k) is batcher_network(k) with every output live."""
+    return _topk_run(v_enc, None, False, l, alice_paillier, alice_dgk, bob_paillier, bob_dgk, payload, payload_bits, descending,
+                     return_indices, kappa, max_rows)
 
 
 def secure_topk_batch(v_enc: torch.Tensor, m: int, l: int, alice_paillier: Paillier, alice_dgk: DGK, bob_paillier: Paillier, bob_dgk: DGK,
@@ -381,28 +356,51 @@ def secure_median_batch(v_enc: torch.Tensor, l: int, alice_paillier: Paillier, a
 # An opening message tells the key holder what he cannot derive, B; he refuses a header that differs from his own arguments in anything
 # else and derives the schedule from it.  Sub-batch i is then the unchanged comparison session and one selection exchange under the tag
 # `session_{sid}_{word}_{i}`, word = `sort` or `topk`: the key holder's work does not depend on which outputs are live.
-def _player_checks(v_enc, max_rows, chunks) -> None:
+# The header `{word}_0_session_{sid}` is int32: the word's own fields -- k for `sort`; k, m, only_last for `topk` -- then B, max_rows,
+# kappa and the column widths.  The callers below pass in the word and what differs.
+async def _alice_half(ini, word, v_enc, m, only_last, payload, payload_bits, flip, return_indices, kappa, source, engine, generator,
+                      chunks, max_rows):
+    """The initiator's half of `word`, in place in the columns' buffer.  m None: the sort, m = k, whose header has k alone."""
     no_chunks(chunks)
     if not isinstance(v_enc, torch.Tensor) or v_enc.dim() != 3:
         raise ValueError("v_enc: expected [B][k][2nw]")
     if not 1 <= int(max_rows) < 1 << 31:
         raise ValueError(f"max_rows = {max_rows}: expected 1 <= max_rows < 2^31")
-
-
-async def _alice_network(ini, sid, word, layout, steps, out, source, generator) -> None:
-    """Alice's compare-exchanges of `steps` (_sort_steps or _topk_steps), in place in `out`."""
-    pai = ini.scheme_paillier
-    for i, (f, g, lo, hi) in enumerate(steps):
+    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
+    pai, sort = ini.scheme_paillier, m is None
+    layout, B, k, m = _start(v_enc, m, ini.l_maximum_bit_length, pai, payload, payload_bits, return_indices, kappa, max_rows)
+    fields = [k] if sort else [k, m, int(only_last)]
+    head = torch.tensor([*fields, B, int(max_rows), *layout.header], dtype=torch.int32, device=v_enc.device)
+    await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"{word}_0_session_{sid}")
+    buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
+    out = buf.reshape(-1, buf.shape[-1])
+    for i, (f, g, lo, hi) in enumerate(_topk_steps(buf, B, k, m, only_last, int(max_rows), flip)):
         tag = f"session_{sid}_{word}_{i}"
         delta, d_key = await _alice_compare(ini, tag, f[0], g[0], None, source, generator)
         d = cx_differences(pai, layout, f, g, d_key)
         products, plain, sd = await _alice_exchange(ini, tag, layout, delta, d, None, source, generator)
         cx_finish(layout, delta, d, f, g, products, plain, sd, pai, out, lo, hi)
+    return _result(buf, payload, return_indices, B, k, m, only_last)
 
 
-async def _bob_network(kh, sid, word, layout, counts, source, generator) -> None:
-    """The key holder's side of the sub-batches of `counts` (schedule_counts or topk_counts); one of another size is refused."""
-    for i, count in enumerate(counts):
+async def _bob_half(kh, sid, word, fields, layers, payload_bits, return_indices, kappa, source, generator, max_rows):
+    """The key holder's half of `word` over the network `layers`, after he opened session sid.  fields: his own header fields by name,
+    k first.  He refuses, in this order, a malformed header, one that announces something else than his arguments and a negative B,
+    and then every sub-batch of another size than the schedule's."""
+    pai, n = kh.scheme_paillier, len(fields)
+    layout = _sort_layout(kh.l_maximum_bit_length, fields["k"], payload_bits, return_indices, kappa, pai)
+    (head,) = wire.incoming(await kh.communicator.recv(kh.other_party, msg_id=f"{word}_0_session_{sid}"), pai.engine.device, expect=1)
+    if not isinstance(head, torch.Tensor) or head.dim() != 1 or not n + 4 <= head.shape[0] <= n + 3 + MAX_FIELDS:
+        raise ValueError(f"{word}: malformed header")
+    theirs = [int(v) for v in head.cpu().tolist()]
+    B = theirs.pop(n)
+    mine = [*fields.values(), int(max_rows), *layout.header]
+    if theirs != mine:
+        raise ValueError(f"{word}: the initiator announces {', '.join(fields)}, max_rows, kappa and widths {theirs}, "
+                         f"this key holder expects {mine}")
+    if B < 0:
+        raise ValueError(f"{word}: the initiator announces B = {B}")
+    for i, count in enumerate(_counts(layers, B, int(max_rows))):
         tag = f"session_{sid}_{word}_{i}"
         got = await kh._batch_session(tag, None, None, source, generator)
         if got != count:
@@ -410,66 +408,24 @@ async def _bob_network(kh, sid, word, layout, counts, source, generator) -> None
         await _bob_select(kh, tag, layout, count, None, source, generator)
 
 
-# `sort_0_session_{sid}` is int32: k, B, max_rows, kappa, the column widths.
 async def alice_sort(ini, v_enc, payload, payload_bits, descending, return_indices, kappa, source, engine, generator, chunks, max_rows):
-    _player_checks(v_enc, max_rows, chunks)
-    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
-    pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
-    layout, B, k = _sort_start(v_enc, l, pai, payload, payload_bits, return_indices, kappa, max_rows)
-    head = torch.tensor([k, B, int(max_rows), *layout.header], dtype=torch.int32, device=v_enc.device)
-    await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"sort_0_session_{sid}")
-    buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
-    steps = _sort_steps(buf, B, k, int(max_rows), descending)
-    await _alice_network(ini, sid, "sort", layout, steps, buf.reshape(-1, buf.shape[-1]), source, generator)
-    return _sort_result(buf, payload, return_indices, B, k)
+    return await _alice_half(ini, "sort", v_enc, None, False, payload, payload_bits, descending, return_indices, kappa, source, engine,
+                             generator, chunks, max_rows)
 
 
 async def bob_sort(kh, k, payload_bits, return_indices, kappa, source, generator, max_rows):
     sid = await kh._open_batch_session()
-    pai = kh.scheme_paillier
-    batcher_network(k)                                                   # k in range
-    layout = _sort_layout(kh.l_maximum_bit_length, k, payload_bits, return_indices, kappa, pai)
-    (head,) = wire.incoming(await kh.communicator.recv(kh.other_party, msg_id=f"sort_0_session_{sid}"), pai.engine.device, expect=1)
-    if not isinstance(head, torch.Tensor) or head.dim() != 1 or not 5 <= head.shape[0] <= 4 + MAX_FIELDS:
-        raise ValueError("sort: malformed header")
-    hk, B, mr, *rest = [int(v) for v in head.cpu().tolist()]
-    mine = [k, int(max_rows), *layout.header]
-    if [hk, mr, *rest] != mine:
-        raise ValueError(f"sort: the initiator announces k, max_rows, kappa and widths {[hk, mr, *rest]}, this key holder expects {mine}")
-    if B < 0:
-        raise ValueError(f"sort: the initiator announces B = {B}")
-    await _bob_network(kh, sid, "sort", layout, schedule_counts(k, B, mr), source, generator)
+    await _bob_half(kh, sid, "sort", {"k": k}, topk_network(k, k), payload_bits, return_indices, kappa, source, generator, max_rows)
 
 
-# `topk_0_session_{sid}` is int32: k, m, only_last, B, max_rows, kappa, the column widths.
 async def alice_topk(ini, v_enc, m, payload, payload_bits, largest, return_indices, kappa, source, engine, generator, chunks, max_rows,
                      only_last):
-    _player_checks(v_enc, max_rows, chunks)
-    only_last = bool(only_last)
-    sid = await ini._open_batch_session(v_enc[:, 0], v_enc[:, 0], engine)
-    pai, l = ini.scheme_paillier, ini.l_maximum_bit_length
-    layout, B, k, m = _topk_start(v_enc, m, l, pai, payload, payload_bits, return_indices, kappa, max_rows)
-    head = torch.tensor([k, m, int(only_last), B, int(max_rows), *layout.header], dtype=torch.int32, device=v_enc.device)
-    await ini.communicator.send(ini.other_party, wire.outgoing(ini.communicator, head), msg_id=f"topk_0_session_{sid}")
-    buf = _sort_buffer(v_enc, payload, return_indices, pai, B, k)
-    steps = _topk_steps(buf, B, k, m, only_last, int(max_rows), largest)
-    await _alice_network(ini, sid, "topk", layout, steps, buf.reshape(-1, buf.shape[-1]), source, generator)
-    return _topk_result(buf, payload, return_indices, B, k, m, only_last)
+    return await _alice_half(ini, "topk", v_enc, m, bool(only_last), payload, payload_bits, largest, return_indices, kappa, source, engine,
+                             generator, chunks, max_rows)
 
 
 async def bob_topk(kh, k, m, payload_bits, return_indices, kappa, only_last, source, generator, max_rows):
     sid = await kh._open_batch_session()
-    pai, only_last = kh.scheme_paillier, bool(only_last)
-    topk_network(k, m, only_last)                                        # k and m in range
-    layout = _sort_layout(kh.l_maximum_bit_length, k, payload_bits, return_indices, kappa, pai)
-    (head,) = wire.incoming(await kh.communicator.recv(kh.other_party, msg_id=f"topk_0_session_{sid}"), pai.engine.device, expect=1)
-    if not isinstance(head, torch.Tensor) or head.dim() != 1 or not 7 <= head.shape[0] <= 6 + MAX_FIELDS:
-        raise ValueError("topk: malformed header")
-    hk, hm, hol, B, mr, *rest = [int(v) for v in head.cpu().tolist()]
-    mine = [k, int(m), int(only_last), int(max_rows), *layout.header]
-    if [hk, hm, hol, mr, *rest] != mine:
-        raise ValueError(f"topk: the initiator announces k, m, only_last, max_rows, kappa and widths {[hk, hm, hol, mr, *rest]}, "
-                         f"this key holder expects {mine}")
-    if B < 0:
-        raise ValueError(f"topk: the initiator announces B = {B}")
-    await _bob_network(kh, sid, "topk", layout, topk_counts(k, int(m), only_last, B, mr), source, generator)
+    layers = topk_network(k, m, bool(only_last))                         # k and m in range
+    await _bob_half(kh, sid, "topk", {"k": k, "m": int(m), "only_last": int(bool(only_last))}, layers, payload_bits, return_indices, kappa,
+                    source, generator, max_rows)

@@ -70,11 +70,11 @@ def test_network_counts_and_disjoint_layers():
 
 @pytest.mark.parametrize("k,B,max_rows", [(2, 1, 65536), (5, 3, 2), (8, 100, 7), (17, 64, 65536), (17, 64, 100), (32, 5, 1)])
 def test_both_players_derive_the_same_schedule(k, B, max_rows):
-    from protocols.secure_comparison_amd.sorting import _sort_steps, batcher_network, schedule_counts, sort_schedule
+    from protocols.secure_comparison_amd.sorting import _topk_steps, batcher_network, schedule_counts, sort_schedule
 
     nf = 2
     buf = torch.arange(nf * B * k, dtype=torch.int32).reshape(nf, B * k, 1)
-    steps = list(_sort_steps(buf, B, k, max_rows, False))                 # what the initiator runs
+    steps = list(_topk_steps(buf, B, k, k, False, max_rows, False))       # what the initiator runs: the m = k network
     counts = schedule_counts(k, B, max_rows)                              # what the key holder expects
     assert [f.shape[1] for f, _, _, _ in steps] == counts
     assert all(0 < c <= max_rows for c in counts)
@@ -94,12 +94,41 @@ def test_both_players_derive_the_same_schedule(k, B, max_rows):
 
 
 def test_descending_swaps_the_operands():
-    from protocols.secure_comparison_amd.sorting import _sort_steps
+    from protocols.secure_comparison_amd.sorting import _topk_steps
 
     buf = torch.arange(2 * 3, dtype=torch.int32).reshape(1, 6, 1)            # B = 2 rows of k = 3
-    asc = [(lo.tolist(), hi.tolist()) for _, _, lo, hi in _sort_steps(buf, 2, 3, 100, False)]
-    desc = [(lo.tolist(), hi.tolist()) for _, _, lo, hi in _sort_steps(buf, 2, 3, 100, True)]
+    asc = [(lo.tolist(), hi.tolist()) for _, _, lo, hi in _topk_steps(buf, 2, 3, 3, False, 100, False)]
+    desc = [(lo.tolist(), hi.tolist()) for _, _, lo, hi in _topk_steps(buf, 2, 3, 3, False, 100, True)]
     assert desc == [(hi, lo) for lo, hi in asc]
+
+
+def test_sort_steps_equal_the_rows_of_the_replay_model():
+    """A sort's sub-batches against rows written out in plain Python from tests/_draw_replay.py's sort_layers and cuts, a model made
+    from the network's definition: comparison t = c B + b of a layer compares positions i and j of row b, F at i ascending and at j
+    descending; column c's row is c B k further on; every output is live, so no row is the one past the buffer."""
+    import _draw_replay as dr
+    from protocols.secure_comparison_amd.sorting import _topk_steps, schedule_counts
+
+    for k, B, nf in itertools.product((1, 2, 3, 5, 8, 9, 17), (1, 3), (1, 3)):
+        buf = torch.arange(nf * B * k * 2, dtype=torch.int32).reshape(nf, B * k, 2)
+        layers = dr.sort_layers(k)
+        for max_rows, descending in itertools.product((1, 4, 7, 65536), (False, True)):
+            want_lo, want_hi = [], []
+            for layer in layers:
+                pairs = [(b * k + (j if descending else i), b * k + (i if descending else j)) for i, j in layer for b in range(B)]
+                for a, z in dr.cuts(B * len(layer), max_rows):
+                    want_lo.append([[c * B * k + f for f, _ in pairs[a:z]] for c in range(nf)])
+                    want_hi.append([[c * B * k + g for _, g in pairs[a:z]] for c in range(nf)])
+            steps = list(_topk_steps(buf, B, k, k, False, max_rows, descending))
+            assert [lo.tolist() for _, _, lo, _ in steps] == want_lo and [hi.tolist() for _, _, _, hi in steps] == want_hi
+            assert schedule_counts(k, B, max_rows) == [len(rows[0]) for rows in want_lo]
+            flat = buf.reshape(-1, 2)
+            for f, g, lo, hi in steps:
+                assert lo.dtype == hi.dtype == torch.int64 and lo.is_contiguous() and hi.is_contiguous()
+                assert max(lo.max().item(), hi.max().item()) < nf * B * k
+                assert torch.equal(f, flat[lo]) and torch.equal(g, flat[hi])
+            if k == 1:
+                assert steps == [] and schedule_counts(k, B, max_rows) == []
 
 
 # ---- the compare-exchange model ------------------------------------------------------------------------------------------------------
