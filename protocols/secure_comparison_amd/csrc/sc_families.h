@@ -76,13 +76,19 @@ static int mul_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int 
   return SC_OK;
 }
 static int mul_ebits(const MulLayout& lay) { int b = lay.s; for (int j = 0; j < lay.nf; j++) b = std::max(b, lay.fbits[j]); return b; }
+// two refusals the scheme-level entries share: exponent rows of ew words hold `bits` bits; finish_ratio's coef is +1, -1 or -2
+static int exp_rows(sc_ctx* ctx, const char* who, int ew, int bits) {
+  return 32 * ew < bits ? fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, bits) : SC_OK;
+}
+static int ratio_coef(sc_ctx* ctx, const char* who, int coef) {
+  return coef != 1 && coef != -1 && coef != -2 ? fail(ctx, SC_ERR_ARG, "%s: coef = %d: expected +1, -1 or -2", who, coef) : SC_OK;
+}
 // the draws' and exponents' row widths of the multiplication and the inner product: the kernels hold a field in MUL_FIELD_WORDS words
 // (bw_max: the multiplication's r_b rows are no wider than N either; has_b: a square reads no r_b)
 static int row_words(sc_ctx* ctx, const char* who, int ebits, int aw, int bw, bool has_b, int bw_max, int ew) {
   if (aw < 1 || aw > MUL_FIELD_WORDS || (has_b && (bw < 1 || bw > bw_max)) || ew < 1)
     return fail(ctx, SC_ERR_ARG, "%s: rows of %d (r_a), %d (r_b), %d (e) words: expected 1 .. %d for the draws", who, aw, bw, ew, MUL_FIELD_WORDS);
-  if (32 * ew < ebits) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, ebits);
-  return SC_OK;
+  return exp_rows(ctx, who, ew, ebits);
 }
 
 int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,

@@ -3,7 +3,7 @@
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
 // sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip, sc_launch_scan.hip and
 // sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
-// the HIP-free plans and checks of the two axis entries) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// the HIP-free plans and checks of the two axis entries, and sc_pack_plan.h, the HIP-free field lists of the four pack entries) holds no device code, so a change of host logic or policy rebuilds in seconds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>

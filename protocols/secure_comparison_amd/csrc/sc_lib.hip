@@ -3,6 +3,7 @@
 // the sc_launch_*.hip translation units (sc_internal.h), so this file holds no device code.
 #include "sc_internal.h"
 #include "sc_axis_plan.h"
+#include "sc_pack_plan.h"
 
 #include <functional>
 #include <type_traits>

@@ -728,7 +728,7 @@ int sc_initiator_step67(sc_ctx* ctx, int paillier_key_id, const uint64_t* delta_
 // of shared-exponent squarings, T_j with per-row exponents (pair kernel, or exponentiations modulo N^2 where the modulus has no
 // per-row pair instance), and the two finishes.  Temporaries TMP_SEL_*; the callees' own (TMP_S_A .. TMP_S_D, TMP_PAIR) are not held
 // across their calls.  The selection, the multiplication (§8e), the inner product (§8g) and the one-hot encoding (§8i) share one blinded
-// round trip: blind_and_randomize and horner_pow2 pack, keyholder_round is the key holder's step, finish_ratio divides
+// round trip: pack_messages packs a family's field list (sc_pack_plan.h), keyholder_round is the key holder's step, finish_ratio divides
 // the blinding out (the one-hot has nothing to divide out: its finish is a rotation of rows).
 enum SelectTmp { TMP_SEL_A = 49, TMP_SEL_B, TMP_SEL_C, TMP_SEL_D, TMP_SEL_E, TMP_SEL_F };
 
@@ -813,8 +813,7 @@ static int sel_t(sc_ctx* ctx, const PaillierKey& k, const SelLayout& lay, const 
 
 static int sel_finish_args(sc_ctx* ctx, const char* who, const PaillierKey* kp, const SelLayout& lay, int aw, int ew, bool ptrs_ok) {
   if (!kp || !ptrs_ok || aw < 1 || aw > 2 || ew < 1) return fail(ctx, SC_ERR_ARG, "%s: bad argument", who);
-  if (32 * ew < sel_t_bits(lay)) return fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, sel_t_bits(lay));
-  return SC_OK;
+  return exp_rows(ctx, who, ew, sel_t_bits(lay));
 }
 
 // ---- the blinded round trip the selection, the multiplication and the inner product share ----------------------------
@@ -834,41 +833,35 @@ static int blind_and_randomize(sc_ctx* ctx, const PaillierKey& k, int key_id, co
   return sc_paillier_randomize(ctx, key_id, dst, rho, dst, items);        // * rho^N
 }
 
-// prod_f field_f^(2^off_f): the exponents are shared by the batch, so Horner from the top field with squarings only.  fld[0 .. n] from the
-// top down, fld[n] the low operand: a field's rows, the bits it lies above the next field, and the rows it holds -- a prefix of the next
-// field's, whose further rows join as copies of themselves.  Step i writes half[(n - 1 - i) & 1], the last one `out`.
-struct HornerField { const uint32_t* rows; int shift; uint64_t held; };
-static int horner_pow2(sc_ctx* ctx, const PaillierKey& k, const HornerField* fld, int n, uint32_t* const half[2], uint32_t* out) {
+// out = msg prod_(f >= 1) field_f^(2^off_f), off_f the bits of fld[0 .. f - 1] (sc_pack_plan.h; msg stands in for field 0): the exponents
+// are shared by the batch, so Horner from the top field with squarings only.  A field holds a prefix of the rows of the one below it, whose
+// further rows join as copies of themselves.  The step that joins field f - 1 writes half[(f - 1) & 1], the last one `out`.
+static int horner_pow2(sc_ctx* ctx, const PaillierKey& k, const PackField* fld, int F, const uint32_t* msg, uint32_t* const half[2], uint32_t* out) {
   const size_t w2 = 2 * (size_t)k.nw;
-  const uint32_t* cur = fld[0].rows;
-  for (int i = 0; i < n; i++) {
-    uint32_t* dst = i == n - 1 ? out : half[(n - 1 - i) & 1];
-    const HornerField& low = fld[i + 1];
-    const uint64_t ncur = fld[i].held;
-    int rc = sel_pow2(ctx, k, fld[i].shift, cur, low.rows, dst, ncur); if (rc) return rc;
-    if (low.held > ncur)
-      HIPCHK(ctx, hipMemcpyAsync(dst + ncur * w2, low.rows + ncur * w2, (low.held - ncur) * w2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  const uint32_t* cur = fld[F - 1].rows;
+  for (int f = F - 1; f >= 1; f--) {
+    uint32_t* dst = f == 1 ? out : half[(f - 1) & 1];
+    const uint32_t* low = f == 1 ? msg : fld[f - 1].rows;
+    const uint64_t ncur = fld[f].held, nlow = fld[f - 1].held;
+    int rc = sel_pow2(ctx, k, fld[f - 1].bits, cur, low, dst, ncur); if (rc) return rc;
+    if (nlow > ncur) HIPCHK(ctx, hipMemcpyAsync(dst + ncur * w2, low + ncur * w2, (nlow - ncur) * w2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
     cur = dst;
   }
   return SC_OK;
 }
 
-// The pack step of the selection and the multiplication once the entry has checked its arguments: R from the family's prep kernel
-// (`prep`, given R), m = [[x + R]] rho_p^N, then P = m prod_j [[col_j]]^(2^off_j) -- every field holds `count` rows
-static int pack_columns(sc_ctx* ctx, const PaillierKey& k, int key_id, const char* who, int nf, const int* off, const uint32_t* x, const uint32_t* cols,
-                        const uint32_t* rho_p, uint32_t* p_out, uint64_t count, const std::function<int(uint32_t*)>& prep) {
-  const size_t col = (size_t)count * 2 * k.nw;
-  uint32_t *R, *m, *acc;
-  int rc = tmp_words(ctx, TMP_SEL_A, (uint64_t)count * k.nw, &R); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, col, &m); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, 2 * col, &acc); if (rc) return rc;
-  if (prep(R)) return fail(ctx, SC_ERR_HIP, "%s: launch failed", who);
-  rc = blind_and_randomize(ctx, k, key_id, x, R, rho_p, m, count); if (rc) return rc;
-  HornerField fld[SEL_MAX_FIELDS + 1];
-  for (int j = nf - 1; j >= 0; j--) fld[nf - 1 - j] = {cols + (size_t)j * col, off[j] - (j > 0 ? off[j - 1] : 0), count};
-  fld[nf] = {m, 0, count};
-  uint32_t* const half[2] = {acc, acc + col};
-  return horner_pow2(ctx, k, fld, nf, half, p_out);
+// The pack step of all four families once the entry has checked its arguments, launched its prep kernel (R [items][nw], TMP_SEL_A) and
+// listed its fields: field 0, held by all `items` messages, becomes m = [[x + R]] rho_p^N (TMP_SEL_B) -- P itself where it is the only
+// field -- and the fields above it join by horner_pow2 over the two halves of TMP_SEL_C.
+static int pack_messages(sc_ctx* ctx, const PaillierKey& k, int key_id, const std::vector<PackField>& fld, const uint32_t* R, const uint32_t* rho_p,
+                         uint32_t* p_out, uint64_t items) {
+  const size_t words = items * 2 * k.nw;
+  uint32_t *m, *acc;
+  int rc = tmp_words(ctx, TMP_SEL_B, words, &m); if (rc) return rc;
+  rc = tmp_words(ctx, TMP_SEL_C, 2 * words, &acc); if (rc) return rc;
+  rc = blind_and_randomize(ctx, k, key_id, fld[0].rows, R, rho_p, fld.size() == 1 ? p_out : m, items); if (rc) return rc;
+  uint32_t* const half[2] = {acc, acc + words};
+  return horner_pow2(ctx, k, fld.data(), (int)fld.size(), m, half, p_out);
 }
 
 // The key holder's step: decrypt the n_messages rows of P, let the family's split kernel (`split`, given the plaintexts, the n_products
@@ -1002,11 +995,12 @@ int sc_initiator_select_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int nf
   if (!rho_p) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: rho_p is required: P must carry a fresh rho^N");
   if (!sigma_enc || !d_enc || !r_a || !r_b || !p_out || !e_out || !rab_out || aw < 1 || aw > 2 || bw < 1 || bw > k.nw || ew < 1)
     return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: bad argument");
-  if (32 * ew < sel_t_bits(lay)) return fail(ctx, SC_ERR_ARG, "sc_initiator_select_pack: exponent rows of %d words are too narrow for %d bits", ew, sel_t_bits(lay));
+  rc = exp_rows(ctx, "sc_initiator_select_pack", ew, sel_t_bits(lay)); if (rc) return rc;
   if (count == 0) return SC_OK;
-  return pack_columns(ctx, k, paillier_key_id, "sc_initiator_select_pack", nfields, lay.off, sigma_enc, d_enc, rho_p, p_out, count, [&](uint32_t* R) {
-    return launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out);
-  });
+  uint32_t* R;
+  rc = tmp_words(ctx, TMP_SEL_A, count * k.nw, &R); if (rc) return rc;
+  if (launch_select_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_select_pack: launch failed");
+  return pack_messages(ctx, k, paillier_key_id, column_fields(sigma_enc, d_enc, nfields, lay.s, lay.fbits, count, (size_t)count * 2 * k.nw), R, rho_p, p_out, count);
 }
 
 int sc_keyholder_select_mult(sc_ctx* ctx, int paillier_key_id, int kappa, int nfields, const int* widths_hptr, const uint32_t* p_enc,
@@ -1096,9 +1090,10 @@ int sc_initiator_mul_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, i
   if (!x_enc || !y_enc || !r_a || !r_b || !p_out || !e_out || !rab_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_pack: bad argument");
   rc = row_words(ctx, "sc_initiator_mul_pack", mul_ebits(lay), aw, bw, true, std::min(k.nw, MUL_FIELD_WORDS), ew); if (rc) return rc;
   if (count == 0) return SC_OK;
-  return pack_columns(ctx, k, paillier_key_id, "sc_initiator_mul_pack", nfields, lay.off, x_enc, y_enc, rho_p, p_out, count, [&](uint32_t* R) {
-    return launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out);
-  });
+  uint32_t* R;
+  rc = tmp_words(ctx, TMP_SEL_A, count * k.nw, &R); if (rc) return rc;
+  if (launch_mul_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, R, e_out, rab_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_mul_pack: launch failed");
+  return pack_messages(ctx, k, paillier_key_id, column_fields(x_enc, y_enc, nfields, lay.s, lay.fbits, count, (size_t)count * 2 * k.nw), R, rho_p, p_out, count);
 }
 
 int sc_keyholder_mul(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p_enc,
@@ -1124,8 +1119,8 @@ int sc_initiator_mul_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   MulLayout lay;
   int rc = mul_layout(ctx, "sc_initiator_mul_finish", big_bits(k.n), kappa, wx, nfields, wy_hptr, 0, &lay); if (rc) return rc;
   if (!x_enc || !y_enc || !products || !e || !rab || !out || ew < 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: bad argument");
-  if (coef != 1 && coef != -1 && coef != -2) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: coef = %d: expected +1, -1 or -2", coef);
-  if (32 * ew < mul_ebits(lay)) return fail(ctx, SC_ERR_ARG, "sc_initiator_mul_finish: exponent rows of %d words are too narrow for %d bits", ew, mul_ebits(lay));
+  rc = ratio_coef(ctx, "sc_initiator_mul_finish", coef); if (rc) return rc;
+  rc = exp_rows(ctx, "sc_initiator_mul_finish", ew, mul_ebits(lay)); if (rc) return rc;
   if (count == 0) return SC_OK;
   const int w2 = 2 * k.nw;
   const uint64_t items = (uint64_t)nfields * count;
@@ -1154,30 +1149,12 @@ int sc_initiator_dot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, i
   if (!x_enc || !r_a || (!square && (!y_enc || !r_b)) || !p_out || !e_out || !s_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_pack: bad argument");
   rc = row_words(ctx, "sc_initiator_dot_pack", lay.ebits, aw, bw, !square, MUL_FIELD_WORDS, ew); if (rc) return rc;
   if (count == 0) return SC_OK;
-  const int w2 = 2 * k.nw, M = lay.M;
-  const size_t col = (size_t)count * w2;               // one plane
-  const uint64_t items = (uint64_t)M * count;          // the messages
-  uint32_t *R, *m, *acc;
+  const uint64_t items = (uint64_t)lay.M * count;      // the messages
+  uint32_t* R;
   rc = tmp_words(ctx, TMP_SEL_A, items * k.nw, &R); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, items * w2, &m); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, 2 * items * w2, &acc); if (rc) return rc;
   if (launch_dot_prep(ctx->stream, r_a, aw, r_b, bw, lay, k.nw, ew, count, e_out, R, s_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_dot_pack: launch failed");
-  // the fields from the low end: x and y of position 0, x and y of position 1, ..; field f of position t = f / fp is held by the messages
-  // m < n(f), all M of them below the top position.  Field 0 -- the planes x_0 .. x_(M-1) -- is folded into [[x + R]] rho_p^N.
-  const int fp = square ? 1 : 2, npos = (kk + M - 1) / M, F = fp * npos;
-  const int n_top = kk - (npos - 1) * M;
-  auto rows = [&](int f) { return ((f % fp) ? y_enc : x_enc) + (size_t)(f / fp) * M * col; };
-  auto fbits = [&](int f) { return (f % fp) ? lay.sb : lay.sa; };
-  auto held = [&](int f) { return (uint64_t)(f / fp == npos - 1 ? n_top : M) * count; };
-  uint32_t* m_dst = F == 1 ? p_out : m;
-  rc = blind_and_randomize(ctx, k, paillier_key_id, x_enc, R, rho_p, m_dst, items); if (rc) return rc;      // * rho_p_m^N
-  // Horner from the top field: cur^(2^bits(f - 1)) times field f - 1; the messages that join below the partial top position start as a
-  // copy of their own field
-  std::vector<HornerField> fld(F);
-  for (int f = F - 1; f >= 1; f--) fld[F - 1 - f] = {rows(f), fbits(f - 1), held(f)};
-  fld[F - 1] = {m, 0, held(0)};
-  uint32_t* const half[2] = {acc + items * w2, acc};
-  return horner_pow2(ctx, k, fld.data(), F - 1, half, p_out);
+  // x and y of position 0, x and y of position 1, ..; a message below the partial top position joins the chain as a copy of its field
+  return pack_messages(ctx, k, paillier_key_id, dot_fields(x_enc, y_enc, square, kk, lay.M, lay.sa, lay.sb, count, (size_t)count * 2 * k.nw), R, rho_p, p_out, items);
 }
 
 int sc_keyholder_dot(sc_ctx* ctx, int paillier_key_id, int kappa, int wx, int wy, int square, int kk, const uint32_t* p_enc, const uint32_t* rho_d,
@@ -1218,8 +1195,8 @@ int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
   DotLayout lay;
   int rc = dot_layout(ctx, "sc_initiator_dot_finish", big_bits(k.n), kappa, wx, wy, 0, square, kk, &lay); if (rc) return rc;
   if (!x_enc || (!square && !y_enc) || !d_enc || !e || !s || !out || ew < 1) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: bad argument");
-  if (coef != 1 && coef != -1 && coef != -2) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: coef = %d: expected +1, -1 or -2", coef);
-  if (32 * ew < lay.ebits) return fail(ctx, SC_ERR_ARG, "sc_initiator_dot_finish: exponent rows of %d words are too narrow for %d bits", ew, lay.ebits);
+  rc = ratio_coef(ctx, "sc_initiator_dot_finish", coef); if (rc) return rc;
+  rc = exp_rows(ctx, "sc_initiator_dot_finish", ew, lay.ebits); if (rc) return rc;
   if (count == 0) return SC_OK;
   const int w2 = 2 * k.nw;
   const size_t col = (size_t)count * w2;
@@ -1247,7 +1224,7 @@ int sc_initiator_dot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int wx,
 // every index, and since d_q mod k = (i_q + r_q) mod k the initiator reads row (t + r_q mod k) mod k as row t -- no arithmetic modulo N^2
 // after the key holder's answer.  Index q lives in message q div g at position q mod g, so the planes of one position are NOT contiguous
 // in index_enc [m][count][2 nw] once a row takes more than one message: they are gathered position by position (TMP_SEL_D) before the
-// Horner chain, which then runs as the inner product's.  Same temporaries as the selection's.
+// shared packer runs.  Same temporaries as the selection's.
 int sc_initiator_onehot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int ib, int kk, int m, const uint32_t* index_enc, const uint32_t* r,
                              int rw, const uint32_t* rho_p, uint32_t* p_out, int32_t* rot_out, uint64_t count) {
   const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
@@ -1263,39 +1240,19 @@ int sc_initiator_onehot_pack(sc_ctx* ctx, int paillier_key_id, int kappa, int ib
   if (!rot_out) return fail(ctx, SC_ERR_ARG, "sc_initiator_onehot_pack: rot_out: missing array");
   rc = onehot_rows(ctx, "sc_initiator_onehot_pack", kk, m, count); if (rc) return rc;
   if (count == 0) return SC_OK;
-  const int w2 = 2 * k.nw, M = lay.M, g = lay.g;
-  const size_t col = (size_t)count * w2;               // one plane
+  const int M = lay.M, g = lay.g;
+  const size_t col = (size_t)count * 2 * k.nw;         // one plane
   const uint64_t items = (uint64_t)M * count;          // the messages
-  const int F = M > 1 ? g : m;                         // positions in use
-  const int n_last = m - (M - 1) * g;                  // fields of the last message: positions >= n_last are held by M - 1 messages
-  uint32_t *R, *msg, *acc, *gat = nullptr;
+  uint32_t *R, *gat = nullptr;
   rc = tmp_words(ctx, TMP_SEL_A, items * k.nw, &R); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_B, items * w2, &msg); if (rc) return rc;
-  rc = tmp_words(ctx, TMP_SEL_C, 2 * items * w2, &acc); if (rc) return rc;
   if (launch_onehot_prep(ctx->stream, r, rw, lay, k.nw, count, R, rot_out)) return fail(ctx, SC_ERR_HIP, "sc_initiator_onehot_pack: launch failed");
-  auto held = [&](int pos) { return (uint64_t)(pos < n_last ? M : M - 1) * count; };
-  std::vector<const uint32_t*> rows(F);
-  if (M == 1) {
-    for (int pos = 0; pos < F; pos++) rows[pos] = index_enc + (size_t)pos * col;
-  } else {
-    rc = tmp_words(ctx, TMP_SEL_D, (uint64_t)m * col, &gat); if (rc) return rc;
-    uint32_t* dst = gat;
-    for (int pos = 0; pos < F; pos++) {
-      rows[pos] = dst;
-      for (int mm = 0; (uint64_t)mm * count < held(pos); mm++, dst += col)
-        HIPCHK(ctx, hipMemcpyAsync(dst, index_enc + (size_t)(mm * g + pos) * col, col * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-  }
-  // position 0 -- held by every message -- is folded into [[i + R]] rho_p^N; Horner from the top position: cur^(2^f) times the next one
-  // down; the last message joins below its own top position as a copy of its field
-  uint32_t* m_dst = F == 1 ? p_out : msg;
-  rc = blind_and_randomize(ctx, k, paillier_key_id, rows[0], R, rho_p, m_dst, items); if (rc) return rc;
-  if (F == 1) return SC_OK;
-  std::vector<HornerField> fld(F);
-  for (int pos = F - 1; pos >= 1; pos--) fld[F - 1 - pos] = {rows[pos], lay.f, held(pos)};
-  fld[F - 1] = {msg, 0, items};
-  uint32_t* const half[2] = {acc + items * w2, acc};
-  return horner_pow2(ctx, k, fld.data(), F - 1, half, p_out);
+  if (M > 1) { rc = tmp_words(ctx, TMP_SEL_D, (uint64_t)m * col, &gat); if (rc) return rc; }
+  const std::vector<PackField> fld = onehot_fields(M > 1 ? gat : index_enc, m, g, M, lay.f, count, col);
+  // the gather: the planes of one position sit g planes apart in index_enc and become consecutive rows of their field
+  for (size_t pos = 0; gat && pos < fld.size(); pos++)
+    for (size_t mm = 0; mm * count < fld[pos].held; mm++)
+      HIPCHK(ctx, hipMemcpyAsync(gat + (fld[pos].rows - gat) + mm * col, index_enc + (mm * g + pos) * col, col * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return pack_messages(ctx, k, paillier_key_id, fld, R, rho_p, p_out, items);
 }
 
 int sc_keyholder_onehot(sc_ctx* ctx, int paillier_key_id, int kappa, int ib, int kk, int m, const uint32_t* p_enc, const uint32_t* rho_e,

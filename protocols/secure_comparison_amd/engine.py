@@ -5,6 +5,7 @@ All arithmetic happens in libsc_amd.so on the GPU; this module only moves pointe
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Iterable
 
@@ -975,10 +976,16 @@ class Engine:
         wa = np.array([int(w) for w in widths], dtype=np.int32)
         return wa, wa.ctypes.data_as(C.c_void_p)
 
-    def _columns(self, t: torch.Tensor, name: str, nf: int, count: int, words: int | None) -> torch.Tensor:
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != nf or t.shape[1] != count:
-            raise ValueError(f"{name}: expected [{nf}][{count}][words]")
-        return self._arr(t, name, nf * count, words)
+    def _planes(self, t: torch.Tensor, name: str, lead, count: int | None, words: int | None = None, *, flat: bool = False) -> int:
+        """`t` is [*lead][count][words] ([*lead][count] when `flat`), `lead` one extent or a tuple of them; returns count.  A count of
+        None is read from `t`, and the refusal then prints the word instead of a number; `words` None accepts any row width."""
+        lead = lead if isinstance(lead, tuple) else (lead,)
+        n = len(lead)
+        if (not isinstance(t, torch.Tensor) or t.dim() != n + (1 if flat else 2) or tuple(t.shape[:n]) != lead
+                or (count is not None and t.shape[n] != count)):
+            raise ValueError(f"{name}: expected " + "".join(f"[{d}]" for d in lead) + f"[{'count' if count is None else count}]" + ("" if flat else "[words]"))
+        self._arr(t, name, None if flat else math.prod(lead) * t.shape[n], words)
+        return t.shape[n]
 
     def initiator_select_d(self, key: PaillierKey, z_enc: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
         """[[d]] = [[z]] (1 - r N) from step 1's [[z]] and r (sc_initiator_select_d)."""
@@ -1005,8 +1012,8 @@ class Engine:
         (sc_initiator_cx_differences: one inversion pass, one launch)."""
         nf, nw = len(widths), key.mod_n.nwords
         count = self._items(d_key)
-        self._columns(f_enc, "f_enc", nf, count, 2 * nw)
-        self._columns(g_enc, "g_enc", nf, count, 2 * nw)
+        self._planes(f_enc, "f_enc", nf, count, 2 * nw)
+        self._planes(g_enc, "g_enc", nf, count, 2 * nw)
         self._arr(d_key, "d_key", count, 2 * nw)
         out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
         wa, pw = self._widths(widths)
@@ -1022,9 +1029,9 @@ class Engine:
         nf, nw = len(widths), key.mod_n.nwords
         count = self._items(sigma_enc)
         self._arr(sigma_enc, "sigma_enc", count, 2 * nw)
-        self._columns(d_enc, "d_enc", nf, count, 2 * nw)
+        self._planes(d_enc, "d_enc", nf, count, 2 * nw)
         self._arr(r_a, "r_a", count)
-        self._columns(r_b, "r_b", nf, count, None)
+        self._planes(r_b, "r_b", nf, count, None)
         self._arr(rho_p, "rho_p", count, nw)
         P = self.empty(count, 2 * nw)
         e = torch.empty((nf, count, int(ew)), dtype=torch.int32, device=self.device)
@@ -1042,7 +1049,7 @@ class Engine:
         nf, nw = len(widths), key.mod_n.nwords
         count = self._items(P)
         self._arr(P, "P", count, 2 * nw)
-        self._columns(rho_products, "rho_products", nf, count, nw)
+        self._planes(rho_products, "rho_products", nf, count, nw)
         out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
         wa, pw = self._widths(widths)
         self._sync_stream()
@@ -1053,18 +1060,18 @@ class Engine:
         nf, nw = len(widths), key.mod_n.nwords
         count = self._items(sigma_enc)
         self._arr(sigma_enc, "sigma_enc", count, 2 * nw)
-        self._columns(d_enc, "d_enc", nf, count, 2 * nw)
-        self._columns(products, "products", nf, count, 2 * nw)
+        self._planes(d_enc, "d_enc", nf, count, 2 * nw)
+        self._planes(products, "products", nf, count, 2 * nw)
         self._arr(r_a, "r_a", count)
-        self._columns(e, "e", nf, count, None)
-        self._columns(rab, "rab", nf, count, nw)
+        self._planes(e, "e", nf, count, None)
+        self._planes(rab, "rab", nf, count, nw)
         return nf, nw, count
 
     def initiator_select_finish(self, key: PaillierKey, kappa: int, widths, sigma_enc: torch.Tensor, d_enc: torch.Tensor, b_enc: torch.Tensor,
                                 products: torch.Tensor, r_a: torch.Tensor, e: torch.Tensor, rab: torch.Tensor) -> torch.Tensor:
         """[[b_j + sigma (a_j - b_j)]] [nf][count][2nw] from the key holder's products (sc_initiator_select_finish)."""
         nf, nw, count = self._finish_args(key, widths, sigma_enc, d_enc, products, r_a, e, rab)
-        self._columns(b_enc, "b_enc", nf, count, 2 * nw)
+        self._planes(b_enc, "b_enc", nf, count, 2 * nw)
         out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
         wa, pw = self._widths(widths)
         self._sync_stream()
@@ -1079,8 +1086,8 @@ class Engine:
                             out: torch.Tensor | None = None) -> torch.Tensor:
         """Both outputs of a compare-exchange (sc_initiator_cx_finish); out / lo_index / hi_index as select_finish_cx."""
         nf, nw, count = self._finish_args(key, widths, delta_enc, d_enc, products, r_a, e, rab)
-        self._columns(f_enc, "f_enc", nf, count, 2 * nw)
-        self._columns(g_enc, "g_enc", nf, count, 2 * nw)
+        self._planes(f_enc, "f_enc", nf, count, 2 * nw)
+        self._planes(g_enc, "g_enc", nf, count, 2 * nw)
         if (lo_index is None) != (hi_index is None):
             raise ValueError("lo_index, hi_index: give both or neither")
         if lo_index is None:
@@ -1109,9 +1116,9 @@ class Engine:
         nf, nw = len(wy), key.mod_n.nwords
         count = self._items(x_enc)
         self._arr(x_enc, "x_enc", count, 2 * nw)
-        self._columns(y_enc, "y_enc", nf, count, 2 * nw)
+        self._planes(y_enc, "y_enc", nf, count, 2 * nw)
         self._arr(r_a, "r_a", count)
-        self._columns(r_b, "r_b", nf, count, None)
+        self._planes(r_b, "r_b", nf, count, None)
         self._arr(rho_p, "rho_p", count, nw, optional=True)
         P = self.empty(count, 2 * nw)
         e = torch.empty((nf + 1, count, int(ew)), dtype=torch.int32, device=self.device)
@@ -1129,7 +1136,7 @@ class Engine:
         nf, nw = len(wy), key.mod_n.nwords
         count = self._items(P)
         self._arr(P, "P", count, 2 * nw)
-        self._columns(rho_products, "rho_products", nf, count, nw)
+        self._planes(rho_products, "rho_products", nf, count, nw)
         out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
         wa, pw = self._widths(wy)
         self._sync_stream()
@@ -1144,12 +1151,12 @@ class Engine:
         nf, nw = len(wy), key.mod_n.nwords
         count = self._items(x_enc)
         self._arr(x_enc, "x_enc", count, 2 * nw)
-        self._columns(y_enc, "y_enc", nf, count, 2 * nw)
-        self._columns(products, "products", nf, count, 2 * nw)
-        self._columns(e, "e", nf + 1, count, None)
-        self._columns(rab, "rab", nf, count, nw)
+        self._planes(y_enc, "y_enc", nf, count, 2 * nw)
+        self._planes(products, "products", nf, count, 2 * nw)
+        self._planes(e, "e", nf + 1, count, None)
+        self._planes(rab, "rab", nf, count, nw)
         if base is not None:
-            self._columns(base, "base", nf, count, 2 * nw)
+            self._planes(base, "base", nf, count, 2 * nw)
         out = torch.empty((nf, count, 2 * nw), dtype=torch.int32, device=self.device)
         wa, pw = self._widths(wy)
         self._sync_stream()
@@ -1165,12 +1172,9 @@ class Engine:
 
     def _dot_planes(self, key, k, square, x_enc, y_enc):
         nw = key.mod_n.nwords
-        if not isinstance(x_enc, torch.Tensor) or x_enc.dim() != 3 or x_enc.shape[0] != k:
-            raise ValueError(f"x_enc: expected [{k}][count][words]")
-        count = x_enc.shape[1]
-        self._columns(x_enc, "x_enc", k, count, 2 * nw)
+        count = self._planes(x_enc, "x_enc", k, None, 2 * nw)
         if not square:
-            self._columns(y_enc, "y_enc", k, count, 2 * nw)
+            self._planes(y_enc, "y_enc", k, count, 2 * nw)
         return nw, count
 
     def initiator_dot_pack(self, key: PaillierKey, kappa: int, wx: int, wy: int, signed: bool, square: bool, k: int, M: int,
@@ -1179,11 +1183,11 @@ class Engine:
         """The messages P [M][count][2nw] and the finish's plaintext arrays (e [2k][count][ew], or [k][count][ew] for a square;
         S [count][nw]) (sc_initiator_dot_pack).  A missing rho_p is the library's ValueError."""
         nw, count = self._dot_planes(key, k, square, x_enc, y_enc)
-        self._columns(r_a, "r_a", k, count, None)
+        self._planes(r_a, "r_a", k, count, None)
         if not square:
-            self._columns(r_b, "r_b", k, count, None)
+            self._planes(r_b, "r_b", k, count, None)
         if rho_p is not None:
-            self._columns(rho_p, "rho_p", M, count, nw)
+            self._planes(rho_p, "rho_p", M, count, nw)
         P = torch.empty((M, count, 2 * nw), dtype=torch.int32, device=self.device)
         e = torch.empty((k if square else 2 * k, count, int(ew)), dtype=torch.int32, device=self.device)
         S = self.empty(count, nw)
@@ -1199,10 +1203,7 @@ class Engine:
         """The key holder's randomized [[D]] [count][2nw] from P [M][count][2nw] (sc_keyholder_dot); ValueError when a decrypted
         message exceeds its end in the layout."""
         nw = key.mod_n.nwords
-        if not isinstance(P, torch.Tensor) or P.dim() != 3 or P.shape[0] != M:
-            raise ValueError(f"P: expected [{M}][count][words]")
-        count = P.shape[1]
-        self._columns(P, "P", M, count, 2 * nw)
+        count = self._planes(P, "P", M, None, 2 * nw)
         self._arr(rho_d, "rho_d", count, nw)
         out = self.empty(count, 2 * nw)
         self._sync_stream()
@@ -1216,7 +1217,7 @@ class Engine:
         """base [[sum_j x_j y_j]]^coef [count][2nw] from the key holder's [[D]] (sc_initiator_dot_finish); coef in {+1, -1, -2}."""
         nw, count = self._dot_planes(key, k, square, x_enc, y_enc)
         self._arr(d_enc, "d_enc", count, 2 * nw)
-        self._columns(e, "e", k if square else 2 * k, count, None)
+        self._planes(e, "e", k if square else 2 * k, count, None)
         self._arr(S, "S", count, nw)
         self._arr(base, "base", count, 2 * nw, optional=True)
         out = self.empty(count, 2 * nw)
@@ -1227,27 +1228,14 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ secure one-hot encoding (one library call each)
-    def _onehot_planes(self, t: torch.Tensor, name: str, lead: tuple[int, ...], words: int | None, dtype=torch.int32) -> int:
-        """`t` is [*lead][count][words] (or [*lead][count] when words is None); returns count."""
-        dims = len(lead) + (1 if words is None else 2)
-        if not isinstance(t, torch.Tensor) or t.dim() != dims or tuple(t.shape[:len(lead)]) != tuple(lead):
-            shape = "".join(f"[{d}]" for d in lead) + "[count]" + ("" if words is None else "[words]")
-            raise ValueError(f"{name}: expected {shape}")
-        count = t.shape[len(lead)]
-        rows = count
-        for d in lead:
-            rows *= d
-        self._arr(t, name, rows if words is not None else None, words, dtype=dtype)
-        return count
-
     def initiator_onehot_pack(self, key: PaillierKey, kappa: int, ib: int, k: int, m: int, M: int, index_enc: torch.Tensor, r: torch.Tensor,
                               rho_p: torch.Tensor | None):
         """The messages P [M][count][2nw] and the rotations rot [m][count] (int32, r mod k) from [[i_q]] [m][count][2nw] and the masks
         r [m][count][rw] (sc_initiator_onehot_pack).  A missing rho_p is the library's ValueError."""
         nw = key.mod_n.nwords
-        count = self._onehot_planes(index_enc, "index_enc", (m,), 2 * nw)
-        self._columns(r, "r", m, count, None)
-        if rho_p is not None and self._onehot_planes(rho_p, "rho_p", (M,), nw) != count:
+        count = self._planes(index_enc, "index_enc", m, None, 2 * nw)
+        self._planes(r, "r", m, count, None)
+        if rho_p is not None and self._planes(rho_p, "rho_p", M, None, nw) != count:
             raise ValueError(f"rho_p: expected [{M}][{count}][{nw}]")
         P = torch.empty((M, count, 2 * nw), dtype=torch.int32, device=self.device)
         rot = torch.empty((m, count), dtype=torch.int32, device=self.device)
@@ -1260,8 +1248,8 @@ class Engine:
         """The key holder's randomized E [m][k][count][2nw], E[q][t] = [[ [t == d_q mod k] ]], from P [M][count][2nw] and the bases
         rho_e [m][k][count][nw] (sc_keyholder_onehot); ValueError when a decrypted message exceeds its end in the layout."""
         nw = key.mod_n.nwords
-        count = self._onehot_planes(P, "P", (M,), 2 * nw)
-        if self._onehot_planes(rho_e, "rho_e", (m, k), nw) != count:
+        count = self._planes(P, "P", M, None, 2 * nw)
+        if self._planes(rho_e, "rho_e", (m, k), None, nw) != count:
             raise ValueError(f"rho_e: expected [{m}][{k}][{count}][{nw}]")
         E = torch.empty((m, k, count, 2 * nw), dtype=torch.int32, device=self.device)
         self._sync_stream()
@@ -1274,12 +1262,12 @@ class Engine:
         """out[q][t][b] = E[q][(t + rot[q][b]) mod k][b], [m][k][count][2nw] (sc_initiator_onehot_finish).  `out` (optional) must not
         overlap E: the library's ValueError."""
         nw = key.mod_n.nwords
-        count = self._onehot_planes(E, "E", (m, k), 2 * nw)
-        if self._onehot_planes(rot, "rot", (m,), None) != count:
+        count = self._planes(E, "E", (m, k), None, 2 * nw)
+        if self._planes(rot, "rot", m, None, flat=True) != count:
             raise ValueError(f"rot: expected [{m}][{count}]")
         if out is None:
             out = torch.empty_like(E)
-        elif self._onehot_planes(out, "out", (m, k), 2 * nw) != count:
+        elif self._planes(out, "out", (m, k), None, 2 * nw) != count:
             raise ValueError(f"out: expected [{m}][{k}][{count}][{2 * nw}]")
         self._sync_stream()
         self._check(self.lib.sc_initiator_onehot_finish(self.ctx, key.id, int(kappa), int(ib), int(k), int(m), self._ptr(E), self._ptr(rot),

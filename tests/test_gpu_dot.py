@@ -252,8 +252,9 @@ def test_steps_bit_exact_vs_model(engine, keys, k, M, signed):
     assert (lay.g, lay.M) == (7, M)
 
 
-@pytest.mark.parametrize("k,M", [(14, 1), (15, 2)])
+@pytest.mark.parametrize("k,M", [(1, 1), (14, 1), (15, 2)])
 def test_steps_square_mode(engine, keys, k, M):
+    """k = 1: a message of one field, so the blinded [[x + R]] rho_p^N is P itself and no squaring follows."""
     sk = _key(keys, 1024)
     ap, bp = _paillier(engine, sk)
     lay = _steps(engine, sk, ap, bp, KAPPA, 32, 0, True, True, k, 300 + k, 1024)

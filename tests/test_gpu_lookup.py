@@ -257,6 +257,15 @@ def test_steps_on_a_512_bit_key(engine, keys):
     assert (lay.g, lay.M) == (10, 2)
 
 
+def test_steps_three_messages_partial_last(engine, keys):
+    """m = 23 at g = 10: three messages, the last with three fields, so the positions 0 .. 2 are held by three messages and 3 .. 9 by
+    two -- the last message joins the chain below its own top position, beside two others that came down it."""
+    sk = _key(keys, 512)
+    ap, bp = _paillier(engine, sk)
+    lay = _steps(engine, sk, ap, bp, KAPPA, 10, 6, 23, 523, 512, 20)
+    assert (lay.g, lay.M) == (10, 3)
+
+
 def test_steps_with_sc_key_no_pairs(engine, keys):
     sk = _key(keys, 1024)
     ap, bp = _paillier(engine, sk, use_pairs=False)
