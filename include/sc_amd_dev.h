@@ -304,7 +304,9 @@ int sc_onehot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int i
 int sc_onehot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* p_dptr,
                     uint32_t* prod_dptr, uint32_t* bad_dptr, uint64_t count);
 /* sc_onehot_rotate (initiator): out[q][t][b] = e[q][(t + rot[q][b]) mod k][b] for rows of `words` words, e and out [m][k][count][words],
- * rot [m][count] int32 (reduced modulo k by the kernel).  out must not overlap e (SC_ERR_ARG). */
+ * rot [m][count] int32.  The kernel reduces rot modulo k as an UNSIGNED 32-bit number, so no value of it reads outside e: for
+ * 0 <= rot < 2^31 that is rot mod k; a negative rot turns by (2^32 + rot) mod k, which is the mathematical residue only where k divides
+ * 2^32.  The library's own callers pass 0 .. k - 1.  out must not overlap e (SC_ERR_ARG). */
 int sc_onehot_rotate(sc_ctx* ctx, int words, int k, int m, const uint32_t* e_dptr, const int32_t* rot_dptr, uint32_t* out_dptr,
                      uint64_t count);
 /* sc_select_finish_cx (initiator, the compare-exchange of a secure sort): from a selection with sigma = delta,

@@ -1,7 +1,8 @@
 """The kernel-edge table (tests/_kernel_edges.py) against the sources it describes, without a GPU: every kernel and template instance
-launched from csrc/sc_launch_misc.hip and launch_xgcd has rows (or a named test elsewhere), every word count lands on the instance it
-is listed under, the inversion rows agree with the kernel's integer model and reach both final signs, the early exit and the long
-runs, the references agree with themselves, and every edge the table promises is present in it."""
+launched from csrc/sc_launch_misc.hip, launch_xgcd and the three families' units has rows (or a named test elsewhere), every kernel
+defined under csrc/ has an owner, every word count lands on the instance it is listed under, the inversion rows agree with the kernel's
+integer model and reach both final signs, the early exit and the long runs, the references agree with themselves and with the
+families' models, the package's own layout classes admit every layout, and every edge the table promises is present in it."""
 import math
 import os
 import re
@@ -21,13 +22,18 @@ def _read(name):
 
 
 # ---- instance coverage ---------------------------------------------------------------------------------------------------------------
-def launched_kernels(misc_text=None, xgcd_text=None):
-    """Every hipLaunchKernelGGL(<kernel><template arguments>, ...) of sc_launch_misc.hip and of launch_xgcd in sc_xgcd.h."""
+FAMILY_UNITS = ("sc_launch_mul.hip", "sc_launch_dot.hip", "sc_launch_lookup.hip")
+
+
+def launched_kernels(misc_text=None, xgcd_text=None, family_texts=None):
+    """Every hipLaunchKernelGGL(<kernel><template arguments>, ...) of sc_launch_misc.hip, of launch_xgcd in sc_xgcd.h and of the three
+    families' units (family_texts: unit name -> a text that replaces the file's)."""
     misc = _read("sc_launch_misc.hip") if misc_text is None else misc_text
     xgcd = _read("sc_xgcd.h") if xgcd_text is None else xgcd_text
     xgcd = xgcd[xgcd.index("inline int launch_xgcd"):]
     xgcd = xgcd[:xgcd.index("\n}\n")]
-    return re.findall(r"hipLaunchKernelGGL\(\s*(\w+(?:<[^>]*>)?)\s*,", misc + xgcd)
+    families = "".join((family_texts or {}).get(u) or _read(u) for u in FAMILY_UNITS)
+    return re.findall(r"hipLaunchKernelGGL\(\s*(\w+(?:<[^>]*>)?)\s*,", misc + xgcd + families)
 
 
 def uncovered(kernels):
@@ -36,7 +42,7 @@ def uncovered(kernels):
 
 def test_every_launched_kernel_has_rows_or_a_named_test():
     got = launched_kernels()
-    assert len(got) == len(set(got)) == 19, sorted(got)
+    assert len(got) == len(set(got)) == 26, sorted(got)
     assert not uncovered(got), uncovered(got)
     assert set(K.COVERED_HERE) | set(K.COVERED_ELSEWHERE) == set(got)            # and the table names nothing that is not compiled
     assert {k for k in got if k.startswith("k_rng_")} == {k for k in K.COVERED_ELSEWHERE if k.startswith("k_rng_")} and \
@@ -48,6 +54,61 @@ def test_every_launched_kernel_has_rows_or_a_named_test():
     for lw in (1, 2, 3, 4):
         assert any(K.lw_of(l) == lw for nw in K.PLAIN_WORDS for l in K.plain_l_values(nw)), lw
     assert K.SEL_LAYOUTS
+    assert K.MUL_LAYOUTS and K.DOT_LAYOUTS and K.ONEHOT_LAYOUTS and K.ROTATE_CASES
+    for kernel, table in K.COVERED_HERE.items():
+        assert getattr(K, table), (kernel, table)
+
+
+def _sources():
+    return {f: _read(f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip"))}
+
+
+def defined_kernels(sources=None):
+    """{kernel name: file} for every __global__ kernel defined under csrc/ (a template once, by its name: the first k_<name>( after the
+    keyword); and the number of times the keyword occurs, which must be the number of names."""
+    out, keywords = {}, 0
+    for name, text in (_sources() if sources is None else sources).items():
+        keywords += len(re.findall(r"__global__", text))
+        for kernel in re.findall(r"__global__\s+void\b.*?\b(k_\w+)\s*\(", text, re.S):
+            out[kernel] = name
+    return out, keywords
+
+
+def owner_of(kernel):
+    """The table of this module or the `file::test` that owns a kernel name, or None."""
+    here = {k.split("<")[0]: v for k, v in K.COVERED_HERE.items()}
+    return here.get(kernel) or K.COVERED_ELSEWHERE.get(kernel) or K.DEFINED_ELSEWHERE.get(kernel)
+
+
+def orphans(found):
+    return sorted(k for k in found if owner_of(k) is None)
+
+
+def test_every_kernel_defined_under_csrc_has_an_owner():
+    """The second ledger, over definitions: a kernel added to any unit fails here until someone says where it is tested."""
+    found, keywords = defined_kernels()
+    assert len(found) == keywords == 23, sorted(found)
+    assert {"k_vm", "k_pvm", "k_xgcd", "k_peak_probe", "k_plain_alice", "k_plain_bob", "k_prod_axis", "k_scan_axis", "k_lin_lift",
+            "k_lin_axis", "k_rng_bits", "k_rng_below", "k_rng_coins", "k_rng_perm"} <= set(found)
+    assert not orphans(found), orphans(found)
+    here = {k.split("<")[0] for k in K.COVERED_HERE}
+    assert here | set(K.COVERED_ELSEWHERE) | set(K.DEFINED_ELSEWHERE) == set(found)          # and no owner of a kernel that is gone
+    assert not set(K.DEFINED_ELSEWHERE) & (here | set(K.COVERED_ELSEWHERE))
+    prose = []
+    for kernel, where in {**K.COVERED_ELSEWHERE, **K.DEFINED_ELSEWHERE}.items():
+        if "::" not in where:
+            prose.append(kernel)
+            continue
+        test_file, test_name = where.split("::")
+        assert f"def {test_name}(" in open(os.path.join(ROOT, test_file)).read(), (kernel, where)
+    assert prose == ["k_peak_probe"]                 # the one kernel without a value to compare: its reason stands in the table
+    # a kernel added to a header or to a unit of its own is reported, with or without launch bounds
+    src = _sources()
+    for unit, text in (("sc_launch_scan.hip", "__global__ void __launch_bounds__(64, (A ? 1 : 2)) k_scan_twin(const ScanArgs a) {}"),
+                       ("sc_kernel_plain.h", "__global__ void k_plain_carol(const uint32_t* __restrict__ r) {}"),
+                       ("sc_launch_new.hip", "template <int W>\n__global__ void k_new_thing(uint32_t* out) {}")):
+        found, keywords = defined_kernels({**src, unit: src.get(unit, "") + "\n" + text + "\n"})
+        assert len(found) == keywords == 24 and orphans(found) == [re.search(r"k_\w+", text).group(0)]
 
 
 def test_the_parser_notices_a_new_instance_and_a_deleted_word_count(monkeypatch):
@@ -59,6 +120,9 @@ def test_the_parser_notices_a_new_instance_and_a_deleted_word_count(monkeypatch)
                                              "  else return -2;")
     assert wider != xgcd and uncovered(launched_kernels(misc, wider)) == ["k_xgcd<16>"]
     assert uncovered(launched_kernels(misc + "\nhipLaunchKernelGGL(k_new_thing, grid, block, 0, s);", xgcd)) == ["k_new_thing"]
+    for unit, twin in zip(FAMILY_UNITS, ("k_mul_twin", "k_dot_twin", "k_onehot_twin")):          # one launch more in each family unit
+        more = _read(unit) + f"\nint f(hipStream_t s) {{ hipLaunchKernelGGL({twin}, dim3(1), dim3(256), 0, s); return launched(); }}\n"
+        assert uncovered(launched_kernels(family_texts={unit: more})) == [twin]
     # an instance whose word counts were deleted from the table fails the routing test below
     monkeypatch.setitem(K.XGCD_WORDS, 4, ())
     with pytest.raises(AssertionError):
@@ -296,3 +360,226 @@ def test_selection_references_agree_with_themselves():
         assert ref["bad"] == 0 and ref["fields"][0] == [(1 << s) - 1] + [(1 << f) - 1 for f in fbits]
         flagged = K.expected_select_split(nbits, kappa, widths, ps[:3] + [ps[3] | 1 << end] + ps[4:], nw)
         assert flagged["bad"] == 1 and flagged["prod"] == ref["prod"]
+
+
+# ---- the three families: layouts, conditions, references ------------------------------------------------------------------------------
+def _package_layout(c):
+    """The layout as the package's own class states it; ValueError where it refuses."""
+    from protocols.secure_comparison_amd import DotLayout, MulLayout, OnehotLayout
+
+    if isinstance(c, K.MulCase):
+        return MulLayout(c.kappa, c.wx, c.wy, c.signed, c.nbits)
+    if isinstance(c, K.DotCase):
+        return DotLayout(c.kappa, c.wx, c.wy, c.k, c.signed, c.square, c.nbits)
+    return OnehotLayout(c.kappa, c.ib, c.k, c.m, c.nbits)
+
+
+def _reached(layouts, conditions_of, promised):
+    reached = {}
+    for c in layouts:
+        n = K.family_modulus(c.nbits)
+        assert n & 1 and n.bit_length() == c.nbits
+        for name in conditions_of(c):
+            reached.setdefault(name, []).append(c)
+    assert set(reached) == set(promised) and len(set(promised)) == len(promised), set(reached) ^ set(promised)
+    return reached
+
+
+def test_multiplication_layouts_reach_every_named_condition():
+    import _mult_model as mm
+
+    reached = _reached(K.MUL_LAYOUTS, K.mul_conditions, K.MUL_CONDITIONS)
+    for c in K.MUL_LAYOUTS:
+        s, offs, fbits, end = K.mul_layout(c.kappa, c.wx, c.wy, c.nbits)
+        lay = _package_layout(c)
+        assert (lay.s, lay.offsets, lay.fbits) == (s, offs, fbits) and offs[-1] + fbits[-1] == end
+        assert mm.layout(c.kappa, c.wx, list(c.wy), c.nbits) == (s, offs, fbits, end, max([s] + fbits))
+        # the launch parameters are ones row_words accepts: the draws fit their rows, r_b rows no wider than N, e rows hold the exponents
+        nw = K.words_of(c.nbits)
+        assert 1 <= c.aw <= K.MUL_FIELD_WORDS and 1 <= c.bw <= min(nw, K.MUL_FIELD_WORDS) and c.ew >= K.mul_ew_min(c)
+        assert all(ra < 1 << (32 * c.aw) and all(rb < 1 << (32 * c.bw) for rb in rbs) for ra, rbs in K.mul_draws(c))
+    # one bit more does not fit where the table says the layout is the largest for its N
+    assert len(reached["end in the top word of N (the largest)"]) == 2
+    for c in reached["end in the top word of N (the largest)"]:
+        wider = c._replace(wy=c.wy[:-1] + (c.wy[-1] + 1,))
+        with pytest.raises(ValueError):
+            K.mul_layout(wider.kappa, wider.wx, wider.wy, wider.nbits)
+        with pytest.raises(ValueError):
+            _package_layout(wider)
+    assert any(c.wy[-1] < K.MUL_MAX_WIDTH for c in reached["end in the top word of N (the largest)"])      # refused by the fit, not the range
+    assert K.MUL_LAYOUTS[0] == min(K.MUL_LAYOUTS, key=lambda c: c.nbits)                                    # the batches run on the smallest
+
+
+def test_multiplication_references_agree_with_the_model_and_themselves(monkeypatch):
+    import types
+
+    import _mult_model as mm
+
+    monkeypatch.setattr(mm, "dec", lambda sk, c: c)                     # the model's key holder, fed plaintexts
+    for c in K.MUL_LAYOUTS:
+        n, nw = K.family_modulus(c.nbits), K.words_of(c.nbits)
+        sk = types.SimpleNamespace(n=n, n2=n * n)
+        s, offs, fbits, end = K.mul_layout(c.kappa, c.wx, c.wy, c.nbits)
+        mask = (1 << (32 * nw)) - 1
+        draws = K.mul_draws(c)
+        abits = min(c.wx + c.kappa, 32 * c.aw)
+        assert {ra for ra, _ in draws} >= {0, 1, (1 << abits) - 1}
+        assert any(ra == (1 << abits) - 1 and all(rb == (1 << min(w + c.kappa, 32 * c.bw)) - 1 for rb, w in zip(rbs, c.wy)) for ra, rbs in draws)
+        prep = K.expected_mul_prep(c, draws)
+        for i, (ra, rbs) in enumerate(draws):
+            e_y, e_xs, rabs = mm.plain(c.kappa, c.wx, list(c.wy), c.signed, ra, rbs)
+            assert [plane[i] for plane in prep["e"]] == e_xs + [e_y]
+            assert [prep["rab"][j][i] for j in range(len(c.wy))] == [v & mask for v in rabs]
+            assert prep["R"][i] == e_y + sum(e_x << o for e_x, o in zip(e_xs, offs)) < min(n, 1 << end)
+            assert all(v < 1 << (32 * c.ew) for v in e_xs + [e_y])
+        # R from the prep reference, split by the split reference, returns the products
+        split = K.expected_mul_split(c, prep["R"])
+        assert split["bad"] == 0 and split["prod"] == prep["rab"]
+        ps = K.mul_p_rows(c)
+        assert ps[0].bit_length() == end and all(p < n and p >> end == 0 for p in ps)
+        ref = K.expected_mul_split(c, ps)
+        for i, p in enumerate(ps):
+            _, prods, bad = mm.mult(sk, c.kappa, c.wx, list(c.wy), p, [1] * len(c.wy))
+            assert not bad and [ref["prod"][j][i] for j in range(len(c.wy))] == [v & mask for v in prods]
+        assert ref["bad"] == 0
+        if len(c.wy) == K.SEL_MAX_FIELDS and s == 318:                  # ten products of 0xffffffff^2 in one column of mul_words
+            assert ps[0] == (1 << end) - 1 and ref["prod"][0][0] == ((1 << 318) - 1) ** 2 & mask
+        for name, bit in K.bad_bits(end, nw).items():
+            flagged = K.plant([ps], 0, 3, bit)[0]
+            assert flagged[3] >> end == 1 << (bit - end) and flagged[:3] + flagged[4:] == ps[:3] + ps[4:], name
+            assert K.expected_mul_split(c, flagged)["bad"] == 1 and mm.mult(sk, c.kappa, c.wx, list(c.wy), flagged[3], [1] * len(c.wy))[2]
+            assert K.first_over([flagged], [end]) == (3, 0, bit)
+
+
+def test_inner_product_layouts_reach_every_named_condition():
+    import _dot_model as dm
+
+    reached = _reached(K.DOT_LAYOUTS, K.dot_conditions, K.DOT_CONDITIONS)
+    for c in K.DOT_LAYOUTS:
+        sa, sb, pb, g, M_, ebits = K.dot_of(c)
+        lay = _package_layout(c)
+        assert (lay.sa, lay.sb, lay.pb, lay.g, lay.M, lay.ebits) == (sa, sb, pb, g, M_, ebits)
+        assert dm.layout(c.kappa, c.wx, c.wy, c.square, c.k, c.nbits) == (sa, sb, pb, g, M_, ebits)
+        assert K.dot_ends(c) == [len(dm.members(m, c.k, M_)) * pb for m in range(M_)] and max(K.dot_ends(c)) <= c.nbits - 2
+        assert 1 <= c.aw <= K.MUL_FIELD_WORDS and (c.square or 1 <= c.bw <= K.MUL_FIELD_WORDS) and 32 * c.ew >= ebits
+    (c,) = reached["k = DOT_MAX_K, sa = sb = 318, g = 1"]
+    assert (c.nbits, K.dot_of(c)[4]) == (1024, 1024)
+    (c,) = reached["k = DOT_MAX_K, sa = sb = 318, g = 3, partial last position"]
+    assert (c.nbits, K.dot_of(c)[4]) == (2048, 342) and sorted(set(K.dot_ends(c))) == [2 * 636, 3 * 636] and K.dot_bad_messages(c) == [0, 171, 341]
+    for c in reached["nw below DOT_ACC_WORDS, the largest k that fits"]:
+        with pytest.raises(ValueError):
+            _package_layout(c._replace(k=c.k + 1))
+    assert K.DOT_LAYOUTS[0] == min(K.DOT_LAYOUTS, key=lambda c: (c.nbits, c.k))
+    assert K.DOT_ACC_WORDS == 21 and {K.words_of(c.nbits) for c in K.DOT_LAYOUTS} >= {2, 13, 22, 96}
+
+
+def test_inner_product_references_agree_with_the_model_and_themselves(monkeypatch):
+    import types
+
+    import _dot_model as dm
+
+    monkeypatch.setattr(dm, "dec", lambda sk, c: c)
+    for c in K.DOT_LAYOUTS:
+        n = K.family_modulus(c.nbits)
+        sk = types.SimpleNamespace(n=n, n2=n * n)
+        sa, sb, pb, g, M_, ebits = K.dot_of(c)
+        ends = K.dot_ends(c)
+        draws = K.dot_draws(c)
+        assert len(draws) == (K.DOT_WIDE_ROWS if c.k == K.DOT_MAX_K else 7)
+        assert all(v < 1 << (32 * c.aw) for r_as, _ in draws for v in r_as) and all(v < 1 << (32 * c.bw) for _, r_bs in draws for v in r_bs or [])
+        prep = K.expected_dot_prep(c, draws)
+        for i, (r_as, r_bs) in enumerate(draws):
+            e, R, S = dm.plain(c.kappa, c.wx, c.wy, c.signed, c.square, c.k, c.nbits, r_as, r_bs)
+            assert [plane[i] for plane in prep["e"]] == e and [row[i] for row in prep["R"]] == R and prep["S"][i] == S < n
+            assert all(v < 1 << (32 * c.ew) for v in e) and all(r < min(n, 1 << end) for r, end in zip(R, ends))
+        # the packed masks, split, give the sum the prep reference states
+        assert K.expected_dot_split(c, prep["R"]) == {"D": prep["S"], "bad": 0}
+        P = K.dot_p_rows(c)
+        count = len(P[0])
+        assert all(P[m][0].bit_length() == ends[m] for m in range(M_)) and all(p < n and p >> ends[m] == 0 for m in range(M_) for p in P[m])
+        ref = K.expected_dot_split(c, P)
+        for i in range(count):
+            _, D, bad = dm.answer(sk, c.kappa, c.wx, c.wy, c.square, c.k, [P[m][i] for m in range(M_)], 1)
+            assert not bad and ref["D"][i] == D < n
+        assert ref["bad"] == 0
+        if c.k == K.DOT_MAX_K:                               # the accumulator's last words: bits at and above 640
+            assert prep["S"][0] >> 640 and ref["D"][0] >> 640 and ref["D"][0] == c.k * ((1 << 318) - 1) ** 2
+        if c.square and sa % 32 == 31:                       # bit 31 of every whole word of a: the doubling carries across every word
+            a = prep["e"][0][4] // 2
+            assert all(a >> (32 * w + 31) & 1 for w in range(sa // 32)) and sa // 32 >= 2
+        for mm in K.dot_bad_messages(c):
+            for name, bit in K.bad_bits(ends[mm], K.words_of(c.nbits)).items():
+                i = count - 1
+                flagged = K.plant(P, mm, i, bit)
+                assert flagged[mm][i] >> ends[mm] == 1 << (bit - ends[mm]), name
+                assert [r for m, r in enumerate(flagged) if m != mm] == [r for m, r in enumerate(P) if m != mm]
+                assert K.expected_dot_split(c, flagged)["bad"] == 1 and K.first_over(flagged, ends) == (i, mm, bit)
+                assert dm.answer(sk, c.kappa, c.wx, c.wy, c.square, c.k, [flagged[m][i] for m in range(M_)], 1)[2]
+
+
+def test_onehot_layouts_reach_every_named_condition():
+    import _onehot_model as om
+
+    _reached(K.ONEHOT_LAYOUTS, K.onehot_conditions, K.ONEHOT_CONDITIONS)
+    for c in K.ONEHOT_LAYOUTS:
+        f, g, M_, rw = K.onehot_of(c)
+        lay = _package_layout(c)
+        assert (lay.f, lay.g, lay.M, lay.rw) == (f, g, M_, rw) == om.layout(c.kappa, c.ib, c.k, c.m, c.nbits)
+        assert K.onehot_ends(c) == [len(om.members(mm, c.m, g)) * f for mm in range(M_)] and max(K.onehot_ends(c)) <= c.nbits - 2
+    assert {c.k for c in K.ONEHOT_LAYOUTS} == {1, 2, 3, 1023, 1024} and {c.rw for c in K.ONEHOT_LAYOUTS} == {1, 2, 3}
+    small = K.ONEHOT_LAYOUTS[0]
+    assert small == min(K.ONEHOT_LAYOUTS, key=lambda c: c.nbits) and (small.k, small.m, K.onehot_of(small)[2]) == (1, 1, 1)
+    # the rotation: every word count, every value of rot on some row, the negative ones where the two readings differ
+    assert {w for w, _, _, _ in K.ROTATE_CASES} == set(K.ROTATE_WORDS) and {m * k * n for _, k, m, n in K.ROTATE_CASES} >= set(K.WAVE_ROWS)
+    seen = set()
+    for words, k, m, count in K.ROTATE_CASES:
+        rot = K.rotate_rot(k, m, count)
+        assert all(-(1 << 31) <= r < 1 << 31 for row in rot for r in row)
+        seen |= {K.rotate_values(k).index(r) for row in rot for r in row}
+        if any(r < 0 and (1 << 32) % k for row in rot for r in row):
+            seen.add("negative, k does not divide 2^32")
+    assert seen == set(range(8)) | {"negative, k does not divide 2^32"}
+    assert K.rotate_source(-1, 7, 0) == 3 != -1 % 7 and K.rotate_source(-8, 7, 2) == (2 + ((1 << 32) - 8) % 7) % 7      # the unsigned reading
+    assert K.rotate_source(-1, 1024, 5) == (5 - 1) % 1024                                                          # k divides 2^32
+
+
+def test_onehot_references_agree_with_the_model_and_themselves():
+    import _onehot_model as om
+
+    for c in K.ONEHOT_LAYOUTS:
+        n, nw = K.family_modulus(c.nbits), K.words_of(c.nbits)
+        f, g, M_, rw = K.onehot_of(c)
+        ends = K.onehot_ends(c)
+        draws = K.onehot_draws(c)
+        assert len(draws) == c.count and draws[0] == [(1 << (c.ib + c.kappa)) - 1] * c.m and all(r < 1 << (32 * c.rw) for rs in draws for r in rs)
+        prep = K.expected_onehot_prep(c, draws)
+        for b, rs in enumerate(draws):
+            R, rot = om.plain(c.kappa, c.ib, c.k, c.m, c.nbits, rs)
+            assert [row[b] for row in prep["R"]] == R and [row[b] for row in prep["rot"]] == rot
+            assert all(r < min(n, 1 << end) for r, end in zip(R, ends))
+        P = K.onehot_p_rows(c)
+        assert all(P[mm][0].bit_length() == ends[mm] for mm in range(M_)) and all(p < n and p >> ends[mm] == 0 for mm in range(M_) for p in P[mm])
+        ref = K.expected_onehot_split(c, P)
+        assert ref["bad"] == 0
+        for b in range(c.count):
+            _, hot, bad = om.split(c.kappa, c.ib, c.k, c.m, c.nbits, [P[mm][b] for mm in range(M_)])
+            assert not bad and [[ref["prod"][q][t][b] for t in range(c.k)] for q in range(c.m)] == [[int(t == j) for t in range(c.k)] for j in hot]
+        for mm in sorted({0, M_ - 1}):
+            bits = K.onehot_bad_bits(c, mm)
+            if nw > 64:
+                assert {"end", "last word"} <= set(bits) and ("word 63" in bits) == (ends[mm] <= 32 * 63 + 31) and \
+                    ("word 64" in bits) == (ends[mm] <= 32 * 64)
+            for name, bit in bits.items():
+                flagged = K.plant(P, mm, c.count - 1, bit)
+                assert flagged[mm][-1] >> ends[mm] == 1 << (bit - ends[mm]), name
+                assert K.expected_onehot_split(c, flagged)["bad"] == 1 and K.first_over(flagged, ends) == (c.count - 1, mm, bit)
+                assert om.split(c.kappa, c.ib, c.k, c.m, c.nbits, [flagged[x][-1] for x in range(M_)])[2]
+        assert any("word 63" in K.onehot_bad_bits(c, mm) for c in K.ONEHOT_LAYOUTS for mm in range(K.onehot_of(c)[2]))
+    for words, k, m, count in K.ROTATE_CASES:
+        e, rot = K.rotate_input(words, k, m, count), K.rotate_rot(k, m, count)
+        want = K.expected_rotate(k, m, count, e, rot)
+        assert len({v for q in e for t in q for v in t}) == m * k * count and all(v >> (32 * words - 1) == 1 for q in e for t in q for v in t)
+        for b in range(count):
+            if all(rot[q][b] >= 0 for q in range(m)):            # where rot is a residue's representative the model's rotation is the same
+                assert om.rotate([[e[q][t][b] for t in range(k)] for q in range(m)], [rot[q][b] for q in range(m)], k, m) == \
+                    [[want[q][t][b] for t in range(k)] for q in range(m)]
