@@ -88,7 +88,12 @@ int sc_memcpy_d2h(sc_ctx* ctx, void* hptr, const void* dptr, size_t bytes);
 /* Paillier key: the public modulus N and optionally the secret primes p, q (key holder) -- what `Paillier.from_security_parameter`
  * produces at SC/keyholder.py:155-158 and what the initiator receives as the public scheme (SC/initiator.py:177-203).  Every derived
  * modulus (N, N^2, p, q, p^2, q^2), exponent (N, lambda, p - 1, q - 1, q mod p - 1, ..), CRT constant and the pair contexts are
- * registered once; flags: SC_KEY_NO_CRT / SC_KEY_NO_PAIRS keep the literal single-modulus forms (tests, A/B). */
+ * registered once; flags: SC_KEY_NO_CRT / SC_KEY_NO_PAIRS keep the literal single-modulus forms (tests, A/B).
+ * Word counts: N^2 is always registered in 2 * nwords words, also where it is shorter (a 1025-bit N has 33 words, its 2049-bit N^2
+ * 66, the top one zero in every ciphertext), and the kernel configuration follows the stored words, not the bit length alone: that
+ * N^2 runs on (4,27), not on the (4,18) a 2049-bit modulus of 65 words would take.  p and q are both registered in
+ * hw = nwords(max(bits(p), bits(q))) words and p^2, q^2 in 2 * hw: the shorter prime is padded, so the two CRT halves of a key always
+ * run on the same kernel instances, whatever the difference in length. */
 int sc_paillier_key_create(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, const uint32_t* p_hptr /* nullable */,
                            const uint32_t* q_hptr /* nullable */, int pwords, int flags, int* out_key);
 /* the primitive handles behind a key (for callers that mix scheme-level calls and the primitives of sc_amd_dev.h) */

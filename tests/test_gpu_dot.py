@@ -157,7 +157,7 @@ def _split_raw(engine, sk, ap, lay, P_plain, count):
     return D, int(bad.item())
 
 
-def _steps(engine, sk, ap, bp, kappa, wx, wy, signed, square, k, seed, bits, count=COUNT):
+def _steps(engine, sk, ap, bp, kappa, wx, wy, signed, square, k, seed, bits, count=COUNT, rows=None):
     from protocols.secure_comparison_amd.dotproduct import dot_finish, dot_pack, dot_sum
 
     n, nw = sk.n, ap.mod_n.nwords
@@ -168,7 +168,7 @@ def _steps(engine, sk, ap, bp, kappa, wx, wy, signed, square, k, seed, bits, cou
     x_c, x_t = _enc_planes(engine, sk, ap, rng, xs)
     y_c, y_t = (None, None) if square else _enc_planes(engine, sk, ap, rng, ys)
     md = _upload_draws(engine, ap, lay, draws)
-    rows = _model_rows(bits, count)
+    rows = _model_rows(bits, count) if rows is None else rows          # (rows: the rows the model follows, when the caller says)
     xv = lambda i: [x_c[j][i] for j in range(k)]  # noqa: E731
     yv = lambda i: None if square else [y_c[j][i] for j in range(k)]  # noqa: E731
 

@@ -138,7 +138,7 @@ def _split_raw(engine, sk, ap, lay, P_plain, count):
     return prod, int(bad.item())
 
 
-def _steps(engine, sk, ap, bp, kappa, ib, k, m, seed, bits, count=COUNT):
+def _steps(engine, sk, ap, bp, kappa, ib, k, m, seed, bits, count=COUNT, rows=None):
     from protocols.secure_comparison_amd.lookup import draw_onehot, onehot_answer, onehot_finish, onehot_pack
 
     n, nw = sk.n, ap.mod_n.nwords
@@ -152,7 +152,7 @@ def _steps(engine, sk, ap, bp, kappa, ib, k, m, seed, bits, count=COUNT):
     rho_e = draw_onehot(count, lay, ap, alice=False).rho_e
     rho_ints = _rows(engine, rho_e)
     md = _upload_draws(engine, ap, lay, draws, rho_e)
-    rows = _model_rows(bits, count)
+    rows = _model_rows(bits, count) if rows is None else rows          # (rows: the rows the model follows, when the caller says)
     iv = lambda b: [i_c[q][b] for q in range(m)]  # noqa: E731
 
     # the plaintext arrays, every row: sc_onehot_prep's R and rot against the model

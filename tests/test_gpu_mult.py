@@ -116,7 +116,7 @@ def _model_rows(bits, count):
     return [0, 7, 14] + list(range(count - 2, count))
 
 
-def _steps(engine, sk, ap, bp, kappa, wx, wy, signed, seed, bits, count=COUNT):
+def _steps(engine, sk, ap, bp, kappa, wx, wy, signed, seed, bits, count=COUNT, rows=None):
     from protocols.secure_comparison_amd.multiplication import MulLayout, mul_finish, mul_mult, mul_pack
 
     n, nf = sk.n, len(wy)
@@ -125,7 +125,7 @@ def _steps(engine, sk, ap, bp, kappa, wx, wy, signed, seed, bits, count=COUNT):
     xs, ys, draws = _case(rng, sk, kappa, wx, wy, signed, count)
     x_c, y_c, x_t, y_t = _encrypt(engine, sk, ap, rng, xs, ys)
     md = _upload_draws(engine, ap, kappa, wx, wy, draws)
-    rows = _model_rows(bits, count)
+    rows = _model_rows(bits, count) if rows is None else rows          # (rows: the rows the model follows, when the caller says)
     ycol = lambda i: [y_c[j][i] for j in range(nf)]  # noqa: E731
 
     P, (e, rab) = mul_pack(lay, x_t, y_t, md, ap)
