@@ -3,7 +3,8 @@
 // units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
 // sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip, sc_launch_scan.hip and
 // sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
-// the HIP-free plans and checks of the two axis entries, and sc_pack_plan.h, the HIP-free field lists of the four pack entries) holds no device code, so a change of host logic or policy rebuilds in seconds.
+// the HIP-free plans and checks of the two axis entries, and sc_pack_plan.h, the HIP-free field lists of the four pack entries) holds no device code, so a change of host logic rebuilds in seconds.
+// sc_route.h, included here, is the HIP-free policy that picks the kernel instance of a launch: configurations, fit rule, twins.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -25,6 +26,7 @@
 
 #include "../../../include/sc_amd_dev.h"
 #include "sc_vm.h"
+#include "sc_route.h"
 
 #ifndef SC_INV_TOP
 #define SC_INV_TOP 2048
@@ -117,35 +119,6 @@ std::vector<uint32_t> to_limbs(const Big& x, int S, int W) {
   return out;
 }
 
-struct Config { int G, L, W; bool primary; };   // primary: eligible as a modulus's own configuration (sc_mod_create)
-// ordered by capacity W*G*L; sc_mod_create takes the first one that fits.  A 28-bit-limb L = 37 family ((2,37), (4,37)) was
-// built and measured in round 1: it needs > 256 registers (one wave per SIMD plus AGPR copies) and came out 2-3 % slower
-// than (4,18) / (8,18), so it is not compiled in; the limb width stays a template parameter for such experiments.
-const Config kConfigs[] = {{1, 18, 29, true}, {2, 18, 29, true}, {2, 27, 29, true}, {4, 14, 29, true}, {4, 18, 29, true}, {4, 27, 29, true},
-                           {8, 14, 29, true}, {8, 18, 29, true}, {8, 27, 29, true}, {16, 14, 29, true}, {16, 18, 29, true}};
-// The one-lane configuration for moduli up to 1028 bits (the primes of 2048-bit Paillier / DGK keys): (1, 37) with 28-bit limbs.
-// A number lives in ONE lane, so the per-limb-step bookkeeping is paid once per number instead of once per lane of a group, the
-// operand of a squaring never leaves the registers and the modulus sits in scalar registers: 1.15 - 1.25x the (2, 18) rate
-// per number.  It needs 64 numbers per wave, i.e. large batches, and is therefore never a modulus's own configuration: the
-// shared-exponent entry points switch to an internal twin context of the same modulus when the batch fills the chip
-// (onelane_for, sc_ctx_set_onelane_mode).
-const Config kOneLane = {1, 37, 28, false};
-// configurations with a pair kernel (k_pvm): every L = 18 one, and (4,14) / (8,14) for the 1536 / 3072-bit sizes whose direct
-// configuration is L = 27 (the pair arithmetic needs the L <= 18 column bound)
-// (the one-lane (1, 37, 28) configuration has no pair kernel: measured on the MI355X its pair squarings run 3 % faster than the
-// (2, 18) ones but its pair products -- three passes over a single LDS staging area, the second area would cost the eighth wave
-// of the CU -- 2.6x a squaring instead of 1.4x, a net loss of 12 % on x^p mod p^2; the one-lane form is used where it wins:
-// the single-modulus exponentiations)
-// (8,5) / (16,5): the SMALL-BATCH pair configurations of 1024 / 2048-bit moduli (kLatencyPair below)
-inline bool pair_capable(int G, int L, int W) { return W == 29 && (L == 18 || (L == 14 && (G == 4 || G == 8)) || (L == 5 && (G == 4 || G == 8 || G == 16))); }
-// Small batches of pair exponentiations (Alice's rho^N mod N^2, the key holder's c^(p-1) mod p^2 at B = 4096) are one dependent
-// chain of ~2400 pair squarings per item, and a wave's time per squaring is its own instruction count: S limb steps of
-// (L + L/2) multiply-adds + ~7 bookkeeping instructions each, whatever the number of lanes.  When even the (2G, 9) form
-// leaves half of the SIMDs without a wave, 4x the lanes with 5 limbs each -- (16,5) for 2048-bit, (8,5) for 1024-bit moduli,
-// S = 80 / 40 limbs -- shorten every limb step from ~22 to ~15 instructions at a multiply-add density (45 %) that would be
-// wasteful on a full chip but costs nothing on an empty one.  A twin context of the same modulus, like the other twins.
-const Config kLatencyPair16 = {16, 5, 29, false}, kLatencyPair8 = {8, 5, 29, false}, kLatencyPair4 = {4, 5, 29, false};   // (4,5): 512-bit primes of 1024-bit keys
-
 struct Mod {
   int G = 0, L = 0, W = 29, S = 0, nwords = 0, nbits = 0;
   Big n;
@@ -208,10 +181,7 @@ struct sc_ctx {
   int chip_share = 1;                                       // sc_ctx_set_chip_share: contexts working on this GPU at the same time
   void* comm = nullptr;                                     // RCCL communicator of this rank (sc_comm_init), one context per GPU
   int comm_rank = 0, comm_nranks = 0;
-  std::map<int, int> onelane_twins;                         // mod -> context of the same modulus in the one-lane configuration
-  std::map<int, int> pair_twins;                            // mod -> context of the same modulus in a pair-capable configuration
-  std::map<int, int> neg1_twins;                            // (4,18) mod n -> context of the multiple M = c n = -1 (mod 2^29)
-  std::map<int, int> latency_pair_twins;                    // mod -> context of the same modulus in the (16,5) / (8,5) small-batch pair configuration
+  std::map<std::pair<int, int>, int> twins;                 // (twin kind, mod) -> its twin context, -1 where it has none (sc_lib.hip: twin_of)
   std::map<int, uint32_t*> pair_consts;                     // mod -> 4 limb arrays: pair(R^2), pair(B R) for the pair arithmetic
   uint32_t* d_one = nullptr;                                // the word 1 (a broadcast operand: the table entry x^0 of sc_modexp_var_sq)
   RngKey rng_key;                                           // ChaCha20 key of the context's generator (sc_rng_seed)

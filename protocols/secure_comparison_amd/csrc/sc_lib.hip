@@ -414,17 +414,9 @@ int cached_prog(sc_ctx* ctx, const std::string& key, int mod, F&& build, const P
   return SC_OK;
 }
 
-// Small batches: an L = 18 configuration with count * G lanes fills only part of the chip, and the run time is the latency of
-// one wave's chain of products.  The same limb arrays (S = G L limbs, identical layout in memory) can be worked on by twice
-// the lanes with half the limbs each -- (2G, 9) -- which doubles the waves and shortens the chain by 1.8x; the multiply-add
-// density drops from 88 % to 78 % of the instruction stream, so this is used only while the L = 18 launch would leave at
-// least half of the SIMDs without a wave.
-inline bool use_latency_config(const sc_ctx* ctx, const Mod& m, uint64_t count) {
-  if (ctx->latency_mode == 0 || m.L != 18 || m.W != 29 || m.G > 8) return false;
-  if (ctx->latency_mode == 2) return true;
-  const uint64_t waves = (count + (64 / m.G) - 1) / (64 / m.G);
-  return waves <= (uint64_t)ctx->num_cu * 2;
-}
+// what the instance policy (sc_route.h) is asked with: the switches of the context, and a modulus as it sees one
+inline Policy policy_of(const sc_ctx* ctx) { return {ctx->latency_mode, ctx->onelane_mode, ctx->chip_share, ctx->num_cu}; }
+inline Instance shape_of(const Mod& m) { return {m.G, m.L, m.W, m.n0inv == 1}; }
 
 int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uint64_t count, const uint32_t* fbt_rows = nullptr) {
   if (count == 0) return SC_OK;
@@ -445,26 +437,16 @@ int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uin
   for (int i = 0; i < next; i++) a.ext[i] = exts[i];
   // multiply-adds issued per item: a product or a reduction pass is S^2 (S/G limb steps x L per lane x G lanes); the a*a part
   // of a squaring is L(L+1)/2 per (lane, block) pair, G^2 pairs
-  const bool lat = use_latency_config(ctx, m, count);
-  const int G = lat ? 2 * m.G : m.G, L = lat ? 9 : m.L;
+  const Instance k = vm_instance(shape_of(m), policy_of(ctx), count);
   ctx->mac_counter += (double)count * ((p.muls_per_item * 2.0 + p.redcs_per_item + p.sqrs_per_item) * (double)m.S * m.S +
-                                        p.sqrs_per_item * (double)G * G * L * (L + 1) / 2.0);
-  // a (4,18) modulus = -1 (mod 2^29) -- in practice the multiple M = c n of neg1_twin -- runs the instance without the quotient multiply
-  const bool neg1 = G == 4 && L == 18 && m.W == 29 && m.n0inv == 1;
-  int rc = launch_vm_part0(ctx, G, L, m.W, neg1, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_vm_part1(ctx, G, L, m.W, neg1, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_vm_part2(ctx, G, L, m.W, neg1, a);
-  if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no kernel configuration for G=%d L=%d", G, L);
+                                        p.sqrs_per_item * (double)k.G * k.G * k.L * (k.L + 1) / 2.0);
+  int rc = launch_vm_part0(ctx, k.G, k.L, k.W, k.neg1, a);
+  if (rc == SC_ERR_UNSUPPORTED) rc = launch_vm_part1(ctx, k.G, k.L, k.W, k.neg1, a);
+  if (rc == SC_ERR_UNSUPPORTED) rc = launch_vm_part2(ctx, k.G, k.L, k.W, k.neg1, a);
+  if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no kernel configuration for G=%d L=%d", k.G, k.L);
   return rc;
 }
 
-// which instance of the pair kernel a launch of `count` items of modulus m takes
-void pvm_instance(const sc_ctx* ctx, const Mod& m, uint64_t count, int* G, int* L, bool* neg1) {
-  *G = m.G; *L = m.L;
-  if (use_latency_config(ctx, m, count) && (m.G == 1 || m.G == 2 || m.G == 4)) { *G = 2 * m.G; *L = 9; }   // (2,9): the 512-bit primes of 1024-bit keys (BASELINE configs[0])
-  // n = -1 (mod 2^29): the instances without the quotient multiply exist for (4,18), (4,14), (8,14)
-  *neg1 = m.n0inv == 1 && ((*G == 4 && *L == 18) || (*L == 14 && (*G == 4 || *G == 8)));
-}
 // resident waves per CU of that instance (the runtime's occupancy answer, not a compiled-in assumption)
 int pvm_occupancy(sc_ctx* ctx, int G, int L, bool neg1) {
   int occ = pvm_occupancy_part0(ctx, G, L, neg1);
@@ -492,13 +474,12 @@ int run_pvm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, ui
     if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no per-row-exponent pair kernel for G=%d L=%d", m.G, m.L);
     return rc;
   }
-  int G, L; bool neg1;
-  pvm_instance(ctx, m, count, &G, &L, &neg1);
-  const bool stamp = neg1 && G == 4 && L == 18 && ctx->stamps != nullptr;     // the stamping twin of (4,18,neg1) is sc_clock_probe's diagnostic launch
-  int rc = launch_pvm_part0(ctx, G, L, neg1, stamp, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_part1(ctx, G, L, neg1, stamp, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_part2(ctx, G, L, neg1, stamp, a);
-  if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no pair kernel for G=%d L=%d", G, L);
+  const Instance k = pvm_instance(shape_of(m), policy_of(ctx), count);
+  const bool stamp = k.neg1 && k.G == 4 && k.L == 18 && ctx->stamps != nullptr;     // the stamping twin of (4,18,neg1) is sc_clock_probe's diagnostic launch
+  int rc = launch_pvm_part0(ctx, k.G, k.L, k.neg1, stamp, a);
+  if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_part1(ctx, k.G, k.L, k.neg1, stamp, a);
+  if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_part2(ctx, k.G, k.L, k.neg1, stamp, a);
+  if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no pair kernel for G=%d L=%d", k.G, k.L);
   return rc;
 }
 
@@ -677,19 +658,8 @@ static int create_mod(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, bool for_
   m.nwords = nwords;
   m.nbits = big_bits(m.n);
   if (m.nbits < 2 || !(m.n[0] & 1)) return fail(ctx, SC_ERR_ARG, "sc_mod_create: modulus must be odd and > 1");
-  auto fits = [&](const Config& c, bool need_words) {
-    const int cap = c.W * c.G * c.L;
-    return cap >= m.nbits + 8 && (!need_words || cap >= 32 * nwords);
-  };
-  if (forced) {
-    if (fits(*forced, false)) { m.G = forced->G; m.L = forced->L; m.W = forced->W; }
-  } else {
-    for (int pass = 0; pass < 2 && !m.G; pass++)
-      for (const Config& c : kConfigs) {
-        if (!c.primary || (for_pairs && !pair_capable(c.G, c.L, c.W))) continue;
-        if (fits(c, pass == 0)) { m.G = c.G; m.L = c.L; m.W = c.W; break; }
-      }
-  }
+  const Config* cfg = forced ? forced_fit(*forced, m.nbits) : first_fit(m.nbits, nwords, for_pairs);
+  if (cfg) { m.G = cfg->G; m.L = cfg->L; m.W = cfg->W; }
   if (!m.G) return fail(ctx, SC_ERR_UNSUPPORTED, "sc_mod_create: %d-bit modulus exceeds the largest configuration", m.nbits);
   m.S = m.G * m.L;
   const int W = m.W;
@@ -1590,42 +1560,42 @@ int sc_crt_combine(sc_ctx* ctx, int mod_p, int mod_full, int cst_k, int cst_negk
   return run_vm(ctx, mod_full, *p2, ex, 3, count);
 }
 
+// ---- twin contexts ---------------------------------------------------------------------------------------------------------------
+// A twin is a second registration of a modulus (or of its multiple M = c n) in another configuration, made on first use and kept
+// for the life of the context.  Which twin a call takes is decided in sc_route.h; here they are made and remembered.
+enum TwinKind { TWIN_PAIR, TWIN_LATENCY_PAIR, TWIN_NEG1, TWIN_ONELANE };
+
+// The twin of `mod` of this kind: the remembered one, else what `make` registers for a COPY of the modulus -- create_mod appends to
+// ctx->mods, so no reference into that table may be held across it, here or in `make` -- remembered too, a failure as -1.
+static int twin_of(sc_ctx* ctx, TwinKind kind, int mod, const std::function<int(const Mod&)>& make) {
+  const auto key = std::make_pair((int)kind, mod);
+  auto it = ctx->twins.find(key);
+  if (it != ctx->twins.end()) return it->second;
+  const Mod m = ctx->mods[mod];
+  const int twin = make(m);
+  ctx->twins[key] = twin;
+  return twin;
+}
+// ... of the same modulus in the first pair-capable configuration that fits (for_pairs) or in `forced`
+static int same_modulus_twin(sc_ctx* ctx, TwinKind kind, int mod, bool for_pairs, const Config* forced) {
+  return twin_of(ctx, kind, mod, [&](const Mod& m) {
+    int twin = -1;
+    return create_mod(ctx, m.n.data(), (int)m.n.size(), for_pairs, &twin, forced) == SC_OK ? twin : -1;
+  });
+}
+
 // the context the pair kernel runs in for modulus `mod`: itself when its configuration has a pair kernel, otherwise a twin
 // context of the same modulus in a pair-capable configuration (created on first use); -1 if no configuration fits
 static int pair_twin(sc_ctx* ctx, int mod) {
-  {
-    const Mod& m = ctx->mods[mod];
-    if (pair_capable(m.G, m.L, m.W)) return mod;
-  }
-  auto it = ctx->pair_twins.find(mod);
-  if (it != ctx->pair_twins.end()) return it->second;
-  const Big n = ctx->mods[mod].n;
-  int twin = -1;
-  if (create_mod(ctx, n.data(), (int)n.size(), true, &twin) != SC_OK) twin = -1;
-  ctx->pair_twins[mod] = twin;
-  return twin;
+  const Mod& m = ctx->mods[mod];
+  return pair_capable(m.G, m.L, m.W) ? mod : same_modulus_twin(ctx, TWIN_PAIR, mod, true, nullptr);
 }
 
-// The small-batch pair twin of `mod` ((16,5) for a (4,18) modulus, (8,5) for a (2,18) one, (4,5) for a (1,18) one) when this batch should run on it, else
-// -1.  Automatic policy: the (2G, 9) launch would still leave at least half of the SIMDs without a wave.
+// The small-batch pair twin of `mod` when this batch should run on it (latency_pair_config), else -1.
 static int latency_pair_twin(sc_ctx* ctx, int mod, uint64_t count) {
-  if (ctx->latency_mode == 0) return -1;
-  const Config* cfg = nullptr;
-  {
-    const Mod& m = ctx->mods[mod];
-    if (m.W != 29 || m.L != 18 || (m.G != 1 && m.G != 2 && m.G != 4)) return -1;
-    cfg = (m.G == 4) ? &kLatencyPair16 : (m.G == 2 ? &kLatencyPair8 : &kLatencyPair4);
-    const uint64_t per_wave = 64 / (2 * m.G), waves = (count + per_wave - 1) / per_wave;
-    if (ctx->latency_mode == 1 && waves > (uint64_t)ctx->num_cu * 2 / (uint64_t)ctx->chip_share) return -1;
-    if (m.nbits + 8 > cfg->W * cfg->G * cfg->L || 32 * m.nwords > cfg->W * cfg->G * cfg->L) return -1;
-  }
-  auto it = ctx->latency_pair_twins.find(mod);
-  if (it != ctx->latency_pair_twins.end()) return it->second;
-  const Big n = ctx->mods[mod].n;
-  int twin = -1;
-  if (create_mod(ctx, n.data(), (int)n.size(), false, &twin, cfg) != SC_OK) twin = -1;
-  ctx->latency_pair_twins[mod] = twin;
-  return twin;
+  const Mod& m = ctx->mods[mod];
+  const Config* cfg = latency_pair_config(shape_of(m), m.nbits, m.nwords, policy_of(ctx), count);
+  return cfg ? same_modulus_twin(ctx, TWIN_LATENCY_PAIR, mod, false, cfg) : -1;
 }
 
 // The twin of a (4,18) / (4,14) / (8,14) modulus n whose own modulus is the multiple M = c n, c = -n^-1 mod 2^29, so that M = -1
@@ -1635,41 +1605,28 @@ static int latency_pair_twin(sc_ctx* ctx, int mod, uint64_t count) {
 // residues modulo n (n^2): the caller finishes in a context of the original modulus.  -1: no such twin (other configurations,
 // moduli too long, or n already = -1).
 static int neg1_twin(sc_ctx* ctx, int mod) {
-  auto it = ctx->neg1_twins.find(mod);
-  if (it != ctx->neg1_twins.end()) return it->second;
-  int twin = -1;
-  {
-    const Mod m = ctx->mods[mod];
+  return twin_of(ctx, TWIN_NEG1, mod, [&](const Mod& m) {
     static const bool enabled = []{ const char* e = getenv("SC_NEG1"); return !(e && e[0] == '0'); }();      // A/B switch (dev): SC_NEG1=0
-    const bool has_kernel = m.W == 29 && ((m.L == 18 && m.G == 4) || (m.L == 14 && (m.G == 4 || m.G == 8)));   // k_pvm<.., true> instances
-    if (enabled && has_kernel && m.n0inv != 1 && m.nbits + 29 + 8 <= m.W * m.S) {
-      Big c(1, m.n0inv);
-      Big M = big_trimmed_words(big_mul(m.n, c));
-      const Config same = {m.G, m.L, m.W, false};
-      // M must hold whole words below R like every other modulus (sc_mod_create's first pass; onelane_for and latency_pair_twin
-      // ask the same of their twins): a wide operand is read in raw chunks of M's words, and bits of a chunk at or above
-      // 2^(W S) are dropped by the limb conversion -- a 1587-bit modulus on (4,14) gave an M of 51 words for 1624 limb bits
-      if (32 * (int)M.size() > m.W * m.S) twin = -1;
-      else if (create_mod(ctx, M.data(), (int)M.size(), false, &twin, &same) != SC_OK) twin = -1;
-      if (twin >= 0 && ctx->mods[twin].n0inv != 1) twin = -1;     // (cannot happen: M = -1 mod 2^29 by construction)
-      if (twin >= 0) {           // what a single-modulus program needs to leave the context with a residue modulo n (sc_vm.h)
-        uint32_t inv = m.n0inv;                                    // c is odd: c c = 1 (mod 8); Newton doubles the good bits
-        for (int it = 0; it < 5; it++) inv *= 2u - m.n0inv * inv;
-        ctx->mods[twin].small_c = m.n0inv;
-        ctx->mods[twin].small_cinv = inv & ((1u << m.W) - 1);
-      }
-    }
-  }
-  ctx->neg1_twins[mod] = twin;
-  return twin;
+    if (!enabled || !neg1_candidate(shape_of(m), m.nbits)) return -1;
+    const Big M = big_trimmed_words(big_mul(m.n, Big(1, m.n0inv)));
+    const Config same = {m.G, m.L, m.W, false};
+    int twin = -1;
+    if (!fits(same, big_bits(M), (int)M.size(), true) || create_mod(ctx, M.data(), (int)M.size(), false, &twin, &same) != SC_OK) return -1;
+    if (ctx->mods[twin].n0inv != 1) return -1;     // (cannot happen: M = -1 mod 2^29 by construction)
+    // what a single-modulus program needs to leave the context with a residue modulo n (sc_vm.h)
+    uint32_t inv = m.n0inv;                                    // c is odd: c c = 1 (mod 8); Newton doubles the good bits
+    for (int it = 0; it < 5; it++) inv *= 2u - m.n0inv * inv;
+    ctx->mods[twin].small_c = m.n0inv;
+    ctx->mods[twin].small_cinv = inv & ((1u << m.W) - 1);
+    return twin;
+  });
 }
 
 // The same twin for the single-modulus interpreter: only the (4,18) instance k_vm<4,18,29,true> exists, and only programs whose
 // outputs are word stores can use it (modexp_var_impl: the blinding launch of step 4i) -- limb-form outputs would carry residues
 // up to 2M into launches of the original context.
 static int neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count) {
-  const Mod& m = ctx->mods[mod];
-  if (m.W != 29 || m.L != 18 || m.G != 4 || use_latency_config(ctx, m, count)) return -1;
+  if (!neg1_vm_allowed(shape_of(ctx->mods[mod]), policy_of(ctx), count)) return -1;
   const int t = neg1_twin(ctx, mod);
   return (t >= 0 && ctx->mods[t].small_c != 0) ? t : -1;
 }
@@ -1681,8 +1638,7 @@ static int neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count) {
 // device and process, on a fixed 1024-bit odd modulus and a 1024-bit exponent -- the shape of the key holder's first CRT stage; a
 // 256-bit exponent gave other RATIOS (two-lane round 0.53 instead of 0.60 of a one-lane round: the window tables weigh differently)
 // and mis-ranked the forms at half a round.  About 80 ms of launches.  Round 3 had these as constants fitted on one box (0.6 / 0.27 /
-// 0.38 of a one-lane round).
-struct OneLaneCal { bool ok = false; double one_full = 1.0, one_half = 0.5, two_full = 0.6, two_half = 0.27, two_only_half = 0.38; int simds = 0; };
+// 0.38 of a one-lane round): the defaults of OneLaneCal (sc_route.h).
 static std::mutex g_cal_mutex;
 static std::map<int, OneLaneCal> g_cal;           // by device
 
@@ -1770,26 +1726,10 @@ int sc_ctx_policy(sc_ctx* ctx, double* out6) {
 // (two shards of 32768 comparisons: the 98304-number launches run one-lane, +1.5 % on the whole step).
 static int onelane_for(sc_ctx* ctx, int mod, uint64_t count) {
   if (ctx->onelane_mode == 0) return mod;
-  {
-    const Mod& m = ctx->mods[mod];
-    // the residue arrays (and the raw chunks a wide operand is read in) must fit below R = 2^(28 * 37): at most 32 words
-    if (m.W == kOneLane.W || m.nbits + 8 > kOneLane.W * kOneLane.G * kOneLane.L || 32 * m.nwords > kOneLane.W * kOneLane.G * kOneLane.L) return mod;
-  }
-  if (ctx->onelane_mode == 1) {
-    const OneLaneCal c = onelane_cal(ctx);          // (may register moduli: no reference into ctx->mods is held across it)
-    const double share = (double)ctx->chip_share / ((double)ctx->num_cu * 4 * 2 * 64);
-    const double r1 = (double)count * share, r2 = 2.0 * r1;
-    const double f1 = r1 - std::floor(r1), f2 = r2 - std::floor(r2);
-    const double one = c.one_full * std::floor(r1) + (f1 <= 0.0 ? 0.0 : (f1 <= 0.5 ? c.one_half : c.one_full));
-    const double two = c.two_full * std::floor(r2) + (f2 <= 0.0 ? 0.0 : (f2 <= 0.5 ? (r2 < 1.0 ? c.two_only_half : c.two_half) : c.two_full));
-    if (one >= two) return mod;
-  }
-  auto it = ctx->onelane_twins.find(mod);
-  if (it != ctx->onelane_twins.end()) return it->second < 0 ? mod : it->second;
-  const Big n = ctx->mods[mod].n;
-  int twin = -1;
-  if (create_mod(ctx, n.data(), (int)n.size(), false, &twin, &kOneLane) != SC_OK) twin = -1;
-  ctx->onelane_twins[mod] = twin;
+  if (const Mod& m = ctx->mods[mod]; !onelane_eligible(shape_of(m), m.nbits, m.nwords)) return mod;
+  // (the calibration may register moduli: no reference into ctx->mods is held across it)
+  if (ctx->onelane_mode == 1 && !onelane_faster(onelane_cal(ctx), count, ctx->chip_share, ctx->num_cu)) return mod;
+  const int twin = same_modulus_twin(ctx, TWIN_ONELANE, mod, false, &kOneLane);
   return twin < 0 ? mod : twin;
 }
 
@@ -1803,8 +1743,8 @@ static std::mutex g_pair_cal_mutex;
 static std::map<std::tuple<int, int, int, bool>, PairOpTimes> g_pair_cal;     // (device, G, L, neg1)
 
 static int pair_op_times(sc_ctx* ctx, int mod_m, uint64_t count, int x_words, const VmExt* ex3, double* sqr_ms, double* mul_ms) {
-  int G, L; bool neg1;
-  pvm_instance(ctx, ctx->mods[mod_m], count, &G, &L, &neg1);
+  const Instance k = pvm_instance(shape_of(ctx->mods[mod_m]), policy_of(ctx), count);
+  const int G = k.G, L = k.L; const bool neg1 = k.neg1;
   const auto key = std::make_tuple(ctx->device, G, L, neg1);
   std::lock_guard<std::mutex> lock(g_pair_cal_mutex);
   auto it = g_pair_cal.find(key);
@@ -1827,7 +1767,7 @@ static int pair_op_times(sc_ctx* ctx, int mod_m, uint64_t count, int x_words, co
   PolicyOverride keep(ctx);
   // the wave must run on the SAME instance as the launch it stands for: the batch-size policy is told the real batch size by keeping
   // the latency mode out of it (a tiny batch would otherwise pick the small-batch twin)
-  ctx->latency_mode = use_latency_config(ctx, m, count) ? 2 : 0;
+  ctx->latency_mode = small_batch(shape_of(m), policy_of(ctx), count) ? 2 : 0;
   const int occ = pvm_occupancy(ctx, G, L, neg1);
   const uint64_t one_wave = std::min<uint64_t>(count, (uint64_t)(64 / G) * (uint64_t)ctx->num_cu * (uint64_t)std::max(1, occ));   // (at most one round)
   double ms[4] = {1e30, 1e30, 1e30, 1e30};
@@ -1934,9 +1874,8 @@ static int pair_pow_prog(sc_ctx* ctx, const std::string& key, int mod_m, int exp
 // anyway, and every segment boundary costs a drain of the chip).  Both knobs: sc_ctx_set_pair_policy.
 static int pair_segment_count(sc_ctx* ctx, int mod_m, const Prog& prog, uint64_t count, int x_words, const VmExt* ex3, int* out_K) {
   *out_K = 1;
-  int iG, iL; bool ineg1;
-  pvm_instance(ctx, ctx->mods[mod_m], count, &iG, &iL, &ineg1);
-  const int occ = pvm_occupancy(ctx, iG, iL, ineg1);
+  const Instance k = pvm_instance(shape_of(ctx->mods[mod_m]), policy_of(ctx), count);
+  const int iG = k.G, occ = pvm_occupancy(ctx, k.G, k.L, k.neg1);
   const uint64_t wave_items = (count + (uint64_t)(64 / iG) - 1) / (uint64_t)(64 / iG);
   const uint64_t resident = (uint64_t)ctx->num_cu * (uint64_t)std::max(1, occ);
   const double rounds = (double)wave_items / (double)resident;
@@ -2032,7 +1971,7 @@ int sc_modexp_shared_sq(sc_ctx* ctx, int mod_m, int mod_m2, int exp, const uint3
   }
   // chip-filling batches of a (4,18) / (4,14) / (8,14) modulus: the pair launch runs modulo the multiple M = c m = -1 (mod 2^29),
   // which needs no quotient multiply; the assembly launch reduces w0 + w1 M modulo m^2 (m | M)
-  if (!use_latency_config(ctx, ctx->mods[mod_m], count)) { const int t = neg1_twin(ctx, mod_m); if (t >= 0) mod_m = t; }
+  if (!small_batch(shape_of(ctx->mods[mod_m]), policy_of(ctx), count)) { const int t = neg1_twin(ctx, mod_m); if (t >= 0) mod_m = t; }
   const int wm = ctx->mods[mod_m].nwords + 1;                            // words of the raw pair halves (< 2m + 1)
   uint32_t* d_w;
   int rc = tmp_buf(ctx, TMP_PAIR, (size_t)count * wm * 4 * 2, (void**)&d_w); if (rc) return rc;

@@ -2,7 +2,8 @@
 k_vm / k_pvm template instances, and plain-integer references for every primitive the matrix runs on them.
 
 Pure Python (no torch at import): tests/test_instance_matrix_cpu.py checks this table against the launcher sources and the first-fit
-rule on a machine without a GPU; tests/test_gpu_instance_matrix.py runs it.  The routes were worked out from csrc/sc_lib.hip:
+rule on a machine without a GPU; tests/test_gpu_instance_matrix.py runs it.  The routes restate csrc/sc_route.h, the header that holds the policy (sc_lib.hip applies
+it); the restatement stays independent of it, and tests/test_route_cpu.py compares the two rule by rule without a GPU:
 
 * sc_mod_create takes the first kConfigs entry with capacity W G L >= bits + 8 that also holds whole words (32 nwords <= W G L).  The
   whole-words condition moves the largest modulus of a configuration below 29 G L - 8 wherever that size needs another word:

@@ -51,7 +51,7 @@ def test_the_parser_notices_a_new_or_a_missing_instance():
 
 
 def source_configs():
-    text = _read("sc_internal.h")
+    text = _read("sc_route.h")
     body = re.search(r"const Config kConfigs\[\] = \{(.*?)\};", text, re.S).group(1)
     return [(int(g), int(l), int(w)) for g, l, w in re.findall(r"\{(\d+), (\d+), (\d+), true\}", body)]
 
