@@ -1,10 +1,12 @@
 // Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
-// (moduli, exponents, constants, tables, programs), the context itself, and the launch entry points of the kernel translation
-// units.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
+// (moduli, exponents, constants, tables, programs), the context itself, the one launch body of the one-wave-per-workgroup kernels
+// (launch_waves) and what the kernel translation units export: one look-up of its instances per part of the two interpreters, a
+// launch entry point per kernel elsewhere.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
 // sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip, sc_launch_scan.hip and
 // sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
 // the HIP-free plans and checks of the two axis entries, and sc_pack_plan.h, the HIP-free field lists of the four pack entries) holds no device code, so a change of host logic rebuilds in seconds.
-// sc_route.h, included here, is the HIP-free policy that picks the kernel instance of a launch: configurations, fit rule, twins.
+// sc_route.h, included here, is the HIP-free list of the interpreters' instances, with their launch keys, and the policy that picks the
+// instance of a launch: configurations, fit rule, twins.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -165,7 +167,7 @@ struct sc_ctx {
   size_t scratch_bytes = 0;
   std::vector<void*> owned;
   double mac_counter = 0;
-  std::map<int, int> occ_cache;  // config index -> blocks per CU
+  std::map<uint32_t, int> occ_cache;  // launch key of a kernel instance -> resident waves per CU (kernel_occupancy)
   std::map<int, std::pair<void*, size_t>> tmp;          // grow-only temporaries, reused across calls (same stream => ordered)
   std::map<std::vector<uint32_t>, uint32_t*> nwords_cache;  // device copy of {n, (n-1)/2} for the plain-word kernels
   std::map<int, int> kred_cache;                            // mod -> constant id of 2^(32 nwords) (wide-operand reduction)
@@ -221,33 +223,45 @@ namespace sc_host {
 // sc_lib.hip
 int fail(sc_ctx* ctx, int code, const char* fmt, ...);
 int ensure_scratch(sc_ctx* ctx, size_t bytes, uint32_t** out);
-// the key of an interpreter instance in sc_ctx::launch_counts (the packing include/sc_amd_dev.h documents)
-constexpr uint32_t launch_key(bool pvm, int G, int L, int W, bool neg1, bool stamp, bool dig) {
-  return (uint32_t)L | ((uint32_t)G << 8) | ((uint32_t)W << 16) | (neg1 ? 1u << 24 : 0u) | (stamp ? 1u << 25 : 0u) | (dig ? 1u << 26 : 0u) |
-         (pvm ? 1u << 27 : 0u);
+// sc_launch_vm.hip / sc_launch_pvm.hip, parts 0 .. 2: the row of the interpreter instance with that launch_key, or null when the part
+// does not compile it (each part holds its rows of the list in sc_route.h).  `launch` runs the instance on the context's stream (grid,
+// scratch arena and launch count handled there); `occupancy` is its resident waves per CU (asked once per context), <= 0 when the
+// query failed.
+struct KernelRow { uint32_t key; int (*launch)(sc_ctx* ctx, const sc::VmArgs& a); int (*occupancy)(sc_ctx* ctx); };
+const KernelRow* vm_part0(uint32_t key);
+const KernelRow* vm_part1(uint32_t key);
+const KernelRow* vm_part2(uint32_t key);
+const KernelRow* pvm_part0(uint32_t key);
+const KernelRow* pvm_part1(uint32_t key);
+const KernelRow* pvm_part2(uint32_t key);
+
+// Resident waves per CU of a one-wave-per-workgroup kernel: the runtime's occupancy answer held to 1 .. 16, cached in the context
+// under the instance's launch key; 0 when the query failed.
+template <typename Kernel>
+int kernel_occupancy(sc_ctx* ctx, uint32_t key, Kernel kernel) {
+  int& occ = ctx->occ_cache[key];                  // 0: not asked yet
+  if (!occ) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 64, 0) != hipSuccess) return 0;
+    occ = std::max(1, std::min(nb, 16));
+  }
+  return occ;
 }
-// the key of a k_prod_axis instance there: bit 28 set, L, G and W where the interpreters have them
-constexpr uint32_t reduce_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 28); }
-// ... and of a k_scan_axis instance: bit 29 set
-constexpr uint32_t scan_launch_key(int G, int L) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 29); }
-// ... and of a k_lin_axis instance: bit 30 set; with bit 24 its lifting launch k_lin_lift
-constexpr uint32_t lin_launch_key(int G, int L, bool lift) { return (uint32_t)L | ((uint32_t)G << 8) | (29u << 16) | (1u << 30) | (lift ? 1u << 24 : 0u); }
-// sc_launch_vm.hip / sc_launch_pvm.hip, parts 0 .. 2: launch the instance (G, L, W, NEG1[, STAMP]) of the interpreter on the context's
-// stream (grid, scratch arena and occupancy handled there); SC_ERR_UNSUPPORTED when the instance lives in another part
-int launch_vm_part0(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);
-int launch_vm_part1(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);
-int launch_vm_part2(sc_ctx* ctx, int G, int L, int W, bool neg1, const sc::VmArgs& a);
-int launch_pvm_part0(sc_ctx* ctx, int G, int L, bool neg1, bool stamp, const sc::VmArgs& a);
-int launch_pvm_part1(sc_ctx* ctx, int G, int L, bool neg1, bool stamp, const sc::VmArgs& a);
-int launch_pvm_part2(sc_ctx* ctx, int G, int L, bool neg1, bool stamp, const sc::VmArgs& a);
-// the instances that also run PV_MULTDIG (per-row exponents); SC_ERR_UNSUPPORTED when (G, L) has none in that part
-int launch_pvm_dig_part0(sc_ctx* ctx, int G, int L, const sc::VmArgs& a);
-int launch_pvm_dig_part1(sc_ctx* ctx, int G, int L, const sc::VmArgs& a);
-int launch_pvm_dig_part2(sc_ctx* ctx, int G, int L, const sc::VmArgs& a);
-// resident waves per CU of that pair kernel instance (occupancy query, cached in the context); <= 0 when the instance lives elsewhere
-int pvm_occupancy_part0(sc_ctx* ctx, int G, int L, bool neg1);
-int pvm_occupancy_part1(sc_ctx* ctx, int G, int L, bool neg1);
-int pvm_occupancy_part2(sc_ctx* ctx, int G, int L, bool neg1);
+// One launch of such a kernel on the context's stream, counted under `key`: `need` waves of work run as a grid-stride loop of at most
+// num_cu * occupancy resident waves, or (grid_stride false) as a wave each.  `prepare(grid, args)` fills in what depends on the grid
+// before the launch and may refuse it with an error code.
+template <typename Args, typename Prepare>
+int launch_waves(sc_ctx* ctx, uint32_t key, void (*kernel)(Args), uint64_t need, bool grid_stride, Args args, Prepare prepare) {
+  const int occ = kernel_occupancy(ctx, key, kernel);
+  if (occ <= 0) return fail(ctx, SC_ERR_HIP, "occupancy query failed for kernel instance %#x", key);
+  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, grid_stride ? std::min<uint64_t>(need, (uint64_t)ctx->num_cu * occ) : need);
+  const int rc = prepare(grid, args);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, ctx->stream, args);
+  ctx->launch_counts[key]++;
+  HIPCHK(ctx, hipGetLastError());
+  return SC_OK;
+}
 // sc_launch_misc.hip: 0 on success, a negative number when the launch itself failed
 int launch_xgcd(hipStream_t stream, const uint32_t* x, uint32_t* out, const uint32_t* d_n, int nw, uint64_t count, int* d_status);
 int launch_plain_alice(hipStream_t stream, const uint32_t* r, const uint32_t* nmod, const uint32_t* halfn, int nw, int l, uint64_t count, uint32_t* m1,

@@ -8,25 +8,26 @@
 
 namespace {
 
+constexpr bool axis_instances_are_the_multi_lane_configs() {
+#define SC_AXIS_PAIR(GG, LL) {GG, LL},
+  constexpr int axis[][2] = {SC_AXIS_INSTANCES(SC_AXIS_PAIR)};
+#undef SC_AXIS_PAIR
+  constexpr size_t n = sizeof axis / sizeof *axis;
+  size_t i = 0;
+  for (const sc_host::Config& c : sc_host::kConfigs) {
+    if (!c.primary || c.G == 1 || c.W != 29) continue;
+    if (i == n || axis[i][0] != c.G || axis[i][1] != c.L) return false;
+    i++;
+  }
+  return i == n;
+}
+static_assert(axis_instances_are_the_multi_lane_configs(), "SC_AXIS_INSTANCES is not the multi-lane primary rows of kConfigs");
+
 // One wave per workgroup, NG chains per wave, grid-stride over min(nchains / NG, num_cu * occupancy) resident waves on the context's
-// stream.  KEY is the instance's key in sc_ctx::launch_counts (reduce_launch_key / scan_launch_key: bit 28 or 29 set) and in
-// occ_cache as well, which the interpreters share: their keys there (10000 G + 10 L + 1000000 W + 0/1 in sc_launch_vm.hip, below
-// 1000000 in sc_launch_pvm.hip) stay below 3e7 < 2^28.
+// stream.  KEY is the instance's key in sc_ctx::launch_counts (reduce_launch_key / scan_launch_key / lin_launch_key).
 template <uint32_t KEY, typename Args>
 int launch_axis(sc_ctx* ctx, void (*kernel)(Args), int NG, uint64_t nchains, const Args& a) {
-  const int key = (int)KEY;
-  int& occ = ctx->occ_cache[key];                  // 0: not asked yet
-  if (!occ) {
-    int nb = 0;
-    HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 64, 0));
-    occ = std::max(1, std::min(nb, 16));
-  }
-  const uint64_t need = (nchains + NG - 1) / NG, maxb = (uint64_t)ctx->num_cu * occ;
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min(need, maxb));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, ctx->stream, a);
-  ctx->launch_counts[KEY]++;
-  HIPCHK(ctx, hipGetLastError());
-  return SC_OK;
+  return sc_host::launch_waves(ctx, KEY, kernel, (nchains + NG - 1) / NG, true, a, [](uint32_t, Args&) { return (int)SC_OK; });
 }
 
 }  // namespace

@@ -418,6 +418,13 @@ int cached_prog(sc_ctx* ctx, const std::string& key, int mod, F&& build, const P
 inline Policy policy_of(const sc_ctx* ctx) { return {ctx->latency_mode, ctx->onelane_mode, ctx->chip_share, ctx->num_cu}; }
 inline Instance shape_of(const Mod& m) { return {m.G, m.L, m.W, m.n0inv == 1}; }
 
+// The row of an interpreter instance in the part that compiles it, or null.
+const KernelRow* find_instance(uint32_t key) {
+  for (auto part : {vm_part0, vm_part1, vm_part2, pvm_part0, pvm_part1, pvm_part2})
+    if (const KernelRow* row = part(key)) return row;
+  return nullptr;
+}
+
 int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uint64_t count, const uint32_t* fbt_rows = nullptr) {
   if (count == 0) return SC_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));  // the caller may have switched the current device since sc_ctx_create
@@ -440,19 +447,15 @@ int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uin
   const Instance k = vm_instance(shape_of(m), policy_of(ctx), count);
   ctx->mac_counter += (double)count * ((p.muls_per_item * 2.0 + p.redcs_per_item + p.sqrs_per_item) * (double)m.S * m.S +
                                         p.sqrs_per_item * (double)k.G * k.G * k.L * (k.L + 1) / 2.0);
-  int rc = launch_vm_part0(ctx, k.G, k.L, k.W, k.neg1, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_vm_part1(ctx, k.G, k.L, k.W, k.neg1, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_vm_part2(ctx, k.G, k.L, k.W, k.neg1, a);
-  if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no kernel configuration for G=%d L=%d", k.G, k.L);
-  return rc;
+  const KernelRow* row = find_instance(launch_key(false, k.G, k.L, k.W, k.neg1, false, false));
+  if (!row) return fail(ctx, SC_ERR_UNSUPPORTED, "no kernel configuration for G=%d L=%d", k.G, k.L);
+  return row->launch(ctx, a);
 }
 
-// resident waves per CU of that instance (the runtime's occupancy answer, not a compiled-in assumption)
+// resident waves per CU of that instance (the runtime's occupancy answer, not a compiled-in assumption); <= 0 when there is none
 int pvm_occupancy(sc_ctx* ctx, int G, int L, bool neg1) {
-  int occ = pvm_occupancy_part0(ctx, G, L, neg1);
-  if (occ < 0) occ = pvm_occupancy_part1(ctx, G, L, neg1);
-  if (occ < 0) occ = pvm_occupancy_part2(ctx, G, L, neg1);
-  return occ;
+  const KernelRow* row = find_instance(launch_key(true, G, L, kPairW, neg1, false, false));
+  return row ? row->occupancy(ctx) : -1;
 }
 
 // pair programs: nscratch counts limb-form entries (2 per pair entry); macs = multiply-adds per item
@@ -468,19 +471,15 @@ int run_pvm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, ui
   ctx->mac_counter += (double)count * p.muls_per_item;   // pair programs carry their exact multiply-add count here
   if (!pair_capable(m.G, m.L, m.W)) return fail(ctx, SC_ERR_UNSUPPORTED, "no pair kernel for G=%d L=%d", m.G, m.L);
   if (p.pair_dig) {      // per-row exponents: the modulus's own instance with PV_MULTDIG (no latency / n = -1 variants of it exist)
-    int rc = launch_pvm_dig_part0(ctx, m.G, m.L, a);
-    if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_dig_part1(ctx, m.G, m.L, a);
-    if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_dig_part2(ctx, m.G, m.L, a);
-    if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no per-row-exponent pair kernel for G=%d L=%d", m.G, m.L);
-    return rc;
+    const KernelRow* row = find_instance(launch_key(true, m.G, m.L, kPairW, false, false, true));
+    if (!row) return fail(ctx, SC_ERR_UNSUPPORTED, "no per-row-exponent pair kernel for G=%d L=%d", m.G, m.L);
+    return row->launch(ctx, a);
   }
   const Instance k = pvm_instance(shape_of(m), policy_of(ctx), count);
   const bool stamp = k.neg1 && k.G == 4 && k.L == 18 && ctx->stamps != nullptr;     // the stamping twin of (4,18,neg1) is sc_clock_probe's diagnostic launch
-  int rc = launch_pvm_part0(ctx, k.G, k.L, k.neg1, stamp, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_part1(ctx, k.G, k.L, k.neg1, stamp, a);
-  if (rc == SC_ERR_UNSUPPORTED) rc = launch_pvm_part2(ctx, k.G, k.L, k.neg1, stamp, a);
-  if (rc == SC_ERR_UNSUPPORTED) return fail(ctx, rc, "no pair kernel for G=%d L=%d", k.G, k.L);
-  return rc;
+  const KernelRow* row = find_instance(launch_key(true, k.G, k.L, kPairW, k.neg1, stamp, false));
+  if (!row) return fail(ctx, SC_ERR_UNSUPPORTED, "no pair kernel for G=%d L=%d", k.G, k.L);
+  return row->launch(ctx, a);
 }
 
 VmExt mk_ext(const void* p, uint32_t stride, uint32_t nwords, uint64_t limit = ~0ull) {

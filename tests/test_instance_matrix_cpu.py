@@ -1,58 +1,87 @@
-"""The instance matrix (tests/_instance_matrix.py) against the sources it describes, without a GPU: the launcher files compile exactly
-the instances the matrix lists, every matrix modulus gets the configuration the matrix claims under the first-fit rule restated from
+"""The instance matrix (tests/_instance_matrix.py) against the sources it describes, without a GPU: csrc/sc_route.h lists exactly the
+instances the matrix lists, every matrix modulus gets the configuration the matrix claims under the first-fit rule restated from
 kConfigs, the inversion operands satisfy their conditions, and the plain-integer references agree with themselves."""
 import math
 import os
 import re
+import subprocess
 
 import _instance_matrix as M
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "protocols", "secure_comparison_amd", "csrc")
 
+# prints the list of sc_route.h, the header the launchers expand: one line per instance, in the fields of M.INSTANCES
+PROGRAM = r"""
+#include "sc_route.h"
+
+#include <cstdio>
+
+#define PUT_VM(G, L, W, NEG1) printf("vm %d %d %d %d 0 0\n", G, L, W, (int)NEG1);
+#define PUT_PVM(G, L, NEG1, STAMP, DIG) printf("pvm %d %d %d %d %d %d\n", G, L, sc_host::kPairW, (int)NEG1, (int)STAMP, (int)DIG);
+
+int main() {
+  SC_VM_INSTANCES(PUT_VM)
+  SC_PVM_INSTANCES(PUT_PVM)
+  return 0;
+}
+"""
+
 
 def _read(name):
     return open(os.path.join(CSRC, name)).read()
 
 
-def compiled_instances(vm_text=None, pvm_text=None):
-    """Every k_vm / k_pvm instance the launchers name: SC_CASE / SC_CASE_NEG1 uses and explicit launch_*_cfg<...> calls (the occupancy
-    dispatcher at the end of sc_launch_pvm.hip re-uses the macro names for queries: it launches nothing and is left out)."""
-    vm = _read("sc_launch_vm.hip") if vm_text is None else vm_text
-    pvm = (_read("sc_launch_pvm.hip") if pvm_text is None else pvm_text).split("#undef SC_CASE")[0]
-    flag = lambda s: s == "true"  # noqa: E731
+def compiled_instances(workdir, header=None):
+    """Every k_vm / k_pvm instance of the list in sc_route.h (or in the text `header`, a changed copy of it), printed by a stand-alone
+    program that includes that header alone.  A header that does not compile raises CalledProcessError with the compiler's words."""
+    include = CSRC
+    if header is not None:
+        include = str(workdir)
+        (workdir / "sc_route.h").write_text(header)
+    src, exe = workdir / "instances.cpp", workdir / "instances"
+    src.write_text(PROGRAM)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", include, str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
     out = []
-    for g, l, w in re.findall(r"\bSC_CASE\((\d+), (\d+), (\d+)\)", vm):
-        out.append(("vm", int(g), int(l), int(w), False, False, False))
-    for g, l, w, n1 in re.findall(r"launch_vm_cfg<(\d+), (\d+), (\d+)(?:, (true|false))?>", vm):
-        out.append(("vm", int(g), int(l), int(w), flag(n1), False, False))
-    for g, l in re.findall(r"\bSC_CASE\((\d+), (\d+)\)", pvm):
-        out.append(("pvm", int(g), int(l), 29, False, False, False))
-    for g, l in re.findall(r"\bSC_CASE_NEG1\((\d+), (\d+)\)", pvm):
-        out.append(("pvm", int(g), int(l), 29, True, False, False))
-    for g, l, w, n1, st, dg in re.findall(r"launch_pvm_cfg<(\d+), (\d+), (\d+)(?:, (true|false))?(?:, (true|false))?(?:, (true|false))?>", pvm):
-        out.append(("pvm", int(g), int(l), int(w), flag(n1), flag(st), flag(dg)))
+    for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
+        kind, g, l, w, neg1, stamp, dig = line.split()
+        out.append((kind, int(g), int(l), int(w), neg1 == "1", stamp == "1", dig == "1"))
     return out
 
 
-def test_matrix_lists_exactly_the_compiled_instances():
-    got = compiled_instances()
+def test_matrix_lists_exactly_the_compiled_instances(tmp_path):
+    got = compiled_instances(tmp_path)
     assert len(got) == len(set(got)) == 37, sorted(got)
     assert sorted(got) == sorted(M.INSTANCES)
     assert len([i for i in got if i[0] == "vm"]) == 17 and len([i for i in got if i[0] == "pvm"]) == 20
     assert len({M.instance_id(i) for i in M.INSTANCES}) == 37
 
 
-def test_the_parser_notices_a_new_or_a_missing_instance():
-    vm, pvm = _read("sc_launch_vm.hip"), _read("sc_launch_pvm.hip")
-    assert sorted(compiled_instances(vm.replace("SC_CASE(16, 14, 29)", "SC_CASE(16, 14, 29) SC_CASE(16, 27, 29)"), pvm)) != sorted(M.INSTANCES)
-    assert sorted(compiled_instances(vm, pvm.replace("SC_CASE(16, 5)", ""))) != sorted(M.INSTANCES)
-    assert sorted(compiled_instances(vm, pvm.replace("SC_CASE_NEG1(8, 14)", "SC_CASE_NEG1(8, 14) SC_CASE_NEG1(8, 18)", 1))) != sorted(M.INSTANCES)
+def _changed(text, old, new):
+    assert text.count(old) == 1, old
+    return text.replace(old, new)
+
+
+def test_the_list_notices_a_new_or_a_missing_instance(tmp_path):
+    text = _read("sc_route.h")
+    more_vm = _changed(text, "X(16, 14, 29, false)", "X(16, 14, 29, false) X(16, 27, 29, false)")
+    fewer_pvm = _changed(text, " X(8, 14, false, false, true)", "")
+    more_neg1 = _changed(text, "X(8, 14, true, false, false)", "X(8, 14, true, false, false) X(8, 18, true, false, false)")
+    for header in (more_vm, fewer_pvm, more_neg1):
+        assert sorted(compiled_instances(tmp_path, header)) != sorted(M.INSTANCES)
+    # a row that a rule can pick -- (16, 9) is the small-batch form of an (8, 18) modulus -- cannot be taken out: the header's
+    # static_asserts refuse to compile
+    try:
+        compiled_instances(tmp_path, _changed(text, " X(16, 9, 29, false)", ""))
+    except subprocess.CalledProcessError as e:
+        assert "static assertion failed" in e.stderr and "has no (2G, 9) k_vm instance" in e.stderr
+    else:
+        raise AssertionError("sc_route.h compiled without k_vm<16, 9>")
 
 
 def source_configs():
     text = _read("sc_route.h")
-    body = re.search(r"const Config kConfigs\[\] = \{(.*?)\};", text, re.S).group(1)
+    body = re.search(r"constexpr Config kConfigs\[\] = \{(.*?)\};", text, re.S).group(1)
     return [(int(g), int(l), int(w)) for g, l, w in re.findall(r"\{(\d+), (\d+), (\d+), true\}", body)]
 
 

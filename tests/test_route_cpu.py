@@ -56,6 +56,8 @@ int main() {
     else if (cmd == "cand") put(neg1_candidate(m, (int)v[4]));
     else if (cmd == "negvm") put(neg1_vm_allowed(m, p, count));
     else if (cmd == "onelane") put(onelane_eligible(m, (int)v[4], (int)v[5]));
+    else if (cmd == "hasvm") put(has_vm(m.G, m.L, m.W, m.neg1));
+    else if (cmd == "haspvm") put(m.W == kPairW && has_pvm(m.G, m.L, m.neg1, v[4] != 0, v[5] != 0));
     else if (cmd == "cost") {
       const OneLaneCal cal;
       const OneLaneCost k = onelane_cost(cal, (uint64_t)v[0], (int)v[1], (int)v[2]);
@@ -174,8 +176,10 @@ def test_first_fit(exe):
     assert M.first_fit(M.MAX_BITS + 1) is None and M.first_fit(M.MAX_BITS) == (16, 18)
 
 
-def test_matrix_instances(exe):
-    q, asked = Queries(), []
+def matrix_routes(q):
+    """The single-modulus and the pair route of every matrix case at every matrix batch size: (where, the instance the matrix expects,
+    the route's answer once `q` has run)."""
+    asked = []
     for inst in matrix_instances():
         for c in M.cases_for(inst):
             words = M.nwords_of(c.bits)
@@ -184,10 +188,34 @@ def test_matrix_instances(exe):
                 asked.append((where, M.expected_instance(c, "pvm"), pvm_route(q, c.n, words, c.latency, c.chip_share, count)))
                 if not c.pair9:         # the k_pvm<2G, 9> window is a statement about pair calls only
                     asked.append((where, M.expected_instance(c, "vm"), vm_route(q, c.n, words, c.latency, c.onelane, c.chip_share, count)))
+    return asked
+
+
+def test_matrix_instances(exe):
+    q = Queries()
+    asked = matrix_routes(q)
     q.run(exe)
     for where, want, answer in asked:
         assert answer() == want, where
     assert len(asked) > 2000
+
+
+def test_every_matrix_route_lands_on_a_compiled_instance(exe):
+    """Where the policy sends a launch, the header's own list has a kernel: has_vm / has_pvm of every route's instance."""
+    q = Queries()
+    asked = matrix_routes(q)
+    q.run(exe)
+    q2, has = Queries(), []
+    for where, _, answer in asked:
+        kind, g, l, w, neg1 = answer()
+        has.append((where, q2.ask("has" + kind, g, l, w, neg1, 0, 0)))
+    absent = [q2.ask("hasvm", 16, 27, M.W, 0), q2.ask("haspvm", 8, 18, M.W, 1, 0, 0), q2.ask("haspvm", 4, 18, 28, 0, 0, 0),
+              q2.ask("haspvm", 4, 18, M.W, 0, 1, 0), q2.ask("haspvm", 16, 18, M.W, 0, 0, 1)]
+    q2.run(exe)
+    assert len(has) == 2425
+    for where, h in has:
+        assert h.value == (1,), where
+    assert [h.value for h in absent] == [(0,)] * 5
 
 
 def test_matrix_cases_land_on_their_instance(exe):
