@@ -14,8 +14,10 @@ from protocols.secure_comparison_amd import Initiator, KeyHolder
 _stream: contextvars.ContextVar = contextvars.ContextVar("session_stream")
 
 
-def run_sessions(pairs, l, bob_p, bob_d, coalesce: bool, alice_paillier=None, strict: bool = True, seed: int = 5, replay: bool = True):
-    """(results as integers, {msg_id: [ciphertext integers]}, coalescer statistics of both players)."""
+def run_sessions(pairs, l, bob_p, bob_d, coalesce: bool, alice_paillier=None, strict: bool = True, seed: int = 5, replay: bool = True,
+                 streams=None):
+    """(results as integers, {msg_id: [ciphertext integers]}, coalescer statistics of both players).  streams(tag, i, rng): the stream
+    of player `tag`'s session i, made from its seeded one (a test that plants a draw wraps it); None = the seeded stream itself."""
     sent = {}
 
     class Tap(DictionaryCommunicator):
@@ -37,7 +39,8 @@ def run_sessions(pairs, l, bob_p, bob_d, coalesce: bool, alice_paillier=None, st
         alice.draw_source = bob.draw_source = SecretsDraws()
 
     async def as_session(tag, i, coro_fn):
-        _stream.set(random.Random(f"{seed}:{tag}:{i}"))
+        rng = random.Random(f"{seed}:{tag}:{i}")
+        _stream.set(rng if streams is None else streams(tag, i, rng))
         return await coro_fn()
 
     async def together():
