@@ -3,7 +3,7 @@
 The library is fourteen translation units: the host side (csrc/sc_lib.hip, no device code), the instances of the two interpreter
 kernels in three parts each (csrc/sc_launch_vm.hip / sc_launch_pvm.hip with -DSC_PART=0/1/2, each part expanding its rows of the
 instance list in csrc/sc_route.h and exporting one look-up of them) and the remaining kernels
-(csrc/sc_launch_misc.hip; the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip, the running product in csrc/sc_launch_scan.hip, the linear map with public weights in csrc/sc_launch_lin.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
+(csrc/sc_launch_misc.hip with csrc/sc_kernel_plain.h; each of these defined in the unit that launches it, over the bit-field helpers of csrc/sc_plain_words.h: the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip, the running product in csrc/sc_launch_scan.hip, the linear map with public weights in csrc/sc_launch_lin.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
 so a change of host logic or policy costs seconds and a kernel change only the parts that hold that kernel.
 """
 from __future__ import annotations

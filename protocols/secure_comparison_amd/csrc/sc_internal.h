@@ -2,7 +2,8 @@
 // (moduli, exponents, constants, tables, programs), the context itself, the one launch body of the one-wave-per-workgroup kernels
 // (launch_waves) and what the kernel translation units export: one look-up of its instances per part of the two interpreters, a
 // launch entry point per kernel elsewhere.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
-// sc_launch_misc.hip, sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip, sc_launch_reduce.hip, sc_launch_scan.hip and
+// sc_launch_misc.hip (with sc_kernel_plain.h), sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip (each family's plain-word kernels
+// in its own unit, the helpers they share in sc_plain_words.h), sc_launch_reduce.hip, sc_launch_scan.hip and
 // sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
 // the HIP-free plans and checks of the two axis entries, and sc_pack_plan.h, the HIP-free field lists of the four pack entries) holds no device code, so a change of host logic rebuilds in seconds.
 // sc_route.h, included here, is the HIP-free list of the interpreters' instances, with their launch keys, and the policy that picks the
@@ -262,7 +263,11 @@ int launch_waves(sc_ctx* ctx, uint32_t key, void (*kernel)(Args), uint64_t need,
   HIPCHK(ctx, hipGetLastError());
   return SC_OK;
 }
-// sc_launch_misc.hip: 0 on success, a negative number when the launch itself failed
+// What the launch entry points below share: their answer, 0 on success and a negative number when the launch itself failed, and the
+// grid of a kernel that runs `count` items in blocks of 256 threads.
+inline int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+inline dim3 blocks256(uint64_t count) { return dim3((unsigned)((count + 255) / 256)); }
+// sc_launch_misc.hip
 int launch_xgcd(hipStream_t stream, const uint32_t* x, uint32_t* out, const uint32_t* d_n, int nw, uint64_t count, int* d_status);
 int launch_plain_alice(hipStream_t stream, const uint32_t* r, const uint32_t* nmod, const uint32_t* halfn, int nw, int l, uint64_t count, uint32_t* m1,
                        uint64_t* alpha, uint64_t* alpha_tilde, uint64_t* rsmall, uint32_t* rshift);

@@ -86,7 +86,7 @@ struct SelLayout {
   int off[SEL_MAX_FIELDS], fbits[SEL_MAX_FIELDS], width[SEL_MAX_FIELDS];
 };
 
-// Field layout of a secure multiplication's packed plaintext (k_mul_prep / k_mul_split, sc_kernel_plain.h): A in [0, s), then B_j
+// Field layout of a secure multiplication's packed plaintext (k_mul_prep / k_mul_split, sc_launch_mul.hip): A in [0, s), then B_j
 constexpr int MUL_MAX_WIDTH = 255;
 constexpr int MUL_FIELD_WORDS = 10;   // a field or an exponent has at most 255 + 62 + 1 = 318 bits
 struct MulLayout {
@@ -94,7 +94,7 @@ struct MulLayout {
   int off[SEL_MAX_FIELDS], fbits[SEL_MAX_FIELDS], wy[SEL_MAX_FIELDS];
 };
 
-// Layout of a secure inner product's packed plaintexts (k_dot_prep / k_dot_split, sc_kernel_plain.h): k pairs (A_j, B_j)
+// Layout of a secure inner product's packed plaintexts (k_dot_prep / k_dot_split, sc_launch_dot.hip): k pairs (A_j, B_j)
 // of sa + sb = pb bits, g of them per message, M = ceil(k / g) messages per row, pair j in message j mod M at position j div M.  The
 // widths are uniform, so the struct holds scalars only.  square: every pair is the one field A_j (sb = 0, pb = sa).
 constexpr int DOT_MAX_K = 1024;
@@ -104,7 +104,7 @@ struct DotLayout {
   int wx, wy, is_signed, square;
 };
 
-// Layout of a secure one-hot's packed plaintexts (k_onehot_prep / k_onehot_split, sc_kernel_plain.h): m indices per row,
+// Layout of a secure one-hot's packed plaintexts (k_onehot_prep / k_onehot_split, sc_launch_lookup.hip): m indices per row,
 // every one a field d_q = i_q + r_q of f = ib + kappa + 1 bits, g of them per message at the bit offsets 0, f, 2f, .., M = ceil(m / g)
 // messages per row; index q lives in message q div g at position q mod g, so only the last message may hold fewer than g fields.
 constexpr int ONEHOT_MAX_K = 1024;

@@ -451,7 +451,7 @@ def first_over(rows, ends):
 
 
 # ==== multiplication ==================================================================================================================
-# sc_kernel_plain.h: A in bits [0, s), s = wx + kappa + 1, then field j of fbits[j] = wy[j] + kappa + 1 bits at off[j], off[0] = s,
+# sc_launch_mul.hip: A in bits [0, s), s = wx + kappa + 1, then field j of fbits[j] = wy[j] + kappa + 1 bits at off[j], off[0] = s,
 # off[j + 1] = off[j] + fbits[j]; every s + fbits[j] and the end of the last field stay below bits(N) - 1.
 MulCase = collections.namedtuple("MulCase", "nbits kappa wx wy signed aw bw ew")
 MUL_LAYOUTS = (
@@ -581,7 +581,7 @@ def expected_mul_split(c, ps) -> dict:
 
 
 # ==== inner product ===================================================================================================================
-# sc_kernel_plain.h: k pairs (A_j, B_j) of sa = wx + kappa + 1 and sb = wy + kappa + 1 bits, pb = sa + sb (square: the one field, sb = 0);
+# sc_launch_dot.hip: k pairs (A_j, B_j) of sa = wx + kappa + 1 and sb = wy + kappa + 1 bits, pb = sa + sb (square: the one field, sb = 0);
 # g = the largest integer with g pb < bits(N) - 1, M = ceil(k / g) messages; pair j in message j mod M at position t = j div M, A in
 # bits [t pb, t pb + sa), B above it; message m ends at n_m pb.  pb' + ceil(log2 k) < bits(N) - 1, pb' = sa + sb (2 sa for a square).
 DotCase = collections.namedtuple("DotCase", "nbits kappa wx wy signed square k aw bw ew")
@@ -756,7 +756,7 @@ def dot_bad_messages(c) -> list:
 
 
 # ==== one-hot =========================================================================================================================
-# sc_kernel_plain.h: m indices per row; field q of f = ib + kappa + 1 bits in message q div g at bits [(q mod g) f, (q mod g + 1) f),
+# sc_launch_lookup.hip: m indices per row; field q of f = ib + kappa + 1 bits in message q div g at bits [(q mod g) f, (q mod g + 1) f),
 # g = floor((bits(N) - 2) / f) >= 1 with f < bits(N) - 1; message mm holds n_mm = min(g, m - mm g) fields.  A mask has ib + kappa bits in
 # rw >= ceil((ib + kappa) / 32) words, rw <= 3.
 OnehotCase = collections.namedtuple("OnehotCase", "nbits kappa ib k m rw count")
