@@ -1,10 +1,12 @@
 """Build libsc_amd.so (hipcc, gfx950) in-tree.  Used by __graft_entry__.build() and by hand.
 
-The library is fourteen translation units: the host side (csrc/sc_lib.hip, no device code), the instances of the two interpreter
+The library is seventeen translation units: the host side in four of them, none with device code (csrc/sc_lib.hip and HOST_UNITS below:
+families, schemes, top-m network; what they share is declared in csrc/sc_host.h, their set-up-time integers are the HIP-free
+csrc/sc_bigint.h), the instances of the two interpreter
 kernels in three parts each (csrc/sc_launch_vm.hip / sc_launch_pvm.hip with -DSC_PART=0/1/2, each part expanding its rows of the
 instance list in csrc/sc_route.h and exporting one look-up of them) and the remaining kernels
 (csrc/sc_launch_misc.hip with csrc/sc_kernel_plain.h; each of these defined in the unit that launches it, over the bit-field helpers of csrc/sc_plain_words.h: the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip, the running product in csrc/sc_launch_scan.hip, the linear map with public weights in csrc/sc_launch_lin.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
-so a change of host logic or policy costs seconds and a kernel change only the parts that hold that kernel.
+so a change of host logic costs the seconds of the host units it touches and a kernel change only the parts that hold that kernel.
 """
 from __future__ import annotations
 
@@ -32,7 +34,9 @@ UNITS = [("sc_lib", "sc_lib.hip", [])] + \
 # The fourteenth unit, the linear map with public weights, is listed apart: tests/test_scan_cpu.py holds UNITS at the
 # thirteen above, whose objects this unit leaves byte for byte what they were.  The library is built from ALL_UNITS.
 LINEAR_UNITS = [("sc_launch_lin", "sc_launch_lin.hip", [])]
-ALL_UNITS = UNITS + LINEAR_UNITS
+# The host units beside sc_lib.hip; each begins with its own includes and compiles on its own.
+HOST_UNITS = [(n, n + ".hip", []) for n in ("sc_families", "sc_schemes", "sc_topk")]
+ALL_UNITS = UNITS + LINEAR_UNITS + HOST_UNITS
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
     os.path.join(INCLUDE, "sc_amd.h"), os.path.join(INCLUDE, "sc_amd_dev.h")]
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)

@@ -1,10 +1,11 @@
 // Secure selection, multiplication, inner product and one-hot encoding: each family's layout rule on the
 // host and the plaintext-word halves of its two players (k_*_prep / k_*_split, the one-hot's k_onehot_rotate); the compare-exchange
-// finish of a sort (§8c).  The scheme-level entries of the four families (sc_schemes.h) check the same layouts before they launch anything.
-//
-// Included in the middle of sc_lib.hip, inside its extern "C" block (same translation unit: uses its context, program builder and
-// launch helpers).
-#pragma once
+// finish of a sort (§8c).  The scheme-level entries of the four families (sc_schemes.hip) check the same layouts before they launch
+// anything: the layout rules and refusals they share are declared, with their comments, in sc_host.h.  Host code only.
+#include "sc_host.h"
+
+using namespace sc;
+using namespace sc_host;
 
 // The one field-packing rule of the selection and the multiplication: a low field of s bits, then nf fields of
 // fbits_j = widths_j + kappa + fbits_extra bits; every s + fbits_j and the end of the last field stay below bits(N) - 1.  Every refusal
@@ -28,9 +29,7 @@ static int pack_fields(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int
 }
 
 // ---- secure selection: the plaintext-word halves of the two players (k_select_prep / k_select_split) -------------------------------
-// SelectLayout.__post_init__ (selection.py) on the host -- the one copy of the rule every selection entry checks before it launches
-// anything (sc_select_prep / sc_select_split here, the scheme-level entries of sc_schemes.h)
-static int select_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int nfields, const int* widths, SelLayout* lay) {
+int sc_host::select_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int nfields, const int* widths, SelLayout* lay) {
   if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
   lay->s = kappa + 1; lay->nf = nfields;
   int rc = pack_fields(ctx, who, nbits_n, kappa, lay->s, nfields, widths, 4096, 2, "a * b", lay->off, lay->fbits, &lay->end); if (rc) return rc;
@@ -38,7 +37,7 @@ static int select_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, i
   return SC_OK;
 }
 
-int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* r_a,
+extern "C" int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* r_a,
                    int aw, const uint32_t* r_b, int bw, int ew, uint32_t* R, uint32_t* e, uint32_t* rab, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   if (!ctx || !n_hptr || nw <= 0 || !r_a || !r_b || !R || !e || !rab || aw < 1 || aw > 2 || bw < 1 || ew < 1)
@@ -53,7 +52,7 @@ int sc_select_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int n
   return SC_OK;
 }
 
-int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* p,
+extern "C" int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int nfields, const int* widths_hptr, const uint32_t* p,
                     uint32_t* prod, uint32_t* bad, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   if (!ctx || !n_hptr || nw <= 0 || !p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_select_split: bad argument");
@@ -65,9 +64,7 @@ int sc_select_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int 
 }
 
 // ---- secure multiplication: the plaintext-word halves of the two players (k_mul_prep / k_mul_split) ---------------
-// MulLayout.__post_init__ (multiplication.py) on the host -- the one copy of the fit rule every multiplication entry checks before it
-// launches anything: s + sum_j fbits_j < bits(N) - 1 and every s + fbits_j < bits(N) - 1
-static int mul_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int nfields, const int* wy, int is_signed, MulLayout* lay) {
+int sc_host::mul_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int nfields, const int* wy, int is_signed, MulLayout* lay) {
   if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
   if (wx < 1 || wx > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: wx = %d: expected 1 .. %d", who, wx, MUL_MAX_WIDTH);
   lay->s = wx + kappa + 1; lay->nf = nfields; lay->wx = wx; lay->is_signed = is_signed ? 1 : 0;
@@ -75,23 +72,20 @@ static int mul_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int 
   std::copy(wy, wy + nfields, lay->wy);
   return SC_OK;
 }
-static int mul_ebits(const MulLayout& lay) { int b = lay.s; for (int j = 0; j < lay.nf; j++) b = std::max(b, lay.fbits[j]); return b; }
-// two refusals the scheme-level entries share: exponent rows of ew words hold `bits` bits; finish_ratio's coef is +1, -1 or -2
-static int exp_rows(sc_ctx* ctx, const char* who, int ew, int bits) {
+int sc_host::mul_ebits(const MulLayout& lay) { int b = lay.s; for (int j = 0; j < lay.nf; j++) b = std::max(b, lay.fbits[j]); return b; }
+int sc_host::exp_rows(sc_ctx* ctx, const char* who, int ew, int bits) {
   return 32 * ew < bits ? fail(ctx, SC_ERR_ARG, "%s: exponent rows of %d words are too narrow for %d bits", who, ew, bits) : SC_OK;
 }
-static int ratio_coef(sc_ctx* ctx, const char* who, int coef) {
+int sc_host::ratio_coef(sc_ctx* ctx, const char* who, int coef) {
   return coef != 1 && coef != -1 && coef != -2 ? fail(ctx, SC_ERR_ARG, "%s: coef = %d: expected +1, -1 or -2", who, coef) : SC_OK;
 }
-// the draws' and exponents' row widths of the multiplication and the inner product: the kernels hold a field in MUL_FIELD_WORDS words
-// (bw_max: the multiplication's r_b rows are no wider than N either; has_b: a square reads no r_b)
-static int row_words(sc_ctx* ctx, const char* who, int ebits, int aw, int bw, bool has_b, int bw_max, int ew) {
+int sc_host::row_words(sc_ctx* ctx, const char* who, int ebits, int aw, int bw, bool has_b, int bw_max, int ew) {
   if (aw < 1 || aw > MUL_FIELD_WORDS || (has_b && (bw < 1 || bw > bw_max)) || ew < 1)
     return fail(ctx, SC_ERR_ARG, "%s: rows of %d (r_a), %d (r_b), %d (e) words: expected 1 .. %d for the draws", who, aw, bw, ew, MUL_FIELD_WORDS);
   return exp_rows(ctx, who, ew, ebits);
 }
 
-int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
+extern "C" int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, int is_signed,
                 const uint32_t* r_a, int aw, const uint32_t* r_b, int bw, int ew, uint32_t* R, uint32_t* e, uint32_t* rab, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   if (!ctx || !n_hptr || nw <= 0 || !r_a || !r_b || !R || !e || !rab) return fail(ctx, SC_ERR_ARG, "sc_mul_prep: bad argument");
@@ -103,7 +97,7 @@ int sc_mul_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, 
   return SC_OK;
 }
 
-int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p,
+extern "C" int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int nfields, const int* wy_hptr, const uint32_t* p,
                  uint32_t* prod, uint32_t* bad, uint64_t count) {
   if (ctx && count == 0) return SC_OK;
   if (!ctx || !n_hptr || nw <= 0 || !p || !prod || !bad) return fail(ctx, SC_ERR_ARG, "sc_mul_split: bad argument");
@@ -115,10 +109,7 @@ int sc_mul_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx,
 }
 
 // ---- secure inner product: the plaintext-word halves of the two players (k_dot_prep / k_dot_split) -----------------
-// DotLayout.__post_init__ (dotproduct.py) on the host -- the one copy of the fit rule every inner-product entry checks before it launches
-// anything: g = the largest integer with g pb < bits(N) - 1 must be at least 1, and the sum of k products must stay below N:
-// pb' + ceil(log2 k) < bits(N) - 1 with pb' = sa + sb (2 sa for a square).  Every refusal names its quantity.
-static int dot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, DotLayout* lay) {
+int sc_host::dot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, DotLayout* lay) {
   if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
   if (wx < 1 || wx > MUL_MAX_WIDTH) return fail(ctx, SC_ERR_ARG, "%s: wx = %d: expected 1 .. %d", who, wx, MUL_MAX_WIDTH);
   if (!square && (wy < 1 || wy > MUL_MAX_WIDTH)) return fail(ctx, SC_ERR_ARG, "%s: wy = %d: expected 1 .. %d", who, wy, MUL_MAX_WIDTH);
@@ -137,7 +128,7 @@ static int dot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int 
   return SC_OK;
 }
 
-int sc_dot_layout(int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, int* out) {
+extern "C" int sc_dot_layout(int nbits_n, int kappa, int wx, int wy, int is_signed, int square, int k, int* out) {
   DotLayout lay;
   if (!out) return SC_ERR_ARG;
   int rc = dot_layout(nullptr, "sc_dot_layout", nbits_n, kappa, wx, wy, is_signed, square, k, &lay); if (rc) return rc;
@@ -145,7 +136,7 @@ int sc_dot_layout(int nbits_n, int kappa, int wx, int wy, int is_signed, int squ
   return SC_OK;
 }
 
-int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int is_signed, int square, int k, const uint32_t* r_a,
+extern "C" int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int is_signed, int square, int k, const uint32_t* r_a,
                 int aw, const uint32_t* r_b, int bw, int ew, uint32_t* e, uint32_t* R, uint32_t* S, uint64_t count) {
   if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_dot_prep: bad argument");
   DotLayout lay;
@@ -158,7 +149,7 @@ int sc_dot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, 
   return SC_OK;
 }
 
-int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int square, int k, const uint32_t* p, uint32_t* D,
+extern "C" int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx, int wy, int square, int k, const uint32_t* p, uint32_t* D,
                  uint32_t* bad, uint64_t count) {
   if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_dot_split: bad argument");
   DotLayout lay;
@@ -171,10 +162,7 @@ int sc_dot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int wx,
 }
 
 // ---- secure one-hot encoding: the plaintext-word kernels of the two players (k_onehot_prep / _split / _rotate) ---------
-// OnehotLayout.__post_init__ (lookup.py) on the host -- the one copy of the fit rule every one-hot entry checks before it launches
-// anything: a field of f = ib + kappa + 1 bits must fit, f < bits(N) - 1; then g = floor((bits(N) - 2) / f) >= 1 fields per message.
-// Every refusal names its quantity.
-static int onehot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int ib, int k, int m, OnehotLayout* lay) {
+int sc_host::onehot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, int ib, int k, int m, OnehotLayout* lay) {
   if (kappa < 1 || kappa > 62) return fail(ctx, SC_ERR_ARG, "%s: kappa = %d: expected 1 <= kappa <= 62", who, kappa);
   if (ib < 1 || ib > 32) return fail(ctx, SC_ERR_ARG, "%s: ib = %d: expected an index width of 1 .. 32 bits", who, ib);
   if (k < 1 || k > ONEHOT_MAX_K) return fail(ctx, SC_ERR_ARG, "%s: k = %d: expected a table length of 1 .. %d", who, k, ONEHOT_MAX_K);
@@ -187,19 +175,18 @@ static int onehot_layout(sc_ctx* ctx, const char* who, int nbits_n, int kappa, i
   lay->M = (m + lay->g - 1) / lay->g;
   return SC_OK;
 }
-// the launches number their rows in 32 bits
-static int onehot_rows(sc_ctx* ctx, const char* who, int k, int m, uint64_t count) {
+int sc_host::onehot_rows(sc_ctx* ctx, const char* who, int k, int m, uint64_t count) {
   if (count > (uint64_t)0x7fffffff / ((uint64_t)k * m))
     return fail(ctx, SC_ERR_ARG, "%s: m k count = %d * %d * %llu rows: expected fewer than 2^31", who, m, k, (unsigned long long)count);
   return SC_OK;
 }
-static int onehot_mask_words(sc_ctx* ctx, const char* who, const OnehotLayout& lay, int rw) {
+int sc_host::onehot_mask_words(sc_ctx* ctx, const char* who, const OnehotLayout& lay, int rw) {
   if (rw < lay.rw) return fail(ctx, SC_ERR_ARG, "%s: draw rows of %d words are too narrow for %d bits", who, rw, lay.ib + lay.kappa);
   if (rw > ONEHOT_FIELD_WORDS) return fail(ctx, SC_ERR_ARG, "%s: draw rows of %d words: expected at most %d", who, rw, ONEHOT_FIELD_WORDS);
   return SC_OK;
 }
 
-int sc_onehot_layout(int nbits_n, int kappa, int ib, int k, int m, int* out) {
+extern "C" int sc_onehot_layout(int nbits_n, int kappa, int ib, int k, int m, int* out) {
   OnehotLayout lay;
   if (!out) return SC_ERR_ARG;
   int rc = onehot_layout(nullptr, "sc_onehot_layout", nbits_n, kappa, ib, k, m, &lay); if (rc) return rc;
@@ -207,7 +194,7 @@ int sc_onehot_layout(int nbits_n, int kappa, int ib, int k, int m, int* out) {
   return SC_OK;
 }
 
-int sc_onehot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* r, int rw, uint32_t* R,
+extern "C" int sc_onehot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* r, int rw, uint32_t* R,
                    int32_t* rot, uint64_t count) {
   if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_onehot_prep: bad argument");
   OnehotLayout lay;
@@ -221,7 +208,7 @@ int sc_onehot_prep(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int i
   return SC_OK;
 }
 
-int sc_onehot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* p, uint32_t* prod,
+extern "C" int sc_onehot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int ib, int k, int m, const uint32_t* p, uint32_t* prod,
                     uint32_t* bad, uint64_t count) {
   if (!ctx || !n_hptr || nw <= 0) return fail(ctx, SC_ERR_ARG, "sc_onehot_split: bad argument");
   OnehotLayout lay;
@@ -234,9 +221,7 @@ int sc_onehot_split(sc_ctx* ctx, const uint32_t* n_hptr, int nw, int kappa, int 
   return SC_OK;
 }
 
-// out [m][k][count][words] from e [m][k][count][words] and rot [m][count]; the two arrays must not overlap: a row of out is read from
-// another row of e
-static int onehot_rotate(sc_ctx* ctx, const char* who, int words, int k, int m, const uint32_t* e, const int32_t* rot, uint32_t* out, uint64_t count) {
+int sc_host::onehot_rotate(sc_ctx* ctx, const char* who, int words, int k, int m, const uint32_t* e, const int32_t* rot, uint32_t* out, uint64_t count) {
   const uint64_t total = (uint64_t)m * k * count * words;
   if (out < e + total && e < out + total) return fail(ctx, SC_ERR_ARG, "%s: out overlaps e: the rotation is not done in place", who);
   if (count == 0) return SC_OK;
@@ -244,7 +229,7 @@ static int onehot_rotate(sc_ctx* ctx, const char* who, int words, int k, int m, 
   return SC_OK;
 }
 
-int sc_onehot_rotate(sc_ctx* ctx, int words, int k, int m, const uint32_t* e, const int32_t* rot, uint32_t* out, uint64_t count) {
+extern "C" int sc_onehot_rotate(sc_ctx* ctx, int words, int k, int m, const uint32_t* e, const int32_t* rot, uint32_t* out, uint64_t count) {
   if (!ctx || words < 1) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: bad argument");
   if (k < 1 || k > ONEHOT_MAX_K) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: k = %d: expected a table length of 1 .. %d", k, ONEHOT_MAX_K);
   if (m < 1 || m > ONEHOT_MAX_M) return fail(ctx, SC_ERR_ARG, "sc_onehot_rotate: m = %d: expected 1 .. %d indices per row", m, ONEHOT_MAX_M);
@@ -257,7 +242,7 @@ int sc_onehot_rotate(sc_ctx* ctx, int words, int k, int m, const uint32_t* e, co
 // The nf columns run as flat items (nf * count of them), so the program does not depend on nf and an index row entry is read at the
 // item's flat number.  Per item, with V = U^-1 R^3 (one product, shared by both outputs): hi = F ab ab V / R^3 = F ab^2 U^-1 and
 // lo = G T T V / R^3 = G T^2 U^-1 -- seven Montgomery products on operands loaded once.
-int sc_select_finish_cx(sc_ctx* ctx, int mod, int nfields, const uint32_t* t, const uint32_t* ab, const uint32_t* u_inv, const uint32_t* f,
+extern "C" int sc_select_finish_cx(sc_ctx* ctx, int mod, int nfields, const uint32_t* t, const uint32_t* ab, const uint32_t* u_inv, const uint32_t* f,
                         const uint32_t* g, const uint64_t* lo_index, const uint64_t* hi_index, uint32_t* out, uint64_t out_rows,
                         uint64_t count) {
   if (ctx && count == 0) return SC_OK;

@@ -1,17 +1,17 @@
-// Host-side internals shared by the translation units of libsc_amd.so: set-up-time integers, the registered objects of a context
-// (moduli, exponents, constants, tables, programs), the context itself, the one launch body of the one-wave-per-workgroup kernels
-// (launch_waves) and what the kernel translation units export: one look-up of its instances per part of the two interpreters, a
-// launch entry point per kernel elsewhere.  The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
+// What every translation unit of libsc_amd.so shares: the registered objects of a context (moduli, exponents, constants, tables,
+// programs), the context itself, the one launch body of the one-wave-per-workgroup kernels (launch_waves) and what the kernel
+// translation units export: one look-up of its instances per part of the two interpreters, a launch entry point per kernel elsewhere.
+// The kernels are instantiated in sc_launch_vm.hip / sc_launch_pvm.hip (three parts each, compiled in parallel),
 // sc_launch_misc.hip (with sc_kernel_plain.h), sc_launch_mul.hip, sc_launch_dot.hip, sc_launch_lookup.hip (each family's plain-word kernels
 // in its own unit, the helpers they share in sc_plain_words.h), sc_launch_reduce.hip, sc_launch_scan.hip and
-// sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h); sc_lib.hip (+ sc_families.h, sc_schemes.h, and sc_axis_plan.h,
-// the HIP-free plans and checks of the two axis entries, and sc_pack_plan.h, the HIP-free field lists of the four pack entries) holds no device code, so a change of host logic rebuilds in seconds.
+// sc_launch_lin.hip (the last three share their instance list and launcher, sc_launch_axis.h).  The host units (sc_lib.hip, sc_families.hip,
+// sc_schemes.hip, sc_topk.hip) hold no device code; what they share among
+// themselves is declared in sc_host.h, their set-up-time integers are sc_bigint.h, and a change of host logic rebuilds the units it
+// touches, in seconds each.  Everything here has a name with linkage -- no unnamed namespace -- so that sc_ctx is one type in every unit.
 // sc_route.h, included here, is the HIP-free list of the interpreters' instances, with their launch keys, and the policy that picks the
 // instance of a launch: configurations, fit rule, twins.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <sys/random.h>
 
 #include <algorithm>
 #include <atomic>
@@ -39,97 +39,16 @@
 #define SC_PVM_WAVES 2    // waves per SIMD the pair interpreter is compiled for (sc_kernel_pvm.h)
 #endif
 
-namespace {
-using namespace sc;
-
-// ------------------------------------------------------------------------------------------------
-// tiny host big-integer helpers on little-endian uint32 word vectors (setup-time only)
-// ------------------------------------------------------------------------------------------------
-typedef std::vector<uint32_t> Big;
-
-int big_bits(const Big& a) {
-  for (int i = (int)a.size() - 1; i >= 0; i--)
-    if (a[i]) return 32 * i + (32 - __builtin_clz(a[i]));
-  return 0;
-}
-int big_cmp(const Big& a, const Big& b) {  // same length
-  for (int i = (int)a.size() - 1; i >= 0; i--)
-    if (a[i] != b[i]) return a[i] > b[i] ? 1 : -1;
-  return 0;
-}
-void big_sub(Big& a, const Big& b) {  // a -= b, same length
-  uint64_t borrow = 0;
-  for (size_t i = 0; i < a.size(); i++) {
-    uint64_t v = (uint64_t)a[i] - b[i] - borrow;
-    a[i] = (uint32_t)v;
-    borrow = (v >> 32) & 1;
-  }
-}
-// a = 2a mod n  (a < n, a and n have the same length with one spare top word)
-void big_dbl_mod(Big& a, const Big& n) {
-  uint32_t carry = 0;
-  for (size_t i = 0; i < a.size(); i++) {
-    uint32_t nc = a[i] >> 31;
-    a[i] = (a[i] << 1) | carry;
-    carry = nc;
-  }
-  if (big_cmp(a, n) >= 0) big_sub(a, n);
-}
-// x * 2^k mod n
-Big big_shl_mod(const Big& x, const Big& n, int k) {
-  Big nn = n; nn.push_back(0);
-  Big v = x; v.resize(nn.size(), 0);
-  while (big_cmp(v, nn) >= 0) big_sub(v, nn);
-  for (int i = 0; i < k; i++) big_dbl_mod(v, nn);
-  v.resize(n.size());
-  return v;
-}
-Big big_trimmed_words(Big a) { while (a.size() > 1 && a.back() == 0) a.pop_back(); return a; }
-Big big_mul(const Big& a, const Big& b) {  // schoolbook product (set-up time only)
-  Big r(a.size() + b.size(), 0);
-  for (size_t i = 0; i < a.size(); i++) {
-    uint64_t carry = 0;
-    for (size_t j = 0; j < b.size(); j++) {
-      uint64_t v = (uint64_t)a[i] * b[j] + r[i + j] + carry;
-      r[i + j] = (uint32_t)v;
-      carry = v >> 32;
-    }
-    r[i + b.size()] = (uint32_t)carry;
-  }
-  return r;
-}
-// x = q * m + rem by restoring division, bit by bit (set-up time only); q has x.size() words, rem m.size() words
-void big_divmod(const Big& x, const Big& m, Big* q, Big* rem) {
-  Big r(m.size() + 1, 0), mm = m; mm.push_back(0);
-  q->assign(x.size(), 0);
-  for (int bit = 32 * (int)x.size() - 1; bit >= 0; bit--) {
-    uint32_t carry = (x[bit >> 5] >> (bit & 31)) & 1;
-    for (size_t i = 0; i < r.size(); i++) { uint32_t nc = r[i] >> 31; r[i] = (r[i] << 1) | carry; carry = nc; }
-    if (big_cmp(r, mm) >= 0) { big_sub(r, mm); (*q)[bit >> 5] |= 1u << (bit & 31); }
-  }
-  r.resize(m.size());
-  *rem = r;
-}
-std::vector<uint32_t> to_limbs(const Big& x, int S, int W) {
-  std::vector<uint32_t> out(S, 0);
-  const uint32_t mask = (1u << W) - 1;
-  for (int i = 0; i < S; i++) {
-    int bit = W * i, w0 = bit >> 5, sh = bit & 31;
-    uint64_t v = (w0 < (int)x.size()) ? x[w0] : 0;
-    if (w0 + 1 < (int)x.size()) v |= (uint64_t)x[w0 + 1] << 32;
-    out[i] = (uint32_t)(v >> sh) & mask;
-  }
-  return out;
-}
+namespace sc_host {
 
 struct Mod {
   int G = 0, L = 0, W = 29, S = 0, nwords = 0, nbits = 0;
-  Big n;
+  std::vector<uint32_t> n;     // little-endian words (sc_bigint.h: Big)
   uint32_t n0inv = 0;
   uint32_t small_c = 0, small_cinv = 0;   // a modulus multiple M = c n (neg1_twin): c and c^-1 mod 2^W, else 0
   uint32_t* d_ctx = nullptr;  // n | R^2 | R  limb form
 };
-struct Exp { Big e; int bits = 0; };
+struct Exp { std::vector<uint32_t> e; int bits = 0; };
 struct Const { int mod = -1; uint32_t* d_limbs = nullptr; };
 // the rows of a fixed-base table are shared between contexts (sc_fbt_import): freed when the last table that uses them goes
 struct FbtRows {
@@ -139,17 +58,17 @@ struct FbtRows {
 struct Fbt { int mod = -1, window = 0, nwin = 0, exp_bits = 0; uint32_t* d_rows = nullptr; std::shared_ptr<FbtRows> rows; };
 struct Prog {
   uint32_t nops = 0, nscratch = 1, nconst = 0;
-  VmOp* d_ops = nullptr;
+  sc::VmOp* d_ops = nullptr;
   uint32_t* d_consts = nullptr;
   double muls_per_item = 0;   // Montgomery products (full) per item
   double redcs_per_item = 0;  // reduction-only passes per item
   double sqrs_per_item = 0;   // squarings (a*a part costs L(L+1)/2 per block instead of L^2)
-  std::shared_ptr<std::vector<VmOp>> host_ops;   // the micro-ops on the host (pair programs: cut into segments on demand)
+  std::shared_ptr<std::vector<sc::VmOp>> host_ops;   // the micro-ops on the host (pair programs: cut into segments on demand)
   uint32_t pair_sqrs = 0, pair_muls = 0;         // pair programs: pair squarings / pair products per item (the hold-time model)
   bool pair_dig = false;                         // pair programs with PV_MULTDIG: run on the k_pvm<.., DIG> instances
 };
 
-}  // namespace
+}  // namespace sc_host
 
 struct sc_ctx {
   int device = 0;
@@ -158,12 +77,12 @@ struct sc_ctx {
   int num_cu = 256;
   std::string err;
   int64_t last_bad_index = -1;                              // the element named by the last SC_ERR_NOT_INVERTIBLE (sc_last_bad_index)
-  std::vector<Mod> mods;
-  std::vector<Exp> exps;
-  std::vector<Const> consts;
-  std::vector<Fbt> fbts;
-  std::map<std::string, Prog> progs;
-  std::map<std::string, std::vector<Prog>> seg_progs;   // pair programs cut into segments (sc_modexp_shared_sq)
+  std::vector<sc_host::Mod> mods;
+  std::vector<sc_host::Exp> exps;
+  std::vector<sc_host::Const> consts;
+  std::vector<sc_host::Fbt> fbts;
+  std::map<std::string, sc_host::Prog> progs;
+  std::map<std::string, std::vector<sc_host::Prog>> seg_progs;   // pair programs cut into segments (sc_modexp_shared_sq)
   uint32_t* scratch = nullptr;
   size_t scratch_bytes = 0;
   std::vector<void*> owned;
@@ -187,7 +106,7 @@ struct sc_ctx {
   std::map<std::pair<int, int>, int> twins;                 // (twin kind, mod) -> its twin context, -1 where it has none (sc_lib.hip: twin_of)
   std::map<int, uint32_t*> pair_consts;                     // mod -> 4 limb arrays: pair(R^2), pair(B R) for the pair arithmetic
   uint32_t* d_one = nullptr;                                // the word 1 (a broadcast operand: the table entry x^0 of sc_modexp_var_sq)
-  RngKey rng_key;                                           // ChaCha20 key of the context's generator (sc_rng_seed)
+  sc::RngKey rng_key;                                           // ChaCha20 key of the context's generator (sc_rng_seed)
   // fork / join inside one library call (AuxFork): independent halves of a small batch -- the p- and q-side of the key holder's CRT
   // -- run on a second stream of the context with its own scratch arena and temporaries
   hipStream_t aux_stream = nullptr;
@@ -201,7 +120,7 @@ struct sc_ctx {
   int* status_host[2] = {nullptr, nullptr};
   size_t status_cap[2] = {0, 0};
   int fork_mode = 1;                                        // sc_ctx_set_fork_mode: 0 never fork inside a call, 1 automatic (small batches), 2 always
-  void* scheme_keys = nullptr;                              // Paillier / DGK key objects of the scheme-level entry points (sc_schemes.h)
+  void* scheme_keys = nullptr;                              // Paillier / DGK key objects of the scheme-level entry points (sc_schemes.hip)
   bool rng_seeded = false;
   std::atomic<uint64_t> rng_call{0};                        // generator calls since seeding: part of every keystream's nonce (atomic: two
                                                             // host threads that ever share a context must never draw one (key, call) twice)

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "sc_plain_words.h"
+#include "sc_vm.h"
 
 namespace sc {
 

@@ -1,12 +1,13 @@
-// libsc_amd.so -- host side of the C ABI declared in include/sc_amd.h and include/sc_amd_dev.h.
-// Builds the micro-programs (sc_vm.h) for each batched operation and queues the launches; the kernels themselves are instantiated in
-// the sc_launch_*.hip translation units (sc_internal.h), so this file holds no device code.
-#include "sc_internal.h"
-#include "sc_axis_plan.h"
-#include "sc_pack_plan.h"
+// libsc_amd.so -- host side of the C ABI declared in include/sc_amd.h and include/sc_amd_dev.h: the context's life cycle and memory, the
+// runners of the micro-programs (sc_vm.h; the builders are in sc_host.h), the registration of moduli, exponents, constants and tables, the
+// modmul, modexp, fixed-base, Paillier raw and plain-word entries, the inversion, the axis entries, twins with the two calibrations and
+// the pair arithmetic, RCCL with the generator, the policy setters, stats and probes.  The other host units hold the families
+// (sc_families.hip), the schemes (sc_schemes.hip) and the top-m network (sc_topk.hip); what they use of this one is declared in sc_host.h;
+// the kernels are instantiated in the sc_launch_*.hip translation units (sc_internal.h), so no host unit holds device code.
+#include "sc_host.h"
 
-#include <functional>
-#include <type_traits>
+#include <dlfcn.h>
+#include <sys/random.h>
 
 using namespace sc;
 using namespace sc_host;
@@ -18,14 +19,7 @@ int fail(sc_ctx* ctx, int code, const char* fmt, ...) {
   if (ctx) ctx->err = buf;
   return code;
 }
-}  // namespace sc_host
 
-namespace {
-
-void free_scheme_keys(void* p);   // sc_schemes.h
-Big big_powmod(const Big& base, const Big& e, const Big& m);
-
-// every allocation selects the context's device first: the caller may have switched the thread's current device
 int dev_alloc(sc_ctx* ctx, size_t bytes, void** out) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 4));
@@ -41,9 +35,8 @@ int upload(sc_ctx* ctx, const void* h, size_t bytes, void** out) {
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return SC_OK;
 }
-}  // namespace
 // the scratch arena of the stream the context currently launches on (its own, or the forked one's: AuxFork)
-int sc_host::ensure_scratch(sc_ctx* ctx, size_t bytes, uint32_t** out) {
+int ensure_scratch(sc_ctx* ctx, size_t bytes, uint32_t** out) {
   uint32_t*& arena = ctx->in_aux ? ctx->scratch_aux : ctx->scratch;
   size_t& have = ctx->in_aux ? ctx->scratch_aux_bytes : ctx->scratch_bytes;
   if (bytes > have) {
@@ -56,10 +49,7 @@ int sc_host::ensure_scratch(sc_ctx* ctx, size_t bytes, uint32_t** out) {
   *out = arena;
   return SC_OK;
 }
-namespace {
 
-// Temporary device buffer `slot`, at least `bytes` large.  Buffers are reused by later calls: every kernel of a context
-// runs on one stream, so a later call cannot overtake an earlier one that still reads the buffer.
 int tmp_buf(sc_ctx* ctx, int slot, size_t bytes, void** out) {
   auto& e = ctx->tmp[slot + (ctx->in_aux ? 1000 : 0)];       // the forked stream's calls never share a temporary with the main one's
   if (e.second < bytes) {
@@ -72,108 +62,7 @@ int tmp_buf(sc_ctx* ctx, int slot, size_t bytes, void** out) {
   *out = e.first;
   return SC_OK;
 }
-// Fork / join inside one library call.  begin(): everything queued so far on the context's stream happens before the forked work;
-// until suspend() the context launches on its second stream (own scratch arena, own temporaries); after suspend() it is back on
-// its own stream, whose later launches run BESIDE the forked work; join(): the context's stream waits for the forked work.
-// (The forked half is queued first: an event recorded after the other half's launches would wait for them.)
-// Used for the q-side of the key holder's CRT when a launch of the batch leaves most of the chip idle.
-struct AuxFork {
-  sc_ctx* ctx = nullptr;
-  hipStream_t main = nullptr;
-  bool active = false, pending = false;
-  int begin(sc_ctx* c) {
-    ctx = c;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->aux_stream) {
-      HIPCHK(c, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-      HIPCHK(c, hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-      HIPCHK(c, hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-    }
-    HIPCHK(c, hipEventRecord(c->aux_fork, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->aux_stream, c->aux_fork, 0));
-    main = c->stream;
-    c->stream = c->aux_stream;
-    c->in_aux = true;
-    active = true;
-    return SC_OK;
-  }
-  int suspend() {
-    if (!active) return SC_OK;
-    active = false;
-    sc_ctx* c = ctx;
-    const hipError_t e1 = hipEventRecord(c->aux_join, c->aux_stream);
-    c->stream = main;
-    c->in_aux = false;
-    if (e1 != hipSuccess) return fail(c, SC_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(e1));
-    pending = true;
-    return SC_OK;
-  }
-  int join() {
-    int rc = suspend();
-    if (rc) return rc;
-    if (pending) { pending = false; HIPCHK(ctx, hipStreamWaitEvent(main, ctx->aux_join, 0)); }
-    return SC_OK;
-  }
-  ~AuxFork() { (void)join(); }      // error paths: never leave the context on its second stream, nor forked work unordered
-};
-// Times work enqueued on the context's stream between two events (created on first use); they are destroyed on every path.
-struct LaunchTimer {
-  sc_ctx* ctx;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  explicit LaunchTimer(sc_ctx* c) : ctx(c) {}
-  // *ms = the time of what `enqueue` queues (it returns SC_OK or an error code, which is passed on), waited for
-  template <class F> int time(F&& enqueue, float* ms) {
-    if (!e0) HIPCHK(ctx, hipEventCreate(&e0));
-    if (!e1) HIPCHK(ctx, hipEventCreate(&e1));
-    HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-    int rc = enqueue(); if (rc) return rc;
-    HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-    HIPCHK(ctx, hipEventSynchronize(e1));
-    HIPCHK(ctx, hipEventElapsedTime(ms, e0, e1));
-    return SC_OK;
-  }
-  ~LaunchTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-// A measurement runs under a launch policy of its own and stays out of the MAC counter: the context's settings are restored on every
-// exit path.
-struct PolicyOverride {
-  sc_ctx* ctx;
-  const int latency_mode, onelane_mode, chip_share;
-  const double mac_counter;
-  explicit PolicyOverride(sc_ctx* c)
-      : ctx(c), latency_mode(c->latency_mode), onelane_mode(c->onelane_mode), chip_share(c->chip_share), mac_counter(c->mac_counter) {}
-  ~PolicyOverride() {
-    ctx->latency_mode = latency_mode; ctx->onelane_mode = onelane_mode; ctx->chip_share = chip_share; ctx->mac_counter = mac_counter;
-  }
-};
-// a device buffer of a measurement, freed on every exit path
-template <class T> struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-// Should the two CRT halves of a call run side by side on two streams?  Small batches: when a second, independent launch fits
-// beside the first (a wave per SIMD for both: half of the chip's 4 x CUs SIMDs each; off with latency mode 0).  Large ones: when
-// this context has the chip to itself.
-inline bool small_enough_to_fork(const sc_ctx* ctx, const Mod& m, uint64_t count) {
-  if (ctx->fork_mode == 0 || ctx->in_aux) return false;
-  if (ctx->fork_mode == 2) return true;                     // always: the two halves' launches beside each other whatever the batch size
-  // a context that has the chip to itself: the halves' launches side by side pack their partial rounds (three launches of 1.5
-  // rounds each are 2 rounds long one after the other) -- single-stream step 381.1 -> 377.2 ms at B = 65536; with concurrent
-  // shards the other shard's launches fill those rounds already and forking costs 1 % (profiles/r04_fork_modes.txt)
-  if (ctx->chip_share == 1 && ctx->latency_mode != 2) {
-    const uint64_t per_wave_full = std::max(1, 64 / m.G);
-    if ((count + per_wave_full - 1) / per_wave_full > (uint64_t)ctx->num_cu * 4) return true;
-  }
-  if (ctx->latency_mode == 0) return false;
-  if (ctx->latency_mode == 2) return true;
-  const uint64_t per_wave = std::max(1, 64 / (2 * m.G));     // in the small-batch configuration this batch would take
-  return (count + per_wave - 1) / per_wave <= (uint64_t)ctx->num_cu * 4 / (uint64_t)ctx->chip_share;
-}
 
-enum TmpSlot { TMP_PARK = 1, TMP_ANYFLAG = 2, TMP_CRT = 3, TMP_PAIR = 4, TMP_INV_MEMBERS = 5, TMP_REDUCE = 6, TMP_SCAN = 7, TMP_LIN = 8, TMP_INV_BASE = 16 /* + 2*depth, + 2*depth+1 */ };
-
-// A u64 accumulator array of the context that is ZERO whenever no step is using it: cleared when it is (re)allocated, reset by its
-// reader afterwards (OP_TAKEFLAG).  The zero tests of step 4j OR their verdicts into it; no clearing launch inside a step.
 int zero_kept_flags(sc_ctx* ctx, uint64_t count, uint64_t** out) {
   auto& e = ctx->tmp[TMP_ANYFLAG + (ctx->in_aux ? 1000 : 0)];
   const size_t bytes = (size_t)count * sizeof(uint64_t);
@@ -194,7 +83,6 @@ void drop_zero_kept_flags(sc_ctx* ctx) {      // forget the accumulator: the nex
   if (e.first) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(e.first); e.first = nullptr; e.second = 0; }
 }
 
-// `count` verdict words in pinned, device-visible host memory (grow-only, per stream of the context)
 int status_words(sc_ctx* ctx, size_t count, int** out) {
   const int s = ctx->in_aux ? 1 : 0;
   if (ctx->status_cap[s] < count) {
@@ -208,7 +96,6 @@ int status_words(sc_ctx* ctx, size_t count, int** out) {
   return SC_OK;
 }
 
-// device copy of n | (n-1)/2 as canonical words (plain-word kernels)
 int device_n_half(sc_ctx* ctx, const uint32_t* n_hptr, int nw, uint32_t** out) {
   std::vector<uint32_t> n(n_hptr, n_hptr + nw);
   auto it = ctx->nwords_cache.find(n);
@@ -223,115 +110,6 @@ int device_n_half(sc_ctx* ctx, const uint32_t* n_hptr, int nw, uint32_t** out) {
   return SC_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// program builders: every micro-op is emitted, and its cost counted, by one of these
-// ------------------------------------------------------------------------------------------------
-// k_vm programs.  Constants: LDS 0 = R^2, 1 = R, 2.. = the extra constants of use_const.
-struct Builder {
-  std::vector<VmOp> ops;
-  std::vector<int> consts;  // extra constant ids (LDS index = 2 + position)
-  int use_const(int cid) {
-    for (size_t i = 0; i < consts.size(); i++) if (consts[i] == cid) return 2 + (int)i;
-    consts.push_back(cid);
-    return 2 + (int)consts.size() - 1;
-  }
-  void mul_const(int lds_idx) { emit(OP_MUL, AK_CONST, 0, lds_idx); muls++; }
-  // times LDS constant lds0 where the item's byte in ext is 0, else lds1
-  void mul_constsel(int ext, int lds0, int lds1) { emit(OP_MUL, AK_CONSTSEL, 0, ext, (uint32_t)lds0 | ((uint32_t)lds1 << 8)); muls++; }
-  void sqr() {   // consecutive squarings merge into one micro-op with a repeat count (imm, 16 bits)
-    sqrs++;
-    if (!ops.empty()) {
-      VmOp& last = ops.back();
-      const uint32_t imm = last.w0 >> 16;
-      if ((last.w0 & 0xffff) == (OP_MUL | (AK_ACC << 8)) && imm >= 1 && imm < 0xffff) { last.w0 += 1u << 16; return; }
-    }
-    emit(OP_MUL, AK_ACC, 1);
-  }
-  void mul_tbl(uint32_t e) { touch(e); emit(OP_MUL, AK_TBL, 0, e); muls++; }
-  void mul_tblsel(int extA, int bitA, int extB, int bitB, uint32_t e00, uint32_t e01, uint32_t e10, uint32_t e11) {
-    touch(std::max(std::max(e00, e01), std::max(e10, e11)));
-    emit(OP_MUL, AK_TBLSEL, 0, extA | (bitA << 4) | (extB << 12) | (bitB << 16), e00 | (e01 << 8) | (e10 << 16) | (e11 << 24));
-    muls++;
-  }
-  void mul_tbldig(int ext, uint32_t bitpos, uint32_t width, uint32_t base) {
-    touch(base + (1u << width) - 1);
-    emit(OP_MUL, AK_TBLDIG, 0, ext | (bitpos << 4) | (width << 24), base); muls++;
-  }
-  void mul_fbt(int ext, uint32_t bitpos, uint32_t width, uint32_t win) { emit(OP_MUL, AK_FBT, 0, ext | (bitpos << 4) | (width << 24), win); muls++; }
-  void mul_extw(int ext, uint32_t off = 0) { emit(OP_MUL, AK_EXTW, 0, ext, off); muls++; }
-  void mul_extl(int ext, uint32_t off = 0) { emit(OP_MUL, AK_EXTL, 0, ext, off); muls++; }
-  void loadw(int ext, uint32_t off = 0, uint32_t woff = 0, uint32_t nw = 0) { emit(OP_LOADW, 0, 0, ext, off, (woff << 16) | nw); }
-  // ext_set where bit `bit` (0 .. 255) of the item's flag row (ext flag_ext) is set, else ext_clear (sc_vm.h)
-  void loadw_sel(int ext_set, int ext_clear, int flag_ext, int bit, uint32_t off = 0) { emit(OP_LOADW, 0, 1, ext_set | (ext_clear << 4) | (flag_ext << 8) | (bit << 12), off); }
-  void add1() { emit(OP_ADD1); }
-  void add_flag(int flag_ext, int bit, bool invert) { emit(OP_ADD1, 0, 1, flag_ext | (bit << 4) | ((invert ? 1 : 0) << 12)); }
-  void sub1() { emit(OP_SUB1); }
-  void neg() { emit(OP_NEG); }
-  void quot() { emit(OP_QUOT); redcs++; }
-  void addw(int ext, uint32_t off = 0, uint32_t woff = 0, uint32_t nw = 0) { emit(OP_ADDW, 0, 0, ext, off, (woff << 16) | nw); }
-  void loadt_const(int lds_idx) { emit(OP_LOADT, AK_CONST, 0, lds_idx); }
-  void loadt_tbl(uint32_t e) { touch(e); emit(OP_LOADT, AK_TBL, 0, e); }
-  void loadt_tbldig(int ext, uint32_t bitpos, uint32_t width, uint32_t base) {
-    touch(base + (1u << width) - 1);
-    emit(OP_LOADT, AK_TBLDIG, 0, ext | (bitpos << 4) | (width << 24), base);
-  }
-  void loadt_tblsel(int extA, int bitA, int extB, int bitB, uint32_t e00, uint32_t e01, uint32_t e10, uint32_t e11) {
-    touch(std::max(std::max(e00, e01), std::max(e10, e11)));
-    emit(OP_LOADT, AK_TBLSEL, 0, extA | (bitA << 4) | (extB << 12) | (bitB << 16), e00 | (e01 << 8) | (e10 << 16) | (e11 << 24));
-  }
-  void loadt_fbt(int ext, uint32_t bitpos, uint32_t width, uint32_t win) { emit(OP_LOADT, AK_FBT, 0, ext | (bitpos << 4) | (width << 24), win); }
-  void loadt_extl(int ext, uint32_t off = 0) { emit(OP_LOADT, AK_EXTL, 0, ext, off); }
-  // ACC = the u64 accumulator ext_acc[item], which is reset to 0; the value also goes to ext_copy[item] (sc_vm.h)
-  void takeflag(int ext_acc, int ext_copy) { emit(OP_TAKEFLAG, 0, 0, ext_acc, ext_copy); }
-  void stt(uint32_t e) { touch(e); emit(OP_STT, 0, e); }
-  void addt(uint32_t e) { touch(e); emit(OP_ADDT, 0, e); }
-  void redc(bool times_c = false) { emit(OP_REDC, 0, times_c ? 1 : 0); redcs++; }     // times_c / over_c: leaving a modulus-multiple context (sc_vm.h)
-  void storew(int ext, uint32_t off = 0, bool over_c = false) { emit(OP_STOREW, 0, over_c ? 1 : 0, ext, off); }
-  void storew_at(int ext, int ext_index, bool over_c = false, bool by_perm = false) {   // row = ext_index[item] (u64), or from a batch of permutations (sc_vm.h)
-    emit(OP_STOREW, 0, (over_c ? 1 : 0) | (by_perm ? 2 : 0), ext, 0, 1 + ext_index);
-  }
-  void storel(int ext, uint32_t off = 0) { emit(OP_STOREL, 0, 0, ext, off); }
-  // or_group: OR the verdict into the item's group flag (u64) instead of storing a byte
-  void storeflag(int ext, uint32_t off, int lds_const, bool or_group = false) { emit(OP_STOREFLAG, 0, or_group ? 1 : 0, ext, off, lds_const); }
-  // ends the program and uploads it with its constants for modulus `mod`
-  int finalize(sc_ctx* ctx, int mod, Prog* out) {
-    emit(OP_END);
-    if (consts.size() + 2 > VM_MAX_CONST) return fail(ctx, SC_ERR_ARG, "too many constants in program");
-    const Mod& m = ctx->mods[mod];
-    Prog p;
-    p.nops = (uint32_t)ops.size();
-    p.nscratch = nscratch;
-    p.nconst = (uint32_t)consts.size();
-    p.muls_per_item = muls;
-    p.redcs_per_item = redcs;
-    p.sqrs_per_item = sqrs;
-    int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops);
-    if (rc) return rc;
-    if (p.nconst) {
-      rc = dev_alloc(ctx, (size_t)p.nconst * m.S * 4, (void**)&p.d_consts);
-      if (rc) return rc;
-      for (uint32_t i = 0; i < p.nconst; i++)
-        HIPCHK(ctx, hipMemcpyAsync(p.d_consts + (size_t)i * m.S, ctx->consts[consts[i]].d_limbs, (size_t)m.S * 4,
-                                   hipMemcpyDeviceToDevice, ctx->stream));   // stream-ordered before the program's first launch
-    }
-    *out = p;
-    return SC_OK;
-  }
-
- private:
-  uint32_t nscratch = 1;
-  double muls = 0, redcs = 0, sqrs = 0;
-  void touch(uint32_t e) { nscratch = std::max(nscratch, e + 1); }
-  void emit(uint32_t opc, uint32_t ak = 0, uint32_t imm = 0, uint32_t w1 = 0, uint32_t w2 = 0, uint32_t w3 = 0) {
-    ops.push_back(VmOp{opc | (ak << 8) | (imm << 16), w1, w2, w3});
-  }
-};
-
-// the encoding of one k_pvm micro-op (PairBuilder, and the segment cutter of sc_modexp_shared_sq)
-inline VmOp pv_op(uint32_t opc, uint32_t w1 = 0, uint32_t w2 = 0, uint32_t w3 = 0) { return VmOp{opc, w1, w2, w3}; }
-
-// Limb-form constant pairs of a modulus m for the pair arithmetic: pair(R^2) embeds an integer (u,0) -> u; pair(B R) is
-// the radix B = 2^(32 nwords) of the operand chunks.  Each pair (c0, c1) satisfies c0 + c1 m = value (mod m^2), c0, c1 < m.
 int get_pair_consts(sc_ctx* ctx, int mod, uint32_t** out) {
   auto it = ctx->pair_consts.find(mod);
   if (it != ctx->pair_consts.end()) { *out = it->second; return SC_OK; }
@@ -355,77 +133,14 @@ int get_pair_consts(sc_ctx* ctx, int mod, uint32_t** out) {
   return SC_OK;
 }
 
-// k_pvm programs.  Constants: LDS 2,3 = pair(R^2), 4,5 = pair(B R) (get_pair_consts).  Pair entry e of the table is limb-form
-// entries 2e and 2e + 1.  Costs: muls_per_item carries the exact multiply-adds per item -- a pair squaring is (a*a part) + 3 S^2,
-// a pair product 5 S^2 with the two-row pass, 6 S^2 in the one-lane form (three single passes over one staging area).
-struct PairBuilder {
-  std::vector<VmOp> ops;
-  explicit PairBuilder(const Mod& m)
-      : one_lane(m.G == 1), S2((double)m.S * m.S), SQ(S2 + (double)m.G * m.G * m.L * (m.L + 1) / 2.0 + 2.0 * S2),
-        MU((m.G == 1 ? 6.0 : 5.0) * S2) {}
-  // ACC0 = words ext[ext] (row `row` of a [rows][count] operand, word offset woff, nw words), ACC1 = 0
-  void loadu(int ext, uint32_t woff, uint32_t nw, uint32_t row = 0) { ops.push_back(pv_op(PV_LOADU, ext, row, (woff << 16) | nw)); }
-  void mul_const(uint32_t lds_idx) { ops.push_back(pv_op(PV_MULC, lds_idx)); macs += MU; muls++; }
-  void sqr() { ops.push_back(pv_op(PV_SQR)); macs += SQ; sqrs++; }
-  void mul_tbl(uint32_t e) { touch(e); ops.push_back(pv_op(PV_MULT, e)); macs += MU; muls++; }
-  // pair *= entry base + digit, the digit `width` bits at `bitpos` of the item's row in ext (k_pvm<.., DIG> instances only)
-  void mul_tbl_digit(int ext, uint32_t bitpos, uint32_t width, uint32_t base) {
-    touch(base + (1u << width) - 1); dig = true;
-    ops.push_back(pv_op(PV_MULTDIG, ext | (bitpos << 4) | (width << 24), base)); macs += MU; muls++;
-  }
-  void loadt_tbl(uint32_t e) { touch(e); ops.push_back(pv_op(PV_LOADT, e)); }
-  void stt(uint32_t e) { touch(e); ops.push_back(pv_op(PV_STT, e)); }
-  void addt(uint32_t e) { touch(e); ops.push_back(pv_op(PV_ADDT, e)); }
-  void out(int ext0, int ext1) { ops.push_back(pv_op(PV_OUT, ext0, ext1)); macs += 2.0 * S2; }
-  // ends the program and uploads it; the host copy of the ops stays with it (segments are cut from it on demand)
-  int finalize(sc_ctx* ctx, int mod, Prog* out) {
-    ops.push_back(pv_op(PV_END));
-    Prog p;
-    // one-lane pair products park an intermediate in a spare row (the last one) of the slot's table
-    p.nops = (uint32_t)ops.size(); p.nscratch = nscratch + (one_lane ? 1 : 0); p.nconst = 4; p.muls_per_item = macs;
-    p.pair_sqrs = sqrs; p.pair_muls = muls; p.pair_dig = dig;
-    p.host_ops = std::make_shared<std::vector<VmOp>>(ops);
-    int rc = upload(ctx, ops.data(), ops.size() * sizeof(VmOp), (void**)&p.d_ops); if (rc) return rc;
-    rc = get_pair_consts(ctx, mod, &p.d_consts); if (rc) return rc;
-    *out = p;
-    return SC_OK;
-  }
-
- private:
-  bool one_lane;
-  double S2, SQ, MU, macs = 0;
-  uint32_t nscratch = 2, sqrs = 0, muls = 0;
-  bool dig = false;
-  void touch(uint32_t e) { nscratch = std::max(nscratch, 2 * e + 2); }
-};
-
-// The program cached under `key` in the context, or the one `build` emits into `bd`, finalized for modulus `mod` and cached.
-// `build` may return an error code, which is passed on (nothing is cached then).
-template <class F, class B = Builder>
-int cached_prog(sc_ctx* ctx, const std::string& key, int mod, F&& build, const Prog** out, B bd = B()) {
-  auto it = ctx->progs.find(key);
-  if (it == ctx->progs.end()) {
-    if constexpr (std::is_void_v<decltype(build(bd))>) build(bd);
-    else { int rc = build(bd); if (rc) return rc; }
-    Prog p; int rc = bd.finalize(ctx, mod, &p); if (rc) return rc;
-    it = ctx->progs.emplace(key, p).first;
-  }
-  *out = &it->second;
-  return SC_OK;
-}
-
-// what the instance policy (sc_route.h) is asked with: the switches of the context, and a modulus as it sees one
-inline Policy policy_of(const sc_ctx* ctx) { return {ctx->latency_mode, ctx->onelane_mode, ctx->chip_share, ctx->num_cu}; }
-inline Instance shape_of(const Mod& m) { return {m.G, m.L, m.W, m.n0inv == 1}; }
-
 // The row of an interpreter instance in the part that compiles it, or null.
-const KernelRow* find_instance(uint32_t key) {
+static const KernelRow* find_instance(uint32_t key) {
   for (auto part : {vm_part0, vm_part1, vm_part2, pvm_part0, pvm_part1, pvm_part2})
     if (const KernelRow* row = part(key)) return row;
   return nullptr;
 }
 
-int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uint64_t count, const uint32_t* fbt_rows = nullptr) {
+int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uint64_t count, const uint32_t* fbt_rows) {
   if (count == 0) return SC_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));  // the caller may have switched the current device since sc_ctx_create
   const Mod& m = ctx->mods[mod];
@@ -452,13 +167,11 @@ int run_vm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uin
   return row->launch(ctx, a);
 }
 
-// resident waves per CU of that instance (the runtime's occupancy answer, not a compiled-in assumption); <= 0 when there is none
 int pvm_occupancy(sc_ctx* ctx, int G, int L, bool neg1) {
   const KernelRow* row = find_instance(launch_key(true, G, L, kPairW, neg1, false, false));
   return row ? row->occupancy(ctx) : -1;
 }
 
-// pair programs: nscratch counts limb-form entries (2 per pair entry); macs = multiply-adds per item
 int run_pvm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, uint64_t count) {
   if (count == 0) return SC_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -482,13 +195,6 @@ int run_pvm(sc_ctx* ctx, int mod, const Prog& p, const VmExt* exts, int next, ui
   return row->launch(ctx, a);
 }
 
-VmExt mk_ext(const void* p, uint32_t stride, uint32_t nwords, uint64_t limit = ~0ull) {
-  VmExt e; e.ptr = p; e.stride = stride; e.nwords = nwords; e.limit = limit; return e;
-}
-
-bool valid_mod(sc_ctx* ctx, int mod) { return ctx && mod >= 0 && mod < (int)ctx->mods.size(); }
-
-// emit: ACC = (ext value reduced mod n), for an operand of x_words >= mod words (Horner over chunks)
 void emit_load_reduced(sc_ctx* ctx, const Mod& m, Builder& b, int ext, int x_words, int kred_lds) {
   const int cw = m.nwords;
   const int nch = (x_words + cw - 1) / cw;
@@ -512,43 +218,12 @@ int best_window(int bits) {
   }
   return best;
 }
-inline int ebit(const Big& e, int i) { return (e[i >> 5] >> (i & 31)) & 1; }
-
-// emit sliding-window exponentiation (ex.bits > 0) of the Montgomery-form value currently in the accumulator, with the table of odd
-// powers x^1, x^3, .. in entries T0, T0 + 1, .. and x^2 in the entry after them; leaves x^e.  Either builder (k_vm or k_pvm).
-template <class B>
-void emit_window_pow(B& b, const Exp& ex, uint32_t T0) {
-  const int bits = ex.bits;
-  const int w = best_window(bits);
-  const uint32_t NT = 1u << (w - 1);
-  b.stt(T0);
-  if (NT > 1) {
-    b.sqr(); b.stt(T0 + NT);
-    for (uint32_t k = 1; k < NT; k++) { b.loadt_tbl(T0 + k - 1); b.mul_tbl(T0 + NT); b.stt(T0 + k); }
-  }
-  bool first = true;
-  int i = bits - 1;
-  while (i >= 0) {
-    if (!ebit(ex.e, i)) { b.sqr(); i--; continue; }
-    int j = std::max(0, i - w + 1);
-    while (!ebit(ex.e, j)) j++;
-    int v = 0;
-    for (int k = i; k >= j; k--) v = (v << 1) | ebit(ex.e, k);
-    if (first) { b.loadt_tbl(T0 + (v - 1) / 2); first = false; }
-    else { for (int k = 0; k < i - j + 1; k++) b.sqr(); b.mul_tbl(T0 + (v - 1) / 2); }
-    i = j - 1;
-  }
-}
-
-// x^e of the Montgomery-form value in ACC, left in ACC (Montgomery form); x^0 is the constant 1
 void emit_pow_shared(Builder& b, const Exp& ex) {
   if (ex.bits == 0) b.loadt_const(1);
   else emit_window_pow(b, ex, 0);
 }
 
-int get_const_kred(sc_ctx* ctx, int mod, int* out_cid);
-
-}  // namespace
+}  // namespace sc_host
 
 // ================================================================================================
 // C ABI
@@ -642,15 +317,40 @@ int sc_memcpy_d2h(sc_ctx* ctx, void* hptr, const void* dptr, size_t bytes) {
   return SC_OK;
 }
 
-static int create_mod(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, bool for_pairs, int* out_mod, const Config* forced = nullptr);
-
 int sc_mod_create(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, int* out_mod) {
   return create_mod(ctx, n_hptr, nwords, false, out_mod);
 }
 
-// for_pairs: take the first configuration that has a pair kernel (used for the internal twin context of sc_modexp_shared_sq);
-// forced: this configuration or failure (the one-lane twin)
-static int create_mod(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, bool for_pairs, int* out_mod, const Config* forced) {
+int sc_mod_words(sc_ctx* ctx, int mod) { return valid_mod(ctx, mod) ? ctx->mods[mod].nwords : SC_ERR_ARG; }
+
+int sc_exp_create(sc_ctx* ctx, const uint32_t* e_hptr, int ewords, int* out_exp) {
+  if (!ctx || !e_hptr || ewords <= 0 || !out_exp) return fail(ctx, SC_ERR_ARG, "sc_exp_create: bad argument");
+  Exp e; e.e.assign(e_hptr, e_hptr + ewords); e.bits = big_bits(e.e);
+  ctx->exps.push_back(e);
+  *out_exp = (int)ctx->exps.size() - 1;
+  return SC_OK;
+}
+
+int sc_const_create(sc_ctx* ctx, int mod, const uint32_t* v_hptr, int nwords, int* out_const) {
+  if (!valid_mod(ctx, mod) || !v_hptr || !out_const) return fail(ctx, SC_ERR_ARG, "sc_const_create: bad argument");
+  const Mod& m = ctx->mods[mod];
+  Big v(v_hptr, v_hptr + nwords);
+  v.resize(std::max(nwords, m.nwords), 0);
+  Big nn = m.n; nn.resize(v.size(), 0);
+  Big vm = big_shl_mod(v, nn, m.W * m.S);  // Montgomery form
+  auto l = to_limbs(vm, m.S, m.W);
+  Const c; c.mod = mod;
+  int rc = upload(ctx, l.data(), l.size() * 4, (void**)&c.d_limbs);
+  if (rc) return rc;
+  ctx->consts.push_back(c);
+  *out_const = (int)ctx->consts.size() - 1;
+  return SC_OK;
+}
+
+}  // extern "C"
+
+namespace sc_host {
+int create_mod(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, bool for_pairs, int* out_mod, const Config* forced) {
   if (!ctx || !n_hptr || nwords <= 0 || !out_mod) return fail(ctx, SC_ERR_ARG, "sc_mod_create: bad argument");
   Mod m;
   m.n.assign(n_hptr, n_hptr + nwords);
@@ -682,36 +382,6 @@ static int create_mod(sc_ctx* ctx, const uint32_t* n_hptr, int nwords, bool for_
   return SC_OK;
 }
 
-int sc_mod_words(sc_ctx* ctx, int mod) { return valid_mod(ctx, mod) ? ctx->mods[mod].nwords : SC_ERR_ARG; }
-
-int sc_exp_create(sc_ctx* ctx, const uint32_t* e_hptr, int ewords, int* out_exp) {
-  if (!ctx || !e_hptr || ewords <= 0 || !out_exp) return fail(ctx, SC_ERR_ARG, "sc_exp_create: bad argument");
-  Exp e; e.e.assign(e_hptr, e_hptr + ewords); e.bits = big_bits(e.e);
-  ctx->exps.push_back(e);
-  *out_exp = (int)ctx->exps.size() - 1;
-  return SC_OK;
-}
-
-int sc_const_create(sc_ctx* ctx, int mod, const uint32_t* v_hptr, int nwords, int* out_const) {
-  if (!valid_mod(ctx, mod) || !v_hptr || !out_const) return fail(ctx, SC_ERR_ARG, "sc_const_create: bad argument");
-  const Mod& m = ctx->mods[mod];
-  Big v(v_hptr, v_hptr + nwords);
-  v.resize(std::max(nwords, m.nwords), 0);
-  Big nn = m.n; nn.resize(v.size(), 0);
-  Big vm = big_shl_mod(v, nn, m.W * m.S);  // Montgomery form
-  auto l = to_limbs(vm, m.S, m.W);
-  Const c; c.mod = mod;
-  int rc = upload(ctx, l.data(), l.size() * 4, (void**)&c.d_limbs);
-  if (rc) return rc;
-  ctx->consts.push_back(c);
-  *out_const = (int)ctx->consts.size() - 1;
-  return SC_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// registers the residue v (host words) as a constant of `mod` once per (mod, value)
 int sc_const_create_cached(sc_ctx* ctx, int mod, const Big& v, int* out_cid) {
   auto key = std::make_pair(mod, v);
   auto it = ctx->const_by_value.find(key);
@@ -723,7 +393,6 @@ int sc_const_create_cached(sc_ctx* ctx, int mod, const Big& v, int* out_cid) {
   *out_cid = cid;
   return SC_OK;
 }
-// Montgomery form of 2^(32 * nwords): multiplying by it shifts a residue up by one operand width
 int get_const_kred(sc_ctx* ctx, int mod, int* out_cid) {
   const Mod& m = ctx->mods[mod];
   auto it = ctx->kred_cache.find(mod);
@@ -737,7 +406,94 @@ int get_const_kred(sc_ctx* ctx, int mod, int* out_cid) {
   *out_cid = cid;
   return SC_OK;
 }
-}  // namespace
+
+int modexp_shared_impl(sc_ctx* ctx, int mod, int exp, const uint32_t* x, int x_words, const uint32_t* mul_into,
+                              uint32_t* out, uint8_t* flags, uint64_t count, uint64_t* any_flags, uint64_t inner, bool any_flags_clean) {
+  if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
+  if (!valid_mod(ctx, mod) || exp < 0 || exp >= (int)ctx->exps.size() || !x || (!out && !flags && !any_flags))
+    return fail(ctx, SC_ERR_ARG, "sc_modexp_shared: bad argument");
+  if (any_flags) {
+    if (inner == 0 || count % inner != 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_shared_isone_any: count must be a multiple of the inner count");
+    if (!any_flags_clean) HIPCHK(ctx, hipMemsetAsync(any_flags, 0, inner * sizeof(uint64_t), ctx->stream));
+  }
+  if (ctx->exps[exp].bits > 64) mod = onelane_for(ctx, mod, count);   // long exponentiations of a chip-filling batch: one-lane twin
+  const Mod& m = ctx->mods[mod];
+  if (x_words <= 0) x_words = m.nwords;
+  const int mode = any_flags ? 3 : (flags ? 2 : (mul_into ? 1 : 0));
+  std::string key = "mexp:" + std::to_string(mod) + ":" + std::to_string(exp) + ":" + std::to_string(x_words) + ":" + std::to_string(mode);
+  const Prog* p;
+  int rc = cached_prog(ctx, key, mod, [&](Builder& bd) -> int {
+    if (x_words > m.nwords) {
+      int kc; int rc = get_const_kred(ctx, mod, &kc); if (rc) return rc;
+      emit_load_reduced(ctx, m, bd, 0, x_words, bd.use_const(kc));
+    } else {
+      bd.loadw(0, 0, 0, x_words);
+    }
+    bd.mul_const(0);                   // to Montgomery form
+    emit_pow_shared(bd, ctx->exps[exp]);
+    if (mode == 0) { bd.redc(); bd.storew(1); }
+    else if (mode == 1) { bd.mul_extw(2); bd.storew(1); }
+    else bd.storeflag(1, 0, 1, mode == 3);             // compare with R mod n (Montgomery one); mode 3: OR the verdict into the item's group flag
+    return SC_OK;
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(x, x_words, x_words),
+                 any_flags ? mk_ext(any_flags, 0, 0, inner) : (flags ? mk_ext(flags, 0, 0) : mk_ext(out, m.nwords, m.nwords)),
+                 mk_ext(mul_into, m.nwords, m.nwords)};
+  return run_vm(ctx, mod, *p, ex, 3, count);
+}
+
+int modexp_var_impl(sc_ctx* ctx, int mod, const uint32_t* x, const uint32_t* e, int ewords, int ebits, int fbt,
+                           const uint32_t* e2, int e2words, const uint64_t* dest, uint32_t* out, uint64_t count,
+                           const uint32_t* premul, const int64_t* perm, uint32_t planes) {
+  if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
+  if (!valid_mod(ctx, mod) || !x || !e || !out || ewords <= 0 || ebits <= 0 || ebits > 32 * ewords)
+    return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad argument");
+  if (perm && (dest || planes == 0 || planes > SC_MAX_L + 1 || count % planes != 0)) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad permutation batch");
+  const Fbt* f = nullptr;
+  if (fbt >= 0) {
+    if (fbt >= (int)ctx->fbts.size() || ctx->fbts[fbt].mod != mod || !e2 || e2words <= 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad fixed-base table");
+    f = &ctx->fbts[fbt];
+  }
+  // chip-filling batches of a (4,18) modulus run in the context of its multiple M = c n = -1 (mod 2^29) (no quotient multiply per
+  // limb step): inputs, constants and table rows are residues modulo n and therefore valid modulo M as they are; the program
+  // leaves through the reduction pass times c and the exact division by c (sc_device.h).  Not with premul: that variant leaves
+  // Montgomery form through a product, which has no room for the factor c.
+  const int tmod = premul ? -1 : neg1_vm_twin(ctx, mod, count);
+  const bool twin = tmod >= 0;
+  const int rmod = twin ? tmod : mod;
+  const Mod& m = ctx->mods[mod];        // (taken after the twin exists: creating it may move the table of moduli)
+  std::string key = "mvar:" + std::to_string(rmod) + ":" + std::to_string(ebits) + ":" + std::to_string(fbt) + (dest ? ":s" : "") + (perm ? ":q" : "") + (premul ? ":p" : "");
+  const Prog* p;
+  int rc = cached_prog(ctx, key, rmod, [&](Builder& bd) {
+    const int w = ebits <= 4 ? 1 : (ebits <= 12 ? 2 : 3);
+    const int nd = (ebits + w - 1) / w;
+    bd.loadw(0); bd.mul_const(0); bd.stt(1);          // t[1] = x (Montgomery)
+    bd.loadt_const(1); bd.stt(0);                      // t[0] = 1
+    for (int k = 2; k < (1 << w); k++) { bd.loadt_tbl(k - 1); bd.mul_tbl(1); bd.stt(k); }
+    bd.loadt_tbldig(1, (nd - 1) * w, w, 0);
+    for (int d = nd - 2; d >= 0; d--) { for (int k = 0; k < w; k++) bd.sqr(); bd.mul_tbldig(1, d * w, w, 0); }
+    if (f) for (int j = 0; j < f->nwin; j++) bd.mul_fbt(3, j * f->window, f->window, j);
+    if (premul) bd.mul_extw(5); else bd.redc(twin);      // (x^e R) * premul / R = x^e premul: leaves Montgomery form by itself
+    if (dest || perm) bd.storew_at(2, 4, twin, perm != nullptr); else bd.storew(2, 0, twin);
+  }, &p); if (rc) return rc;
+  // a scattered store never leaves the output array: rows >= count are dropped by the limit of the output operand
+  VmExt ex[6] = {mk_ext(x, m.nwords, m.nwords), mk_ext(e, ewords, ewords), mk_ext(out, m.nwords, m.nwords, (dest || perm) ? count : ~0ull),
+                 mk_ext(e2, e2words, e2words), perm ? mk_ext(perm, planes, 0, count / planes) : mk_ext(dest, 2, 2), mk_ext(premul, m.nwords, m.nwords)};
+  return run_vm(ctx, rmod, *p, ex, 6, count, f ? f->d_rows : nullptr);
+}
+
+int plain_bob_impl(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint64_t* beta,
+                          uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2, uint8_t* bits) {
+  if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
+  if (!ctx || !z || !n_hptr || nw <= 0 || l <= 0 || l > SC_MAX_L || !beta || !dbit || !zeta1 || !zeta2)
+    return fail(ctx, SC_ERR_ARG, "sc_plain_bob: bad argument");
+  if (l >= 32 * nw) return fail(ctx, SC_ERR_ARG, "sc_plain_bob: l = %d does not fit below a modulus of %d words (l < 32 nw)", l, nw);
+  uint32_t* d_n = nullptr;
+  { int rc = device_n_half(ctx, n_hptr, nw, &d_n); if (rc) return rc; }
+  if (launch_plain_bob(ctx->stream, z, d_n, d_n + nw, nw, l, count, beta, dbit, zeta1, zeta2, bits)) return fail(ctx, SC_ERR_HIP, "sc_plain_bob: launch failed");
+  return SC_OK;
+}
+}  // namespace sc_host
 
 extern "C" {
 
@@ -784,45 +540,6 @@ int sc_modmul_const_sel(sc_ctx* ctx, int mod, const uint32_t* a, int cst0, int c
     bd.storew(1);
   }, &p); if (rc) return rc;
   VmExt ex[3] = {mk_ext(a, m.nwords, m.nwords), mk_ext(out, m.nwords, m.nwords), mk_ext(flags, 0, 0)};
-  return run_vm(ctx, mod, *p, ex, 3, count);
-}
-
-static int onelane_for(sc_ctx* ctx, int mod, uint64_t count);
-
-// any_flags_clean: the caller guarantees that any_flags[0 .. inner) is zero already (a context-owned accumulator that its reader
-// resets, OP_TAKEFLAG): no clearing launch
-static int modexp_shared_impl(sc_ctx* ctx, int mod, int exp, const uint32_t* x, int x_words, const uint32_t* mul_into,
-                              uint32_t* out, uint8_t* flags, uint64_t count, uint64_t* any_flags, uint64_t inner, bool any_flags_clean = false) {
-  if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!valid_mod(ctx, mod) || exp < 0 || exp >= (int)ctx->exps.size() || !x || (!out && !flags && !any_flags))
-    return fail(ctx, SC_ERR_ARG, "sc_modexp_shared: bad argument");
-  if (any_flags) {
-    if (inner == 0 || count % inner != 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_shared_isone_any: count must be a multiple of the inner count");
-    if (!any_flags_clean) HIPCHK(ctx, hipMemsetAsync(any_flags, 0, inner * sizeof(uint64_t), ctx->stream));
-  }
-  if (ctx->exps[exp].bits > 64) mod = onelane_for(ctx, mod, count);   // long exponentiations of a chip-filling batch: one-lane twin
-  const Mod& m = ctx->mods[mod];
-  if (x_words <= 0) x_words = m.nwords;
-  const int mode = any_flags ? 3 : (flags ? 2 : (mul_into ? 1 : 0));
-  std::string key = "mexp:" + std::to_string(mod) + ":" + std::to_string(exp) + ":" + std::to_string(x_words) + ":" + std::to_string(mode);
-  const Prog* p;
-  int rc = cached_prog(ctx, key, mod, [&](Builder& bd) -> int {
-    if (x_words > m.nwords) {
-      int kc; int rc = get_const_kred(ctx, mod, &kc); if (rc) return rc;
-      emit_load_reduced(ctx, m, bd, 0, x_words, bd.use_const(kc));
-    } else {
-      bd.loadw(0, 0, 0, x_words);
-    }
-    bd.mul_const(0);                   // to Montgomery form
-    emit_pow_shared(bd, ctx->exps[exp]);
-    if (mode == 0) { bd.redc(); bd.storew(1); }
-    else if (mode == 1) { bd.mul_extw(2); bd.storew(1); }
-    else bd.storeflag(1, 0, 1, mode == 3);             // compare with R mod n (Montgomery one); mode 3: OR the verdict into the item's group flag
-    return SC_OK;
-  }, &p); if (rc) return rc;
-  VmExt ex[3] = {mk_ext(x, x_words, x_words),
-                 any_flags ? mk_ext(any_flags, 0, 0, inner) : (flags ? mk_ext(flags, 0, 0) : mk_ext(out, m.nwords, m.nwords)),
-                 mk_ext(mul_into, m.nwords, m.nwords)};
   return run_vm(ctx, mod, *p, ex, 3, count);
 }
 
@@ -927,51 +644,6 @@ int sc_fixedbase_pow(sc_ctx* ctx, int fbt, const uint32_t* e, int ewords, const 
   return run_vm(ctx, f.mod, *p, ex, 3, count, f.d_rows);
 }
 
-static int neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count);
-// premul (nullable): a finished factor per item (e.g. a randomizer h^r computed ahead of time on another stream) multiplied in
-// before the store -- the alternative to the fixed-base tail (fbt / e2)
-// perm (nullable, instead of dest): int64 [count / planes][planes], one permutation per comparison of a bit-major vector
-// [planes][inner]: item (j, b) is stored at plane k with perm[b][k] == j (the step-4i shuffle inside the store)
-static int modexp_var_impl(sc_ctx* ctx, int mod, const uint32_t* x, const uint32_t* e, int ewords, int ebits, int fbt,
-                           const uint32_t* e2, int e2words, const uint64_t* dest, uint32_t* out, uint64_t count,
-                           const uint32_t* premul = nullptr, const int64_t* perm = nullptr, uint32_t planes = 0) {
-  if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!valid_mod(ctx, mod) || !x || !e || !out || ewords <= 0 || ebits <= 0 || ebits > 32 * ewords)
-    return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad argument");
-  if (perm && (dest || planes == 0 || planes > SC_MAX_L + 1 || count % planes != 0)) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad permutation batch");
-  const Fbt* f = nullptr;
-  if (fbt >= 0) {
-    if (fbt >= (int)ctx->fbts.size() || ctx->fbts[fbt].mod != mod || !e2 || e2words <= 0) return fail(ctx, SC_ERR_ARG, "sc_modexp_var: bad fixed-base table");
-    f = &ctx->fbts[fbt];
-  }
-  // chip-filling batches of a (4,18) modulus run in the context of its multiple M = c n = -1 (mod 2^29) (no quotient multiply per
-  // limb step): inputs, constants and table rows are residues modulo n and therefore valid modulo M as they are; the program
-  // leaves through the reduction pass times c and the exact division by c (sc_device.h).  Not with premul: that variant leaves
-  // Montgomery form through a product, which has no room for the factor c.
-  const int tmod = premul ? -1 : neg1_vm_twin(ctx, mod, count);
-  const bool twin = tmod >= 0;
-  const int rmod = twin ? tmod : mod;
-  const Mod& m = ctx->mods[mod];        // (taken after the twin exists: creating it may move the table of moduli)
-  std::string key = "mvar:" + std::to_string(rmod) + ":" + std::to_string(ebits) + ":" + std::to_string(fbt) + (dest ? ":s" : "") + (perm ? ":q" : "") + (premul ? ":p" : "");
-  const Prog* p;
-  int rc = cached_prog(ctx, key, rmod, [&](Builder& bd) {
-    const int w = ebits <= 4 ? 1 : (ebits <= 12 ? 2 : 3);
-    const int nd = (ebits + w - 1) / w;
-    bd.loadw(0); bd.mul_const(0); bd.stt(1);          // t[1] = x (Montgomery)
-    bd.loadt_const(1); bd.stt(0);                      // t[0] = 1
-    for (int k = 2; k < (1 << w); k++) { bd.loadt_tbl(k - 1); bd.mul_tbl(1); bd.stt(k); }
-    bd.loadt_tbldig(1, (nd - 1) * w, w, 0);
-    for (int d = nd - 2; d >= 0; d--) { for (int k = 0; k < w; k++) bd.sqr(); bd.mul_tbldig(1, d * w, w, 0); }
-    if (f) for (int j = 0; j < f->nwin; j++) bd.mul_fbt(3, j * f->window, f->window, j);
-    if (premul) bd.mul_extw(5); else bd.redc(twin);      // (x^e R) * premul / R = x^e premul: leaves Montgomery form by itself
-    if (dest || perm) bd.storew_at(2, 4, twin, perm != nullptr); else bd.storew(2, 0, twin);
-  }, &p); if (rc) return rc;
-  // a scattered store never leaves the output array: rows >= count are dropped by the limit of the output operand
-  VmExt ex[6] = {mk_ext(x, m.nwords, m.nwords), mk_ext(e, ewords, ewords), mk_ext(out, m.nwords, m.nwords, (dest || perm) ? count : ~0ull),
-                 mk_ext(e2, e2words, e2words), perm ? mk_ext(perm, planes, 0, count / planes) : mk_ext(dest, 2, 2), mk_ext(premul, m.nwords, m.nwords)};
-  return run_vm(ctx, rmod, *p, ex, 6, count, f ? f->d_rows : nullptr);
-}
-
 int sc_modexp_var(sc_ctx* ctx, int mod, const uint32_t* x, const uint32_t* e, int ewords, int ebits, int fbt,
                   const uint32_t* e2, int e2words, uint32_t* out, uint64_t count) {
   return modexp_var_impl(ctx, mod, x, e, ewords, ebits, fbt, e2, e2words, nullptr, out, count);
@@ -981,15 +653,6 @@ int sc_modexp_var_scatter(sc_ctx* ctx, int mod, const uint32_t* x, const uint32_
                           const uint32_t* e2, int e2words, const uint64_t* dest_index, uint32_t* out, uint64_t count) {
   if (ctx && count != 0 && !dest_index) return fail(ctx, SC_ERR_ARG, "sc_modexp_var_scatter: no destination index");
   return modexp_var_impl(ctx, mod, x, e, ewords, ebits, fbt, e2, e2words, dest_index, out, count);
-}
-
-static int paillier_encrypt_raw_impl(sc_ctx* ctx, int mod_n2, int cst_n, const uint32_t* mwords, int m_words, uint32_t* out, uint64_t count, bool negate);
-
-int sc_paillier_encrypt_raw(sc_ctx* ctx, int mod_n2, int cst_n, const uint32_t* mwords, int m_words, uint32_t* out, uint64_t count) {
-  return paillier_encrypt_raw_impl(ctx, mod_n2, cst_n, mwords, m_words, out, count, false);
-}
-int sc_paillier_encrypt_raw_neg(sc_ctx* ctx, int mod_n2, int cst_n, const uint32_t* mwords, int m_words, uint32_t* out, uint64_t count) {
-  return paillier_encrypt_raw_impl(ctx, mod_n2, cst_n, mwords, m_words, out, count, true);
 }
 
 static int paillier_encrypt_raw_impl(sc_ctx* ctx, int mod_n2, int cst_n, const uint32_t* mwords, int m_words, uint32_t* out, uint64_t count, bool negate) {
@@ -1008,6 +671,13 @@ static int paillier_encrypt_raw_impl(sc_ctx* ctx, int mod_n2, int cst_n, const u
   }, &p); if (rc) return rc;
   VmExt ex[2] = {mk_ext(mwords, m_words, m_words), mk_ext(out, m.nwords, m.nwords)};
   return run_vm(ctx, mod_n2, *p, ex, 2, count);
+}
+
+int sc_paillier_encrypt_raw(sc_ctx* ctx, int mod_n2, int cst_n, const uint32_t* mwords, int m_words, uint32_t* out, uint64_t count) {
+  return paillier_encrypt_raw_impl(ctx, mod_n2, cst_n, mwords, m_words, out, count, false);
+}
+int sc_paillier_encrypt_raw_neg(sc_ctx* ctx, int mod_n2, int cst_n, const uint32_t* mwords, int m_words, uint32_t* out, uint64_t count) {
+  return paillier_encrypt_raw_impl(ctx, mod_n2, cst_n, mwords, m_words, out, count, true);
 }
 
 int sc_paillier_l_mul(sc_ctx* ctx, int mod, int cst_k, const uint32_t* x, int x_words, uint32_t* out, uint64_t count) {
@@ -1042,23 +712,9 @@ int sc_plain_alice(sc_ctx* ctx, const uint32_t* r, const uint32_t* n_hptr, int n
   return SC_OK;
 }
 
-static int plain_bob_impl(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint64_t* beta,
-                          uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2, uint8_t* bits);
 int sc_plain_bob(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint64_t* beta,
                  uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2) {
   return plain_bob_impl(ctx, z, n_hptr, nw, l, count, beta, dbit, zeta1, zeta2, nullptr);
-}
-// bits (nullable): additionally the bytes [l+1][count] of d and the bits of beta (k_plain_bob)
-static int plain_bob_impl(sc_ctx* ctx, const uint32_t* z, const uint32_t* n_hptr, int nw, int l, uint64_t count, uint64_t* beta,
-                          uint64_t* dbit, uint32_t* zeta1, uint32_t* zeta2, uint8_t* bits) {
-  if (ctx && count == 0) return SC_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!ctx || !z || !n_hptr || nw <= 0 || l <= 0 || l > SC_MAX_L || !beta || !dbit || !zeta1 || !zeta2)
-    return fail(ctx, SC_ERR_ARG, "sc_plain_bob: bad argument");
-  if (l >= 32 * nw) return fail(ctx, SC_ERR_ARG, "sc_plain_bob: l = %d does not fit below a modulus of %d words (l < 32 nw)", l, nw);
-  uint32_t* d_n = nullptr;
-  { int rc = device_n_half(ctx, n_hptr, nw, &d_n); if (rc) return rc; }
-  if (launch_plain_bob(ctx->stream, z, d_n, d_n + nw, nw, l, count, beta, dbit, zeta1, zeta2, bits)) return fail(ctx, SC_ERR_HIP, "sc_plain_bob: launch failed");
-  return SC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1558,6 +1214,7 @@ int sc_crt_combine(sc_ctx* ctx, int mod_p, int mod_full, int cst_k, int cst_negk
   VmExt ex[3] = {mk_ext(d_t, mp.nwords, mp.nwords), mk_ext(a_q, a_q_words, a_q_words), mk_ext(out, mf.nwords, mf.nwords)};
   return run_vm(ctx, mod_full, *p2, ex, 3, count);
 }
+}  // extern "C"
 
 // ---- twin contexts ---------------------------------------------------------------------------------------------------------------
 // A twin is a second registration of a modulus (or of its multiple M = c n) in another configuration, made on first use and kept
@@ -1607,7 +1264,7 @@ static int neg1_twin(sc_ctx* ctx, int mod) {
   return twin_of(ctx, TWIN_NEG1, mod, [&](const Mod& m) {
     static const bool enabled = []{ const char* e = getenv("SC_NEG1"); return !(e && e[0] == '0'); }();      // A/B switch (dev): SC_NEG1=0
     if (!enabled || !neg1_candidate(shape_of(m), m.nbits)) return -1;
-    const Big M = big_trimmed_words(big_mul(m.n, Big(1, m.n0inv)));
+    const Big M = big_trimmed(big_mul(m.n, Big(1, m.n0inv)));
     const Config same = {m.G, m.L, m.W, false};
     int twin = -1;
     if (!fits(same, big_bits(M), (int)M.size(), true) || create_mod(ctx, M.data(), (int)M.size(), false, &twin, &same) != SC_OK) return -1;
@@ -1621,10 +1278,7 @@ static int neg1_twin(sc_ctx* ctx, int mod) {
   });
 }
 
-// The same twin for the single-modulus interpreter: only the (4,18) instance k_vm<4,18,29,true> exists, and only programs whose
-// outputs are word stores can use it (modexp_var_impl: the blinding launch of step 4i) -- limb-form outputs would carry residues
-// up to 2M into launches of the original context.
-static int neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count) {
+int sc_host::neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count) {
   if (!neg1_vm_allowed(shape_of(ctx->mods[mod]), policy_of(ctx), count)) return -1;
   const int t = neg1_twin(ctx, mod);
   return (t >= 0 && ctx->mods[t].small_c != 0) ? t : -1;
@@ -1641,8 +1295,6 @@ static int neg1_vm_twin(sc_ctx* ctx, int mod, uint64_t count) {
 static std::mutex g_cal_mutex;
 static std::map<int, OneLaneCal> g_cal;           // by device
 
-static int modexp_shared_impl(sc_ctx* ctx, int mod, int exp, const uint32_t* x, int x_words, const uint32_t* mul_into,
-                              uint32_t* out, uint8_t* flags, uint64_t count, uint64_t* any_flags, uint64_t inner, bool any_flags_clean);
 
 static int onelane_calibrate(sc_ctx* ctx, OneLaneCal* out) {
   OneLaneCal c;
@@ -1697,8 +1349,7 @@ static int onelane_calibrate(sc_ctx* ctx, OneLaneCal* out) {
   return SC_OK;
 }
 
-// the calibration of this context's device (measured by the first context that asks; a failed measurement leaves round 3's constants)
-static OneLaneCal onelane_cal(sc_ctx* ctx) {
+OneLaneCal sc_host::onelane_cal(sc_ctx* ctx) {
   std::lock_guard<std::mutex> lock(g_cal_mutex);
   auto it = g_cal.find(ctx->device);
   if (it != g_cal.end()) return it->second;
@@ -1708,7 +1359,7 @@ static OneLaneCal onelane_cal(sc_ctx* ctx) {
   return c;
 }
 
-int sc_ctx_policy(sc_ctx* ctx, double* out6) {
+extern "C" int sc_ctx_policy(sc_ctx* ctx, double* out6) {
   if (!ctx || !out6) return SC_ERR_ARG;
   const OneLaneCal c = onelane_cal(ctx);
   out6[0] = c.one_full; out6[1] = c.one_half; out6[2] = c.two_full; out6[3] = c.two_half; out6[4] = c.two_only_half; out6[5] = (double)c.simds;
@@ -1723,7 +1374,7 @@ int sc_ctx_policy(sc_ctx* ctx, double* out6) {
 // When several contexts work on the GPU at once (concurrent shards: sc_ctx_set_chip_share) a launch owns its share of the chip
 // only, and the idle SIMDs of an under-filled launch are taken by the other contexts' kernels: rounds are counted on that share
 // (two shards of 32768 comparisons: the 98304-number launches run one-lane, +1.5 % on the whole step).
-static int onelane_for(sc_ctx* ctx, int mod, uint64_t count) {
+int sc_host::onelane_for(sc_ctx* ctx, int mod, uint64_t count) {
   if (ctx->onelane_mode == 0) return mod;
   if (const Mod& m = ctx->mods[mod]; !onelane_eligible(shape_of(m), m.nbits, m.nwords)) return mod;
   // (the calibration may register moduli: no reference into ctx->mods is held across it)
@@ -1784,6 +1435,8 @@ static int pair_op_times(sc_ctx* ctx, int mod_m, uint64_t count, int x_words, co
   *sqr_ms = t.sqr_ms; *mul_ms = t.mul_ms;
   return SC_OK;
 }
+
+extern "C" {
 
 int sc_ctx_set_pair_policy(sc_ctx* ctx, double hold_ms, double max_rounds) {
   if (!ctx || hold_ms < 0 || !(max_rounds > 0)) return SC_ERR_ARG;
@@ -2067,8 +1720,6 @@ int sc_modexp_var_sq(sc_ctx* ctx, int mod_m, int mod_m2, int nbases, const uint3
   return pair_assemble(ctx, mod_m, mod_m2, d_w, d_w1, wm, mul_into, out, count);
 }
 
-#include "sc_families.h"
-
 // ------------------------------------------------------------------------------------------------
 // Multi-GPU: comparisons are independent, so the only exchange is the reassembly of per-rank result blocks -- one
 // RCCL all-gather over xGMI on the context's stream.  RCCL is bound at run time (dlopen): a single-GPU user never loads it, and
@@ -2291,6 +1942,3 @@ int sc_mac_counter(sc_ctx* ctx, int reset, double* out_macs) {
 }
 
 }  // extern "C"
-
-#include "sc_schemes.h"
-#include "sc_topk.h"

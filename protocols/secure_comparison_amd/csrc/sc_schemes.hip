@@ -1,60 +1,16 @@
 // Scheme-level entry points of the C ABI: what the reference's scheme objects and protocol steps do, ONE call each.
-// Included at the end of sc_lib.hip (same translation unit: uses its context, program builder and launch helpers).
-//
 // The reference reaches its arithmetic through `ct.randomize()` (SC/keyholder.py:106-108, 126-128; SC/initiator.py:109,
 // 153-154), `Paillier.decrypt` (SC/keyholder.py:195), `DGK.is_zero` (:249) and the operator algebra inside step_1 / step_4* /
 // step_6 / step_7.  Rounds 1-2 exposed the primitives those decompose into; a maintainer binding them had to re-implement the
 // key holder's CRT, the pair arithmetic's plumbing and the exponent reductions.  Here that composition lives in the library:
 // a key object holds every derived modulus, exponent, constant and fixed-base table, and each entry point queues the same
-// launches the Python layer used to compose -- identical residues.
-#pragma once
+// launches the Python layer used to compose -- identical residues.  Host code only.
+#include "sc_host.h"
+
+using namespace sc;
+using namespace sc_host;
 
 namespace {
-
-// ---- more set-up-time host integers (little-endian uint32 words) -------------------------------------------------------------
-Big big_trimmed(Big a) { while (a.size() > 1 && a.back() == 0) a.pop_back(); return a; }
-Big big_fit(Big a, size_t words) { a.resize(words, 0); return a; }
-bool big_is_zero(const Big& a) { for (uint32_t w : a) if (w) return false; return true; }
-bool big_is_one(const Big& a) { if (a.empty() || a[0] != 1) return false; for (size_t i = 1; i < a.size(); i++) if (a[i]) return false; return true; }
-Big big_mod(const Big& x, const Big& m) { Big q, r; big_divmod(x, m, &q, &r); return r; }       // m.size() words
-Big big_mulmod(const Big& a, const Big& b, const Big& m) { return big_mod(big_mul(a, b), m); }
-// base^e mod m, set-up time only (square and multiply over the bits of e; m.size() words)
-Big big_powmod(const Big& base, const Big& e, const Big& m) {
-  Big r(m.size(), 0); r[0] = 1;
-  r = big_mod(r, m);
-  const Big b = big_mod(base, m);
-  for (int i = big_bits(e) - 1; i >= 0; i--) {
-    r = big_mulmod(r, r, m);
-    if ((e[i >> 5] >> (i & 31)) & 1) r = big_mulmod(r, b, m);
-  }
-  return r;
-}
-Big big_sub_small(Big a, uint32_t k) { Big b(a.size(), 0); b[0] = k; big_sub(a, b); return a; }
-void big_add_inplace(Big& a, const Big& b) {   // same length; the carry out is dropped (callers keep a spare top word)
-  uint64_t c = 0;
-  for (size_t i = 0; i < a.size(); i++) { c += (uint64_t)a[i] + b[i]; a[i] = (uint32_t)c; c >>= 32; }
-}
-void big_shr1(Big& a) { for (size_t i = 0; i < a.size(); i++) a[i] = (a[i] >> 1) | ((i + 1 < a.size()) ? (a[i + 1] << 31) : 0u); }
-// a^-1 mod m for odd m (binary extended Euclid, HAC 14.61 shape); empty when gcd(a, m) != 1.  Result has m.size() words.
-Big big_modinv_odd(const Big& a_in, const Big& m_in) {
-  const size_t W = m_in.size() + 1;                         // one spare word: x + m never overflows
-  const Big m = big_fit(m_in, W);
-  Big u = big_fit(big_mod(a_in, m_in), W), v = m, x1(W, 0), x2(W, 0);
-  x1[0] = 1;
-  if (big_is_zero(u)) return Big();
-  auto halve = [&](Big& x) { if (x[0] & 1) big_add_inplace(x, m); big_shr1(x); };
-  while (!big_is_one(u) && !big_is_one(v)) {
-    while (!(u[0] & 1)) { big_shr1(u); halve(x1); }
-    while (!(v[0] & 1)) { big_shr1(v); halve(x2); }
-    if (big_cmp(u, v) >= 0) { big_sub(u, v); if (big_cmp(x1, x2) < 0) big_add_inplace(x1, m); big_sub(x1, x2); }
-    else { big_sub(v, u); if (big_cmp(x2, x1) < 0) big_add_inplace(x2, m); big_sub(x2, x1); }
-    if (big_is_zero(u) || big_is_zero(v)) return Big();     // a common factor was subtracted away
-  }
-  Big r = big_is_one(u) ? x1 : x2;
-  while (big_cmp(r, m) >= 0) big_sub(r, m);
-  r.resize(m_in.size());
-  return r;
-}
 
 int reg_exp(sc_ctx* ctx, const Big& e, int* out) { Big t = big_trimmed(e); return sc_exp_create(ctx, t.data(), (int)t.size(), out); }
 int reg_const(sc_ctx* ctx, int mod, const Big& v, int* out) {
@@ -96,9 +52,9 @@ struct sc_scheme_keys {
   ~sc_scheme_keys() { if (select_verdict) (void)hipHostFree(select_verdict); }
 };
 
-namespace {
+void sc_host::free_scheme_keys(void* p) { delete (sc_scheme_keys*)p; }
 
-void free_scheme_keys(void* p) { delete (sc_scheme_keys*)p; }
+namespace {
 
 sc_scheme_keys* keys_of(sc_ctx* ctx) {
   if (!ctx->scheme_keys) ctx->scheme_keys = new sc_scheme_keys();
@@ -116,9 +72,6 @@ DgkKey* dgk_key(sc_ctx* ctx, int key) {
 }
 
 enum SchemeTmp { TMP_S_A = 40, TMP_S_B, TMP_S_C, TMP_S_D, TMP_S_E, TMP_S_F, TMP_S_G, TMP_S_H, TMP_S_I };
-template <typename T>
-int tmp_words(sc_ctx* ctx, int slot, uint64_t elems, T** out) { return tmp_buf(ctx, slot, (size_t)elems * sizeof(T), (void**)out); }
-
 
 // rho^N mod N^2 for the key holder: ((rho mod p)^(q mod p-1) mod p)^p mod p^2 per prime, recombined (identical integers)
 int paillier_crt_pow_n(sc_ctx* ctx, const PaillierKey& k, const uint32_t* rho, uint32_t* out, uint64_t count) {

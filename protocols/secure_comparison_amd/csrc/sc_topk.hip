@@ -1,12 +1,11 @@
 // The truncated sorting network of a secure top-m for a C host: sc_topk_network.  Host code only, no context and no
 // device work.  Python derives the same network on its own (sorting.topk_network); the two are compared field by field in
 // tests/test_topk_cpu.py, so a host that iterates these layers sends the key holder exactly the sub-batches he expects.
-//
-// Included at the end of sc_lib.hip.
-#pragma once
 #include <algorithm>
 #include <cstdint>
 #include <vector>
+
+#include "../../../include/sc_amd.h"
 
 namespace {
 

@@ -32,7 +32,7 @@ class DotLayout:
     """Layout of the packed plaintexts of an inner product of k pairs of widths (wx, wy) under a key of nbits bits: a pair takes
     pb = sa + sb bits (sa = wx + kappa + 1, sb = wy + kappa + 1; square mode: the one field, sb = 0 and wy = 0), g pairs fit a message
     and a row takes M messages.  Raises ValueError when a quantity is out of range, when not even one pair fits (g < 1) or when the sum
-    of k products would not stay below N (dot_layout in csrc/sc_families.h is the library's copy of the rule)."""
+    of k products would not stay below N (dot_layout in csrc/sc_families.hip is the library's copy of the rule)."""
 
     kappa: int
     wx: int

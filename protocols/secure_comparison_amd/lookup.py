@@ -39,7 +39,7 @@ def default_index_bits(k: int) -> int:
 class OnehotLayout:
     """Layout of the packed plaintexts of a one-hot encoding of m indices of ib bits against a table of k entries under a key of nbits
     bits: a field takes f = ib + kappa + 1 bits, g fields fit a message and a row takes M messages.  Raises ValueError when a quantity
-    is out of range or when not even one field fits, f >= nbits - 1 (onehot_layout in csrc/sc_families.h is the library's copy of the
+    is out of range or when not even one field fits, f >= nbits - 1 (onehot_layout in csrc/sc_families.hip is the library's copy of the
     rule)."""
 
     kappa: int

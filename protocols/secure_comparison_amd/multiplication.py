@@ -31,7 +31,7 @@ MAX_WIDTH = 255     # bits of one operand (csrc/sc_vm.h MUL_MAX_WIDTH)
 class MulLayout:
     """Field layout of the packed plaintext of P for x of wx bits and columns y_j of wy[j] bits under a key of nbits bits:
     A = x + e_y in [0, s), s = wx + kappa + 1, then B_j = y_j + e_x_j in fbits_j = wy[j] + kappa + 1 bits.  Raises ValueError when
-    s + sum_j fbits_j or one s + fbits_j reaches bits(N) - 1 (mul_layout in csrc/sc_families.h is the library's copy of the rule)."""
+    s + sum_j fbits_j or one s + fbits_j reaches bits(N) - 1 (mul_layout in csrc/sc_families.hip is the library's copy of the rule)."""
 
     kappa: int
     wx: int

@@ -6,7 +6,7 @@ tests/test_gpu_odd_keys.py runs it.  Nothing here is a literal: the conditions, 
 must launch come from the policy restated in tests/_instance_matrix.py (first_fit, pair_capable, has_neg1_multiple, nwords_of), and
 the widths from the package's own layout classes, imported only when a width is asked for.
 
-How sc_paillier_key_create lays a key out (csrc/sc_schemes.h): N in nw = nwords(N) words; N^2 in 2 nw words, whatever its own
+How sc_paillier_key_create lays a key out (csrc/sc_schemes.hip): N in nw = nwords(N) words; N^2 in 2 nw words, whatever its own
 length; both primes in hw = nwords(max(bits(p), bits(q))) words, so the shorter prime is padded; p^2 and q^2 in 2 hw words each.
 """
 from __future__ import annotations

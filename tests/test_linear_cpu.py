@@ -190,7 +190,7 @@ def test_rows_on_the_stand_in(sk):
 # ---- the symbols ---------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_declared_and_bound():
     from protocols.secure_comparison_amd import _lib
-    from protocols.secure_comparison_amd.build import ALL_UNITS, LINEAR_UNITS, UNITS, build_lib
+    from protocols.secure_comparison_amd.build import ALL_UNITS, HOST_UNITS, LINEAR_UNITS, UNITS, build_lib
     from protocols.secure_comparison_amd.engine import Engine
 
     dev = open(os.path.join(ROOT, "include", "sc_amd_dev.h")).read()
@@ -203,7 +203,7 @@ def test_symbols_are_declared_and_bound():
         assert hasattr(lib, name) and name in _lib.SYMBOLS
         assert len(getattr(_lib.load(), name).argtypes) == 9
     assert callable(Engine.modlin_axis) and callable(Engine.paillier_linear_axis) and _lib.ABI_VERSION == 5
-    assert LINEAR_UNITS == [("sc_launch_lin", "sc_launch_lin.hip", [])] and ALL_UNITS == UNITS + LINEAR_UNITS and len(ALL_UNITS) == 14
+    assert LINEAR_UNITS == [("sc_launch_lin", "sc_launch_lin.hip", [])] and ALL_UNITS == UNITS + LINEAR_UNITS + HOST_UNITS and len(ALL_UNITS) == 17
     unit = open(os.path.join(ROOT, "protocols", "secure_comparison_amd", "csrc", "sc_launch_lin.hip")).read()
     assert '#include "sc_launch_axis.h"' in unit and not re.search(r"#define\s+SC_\w*INSTANCES", unit) and "asm" not in unit
     import protocols.secure_comparison_amd as pkg

@@ -1,8 +1,8 @@
 """Instruction summary of the gfx950 kernels from the compiler's assembly listing.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -pragma-unroll-threshold=1000000 --cuda-device-only -S \
-        protocols/secure_comparison_amd/csrc/sc_lib.hip -o /tmp/sc_lib.s
-    python tools/isa_summary.py /tmp/sc_lib.s [kernel-substring ...] > profiles/rNN_isa_summary.json
+        -DSC_PART=0 protocols/secure_comparison_amd/csrc/sc_launch_vm.hip -o /tmp/sc_launch_vm0.s      (any kernel unit of build.py)
+    python tools/isa_summary.py /tmp/sc_launch_vm0.s [kernel-substring ...] > profiles/rNN_isa_summary.json
 
 Per kernel: register / scratch metadata, an instruction histogram, and the basic blocks ranked by multiply-add count (the hot
 blocks are the unrolled limb-step loops) with the scratch_* (spill) instructions each block contains -- the evidence for

@@ -29,7 +29,7 @@ static void check_columns(int nf) {
   std::vector<uint32_t> x(COL), cols(nf * COL);
   const auto fld = column_fields(x.data(), cols.data(), nf, s, fbits, COUNT, COL);
   CHECK((int)fld.size() == nf + 1 && fld[0].rows == x.data() && shift_of(fld, 0) == 0 && fld[0].held == COUNT);
-  for (int j = 0, off = s; j < nf; off += fbits[j++])            // off[j] as pack_fields (sc_families.h) lays the columns out
+  for (int j = 0, off = s; j < nf; off += fbits[j++])            // off[j] as pack_fields (sc_families.hip) lays the columns out
     CHECK(shift_of(fld, j + 1) == off && fld[j + 1].rows == cols.data() + j * COL && fld[j + 1].held == COUNT);
 }
 
