@@ -358,6 +358,35 @@ int sc_initiator_onehot_finish(sc_ctx* ctx, int paillier_key, int kappa, int ib,
 int sc_topk_network(int k, int m, int only_last, int cap, int32_t* ij_out /* [cap][2] */, uint8_t* keep_out /* [cap][2] */,
                     int32_t* layer_end_out /* [cap] */, int* n_comparators, int* n_layers);
 
+/* ---- secure division by public divisors: [[x div d]] and [[x mod d]], exact floor division ---------------------------- */
+/* [[x]] with 0 <= x < 2^x_bits and a public divisor 1 <= d < 2^64 per row.  The comparison is this division with d = 2^l, so the calls
+ * a host already has carry it: the initiator blinds, z = x + r with r < 2^(x_bits + kappa) (sc_initiator_div_blind, which also returns
+ * rq = r div d and rm = r mod d); the key holder decrypts and divides (sc_keyholder_div_open: zq = z div d, zm = z mod d); then both run
+ * the DGK sub-comparison [[zm < rm]] at l = max(1, bits(max d - 1)) through sc_dgk_encrypt_bits_randomized (the bit 1, then the l bits
+ * of zm), sc_initiator_step4 (alpha = alpha_tilde = rm, r_small = 1), sc_keyholder_step4j_5 (zeta_1 = zeta_2 = zq) and
+ * sc_initiator_step67 (r_small = 1, r_shift = rq), whose result is [[zq]] ([[rq]] [[zm < rm]])^-1 = [[x div d]].  The DGK key needs
+ * u > 2^(l + 2).  INTEGRATION.md section 2b has the sequence.
+ * The fit rule, 1 when it holds and 0 when not: x_bits + kappa + 2 < nbits_n - 1 with 1 <= kappa <= 62 and x_bits >= 1, so that z never
+ * wraps around N and stays below (N - 1) / 2.  is_signed: -2^x_bits <= x < 2^x_bits; the caller divides x + c d, c = ceil(2^x_bits / d),
+ * and subtracts c from the quotient, and the rule holds for the offset dividend's width max(x_bits + 2, 65) in place of x_bits.  Host
+ * only, no context. */
+int sc_div_fits(int nbits_n, int kappa, int x_bits, int is_signed);
+/* Initiator: z_out [count][2 nwords] = [[x + r]] rho^N from x_enc [count][2 nwords] (signed input: the offset [[x + c d]]), r
+ * [count][nwords] (< 2^(x_bits + kappa), zero-extended to the words of N) and rho [count][nwords] -- or, with SC_STEP_RANDOMIZERS_READY
+ * in flags, the finished randomizers rho^N [count][2 nwords]; rq_out [count][nwords] = r div d and rm_out [count] uint64 = r mod d for
+ * the divisors d [count] uint64 (device).  SC_ERR_ARG before anything is launched where sc_div_fits refuses.
+ * ZERO DIVISORS: the call queues its launches and cannot see a divisor of zero.  A host that has not checked d itself MUST call
+ * sc_ctx_synchronize(ctx) after this call (and after sc_keyholder_div_open) and before it uses rq, rm (zq, zm): that is the one place
+ * where the error comes back -- SC_ERR_ARG, once, the affected rows written as zero -- and a host that never synchronises through the
+ * context never sees it, while a later, unrelated sc_ctx_synchronize would (sc_plain_divmod, sc_amd_dev.h). */
+int sc_initiator_div_blind(sc_ctx* ctx, int paillier_key, int kappa, int x_bits, int is_signed, const uint32_t* x_enc_dptr,
+                           const uint32_t* r_dptr, const uint32_t* rho_dptr, int flags, const uint64_t* d_dptr, uint32_t* z_out_dptr,
+                           uint32_t* rq_out_dptr, uint64_t* rm_out_dptr, uint64_t count);
+/* Key holder: z = Dec([[z]]) for z_enc [count][2 nwords], then zq_out [count][nwords] = z div d and zm_out [count] uint64 = z mod d.
+ * The decryption, then one division launch in place; a zero divisor as above. */
+int sc_keyholder_div_open(sc_ctx* ctx, int paillier_key, const uint32_t* z_enc_dptr, const uint64_t* d_dptr, uint32_t* zq_out_dptr,
+                          uint64_t* zm_out_dptr, uint64_t count);
+
 /* ---- device-side CSPRNG: the random draws of a batch, generated where they are consumed ---------------- */
 /* The reference draws from Python's `secrets` (SC/initiator.py:223 permutation, :250 r, :420 delta_A, :512 rho_i) and the
  * scheme packages draw the randomizers behind every .randomize() ([ext]).  A batch of 65536 comparisons needs ~0.3 GB of such

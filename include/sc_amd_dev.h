@@ -243,6 +243,16 @@ int sc_plain_alice(sc_ctx* ctx, const uint32_t* r_dptr, const uint32_t* n_hptr, 
 int sc_plain_bob(sc_ctx* ctx, const uint32_t* z_dptr, const uint32_t* n_hptr, int nw, int l, uint64_t count,
                  uint64_t* beta_dptr, uint64_t* dbit_dptr, uint32_t* zeta1_dptr, uint32_t* zeta2_dptr);
 
+/* ---- secure division: the plaintext-word long division of both players ------------------------------------------- */
+/* q [count][nw] = x div d and rem [count] = x mod d, row by row, for x [count][nw] (nw >= 1 words) and d [count] uint64 divisors, all
+ * device arrays (k_divmod_words: Knuth's algorithm D, one thread per row).  q may be x itself -- the division then runs in place -- or
+ * an array apart from x; a q that partly overlaps x, a rem that overlaps x, q or d, a d that overlaps q, a null pointer and nw < 1 are
+ * SC_ERR_ARG before anything is launched.  A row whose divisor is ZERO is an error the call cannot see when it queues the launch: the
+ * kernel writes that row's q and rem as zero, divides nothing and sets a flag word of the context, and the next sc_ctx_synchronize of
+ * the context returns SC_ERR_ARG once (and clears the flag).  Never a device fault. */
+int sc_plain_divmod(sc_ctx* ctx, const uint32_t* x_dptr, int nw, const uint64_t* d_dptr, uint64_t count, uint32_t* q_dptr,
+                    uint64_t* rem_dptr);
+
 /* ---- secure selection ("Secure selection"): the plaintext-word halves of the two players -------------- */
 /* Layout of the packed plaintext of P = [[delta]] prod_j [[d_j]]^(2^off_j) (1 + R N) rho^N, low bits first: a = delta + r_a in
  * [0, s), s = kappa + 1, then field j = d_j + r_b_j (d_j < 2^(widths[j] + 1)) of widths[j] + kappa + 2 bits; nfields <= 4,

@@ -22,6 +22,7 @@ SYMBOLS = [
     "sc_topk_network", "sc_dot_layout", "sc_initiator_dot_pack", "sc_keyholder_dot", "sc_initiator_dot_finish",
     "sc_onehot_prep", "sc_onehot_split", "sc_onehot_rotate", "sc_onehot_layout", "sc_initiator_onehot_pack", "sc_keyholder_onehot",
     "sc_initiator_onehot_finish",
+    "sc_plain_divmod", "sc_div_fits", "sc_initiator_div_blind", "sc_keyholder_div_open",
     "sc_rng_seed", "sc_rng_bits", "sc_rng_below", "sc_rng_coins", "sc_rng_permutations",
     "sc_peak_probe", "sc_mac_counter", "sc_table_traffic_probe", "sc_ctx_set_latency_mode", "sc_ctx_set_onelane_mode", "sc_ctx_set_chip_share", "sc_ctx_set_fork_mode", "sc_ctx_set_pair_policy", "sc_ctx_stats", "sc_ctx_launch_counts", "sc_ctx_policy", "sc_clock_probe", "sc_comm_unique_id", "sc_comm_init", "sc_allgather", "sc_comm_destroy",
 ]
@@ -142,6 +143,10 @@ def load() -> C.CDLL:
         "sc_initiator_onehot_pack": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, u64]),
         "sc_keyholder_onehot": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
         "sc_initiator_onehot_finish": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, u64]),
+        "sc_plain_divmod": (i32, [vp, vp, i32, vp, u64, vp, vp]),
+        "sc_div_fits": (i32, [i32, i32, i32, i32]),
+        "sc_initiator_div_blind": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, u64]),
+        "sc_keyholder_div_open": (i32, [vp, i32, vp, vp, vp, vp, u64]),
         "sc_rng_seed": (i32, [vp, vp]),
         "sc_rng_bits": (i32, [vp, i32, vp, u64]),
         "sc_rng_below": (i32, [vp, vp, i32, i32, vp, u64]),

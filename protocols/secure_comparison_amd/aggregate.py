@@ -323,6 +323,23 @@ def secure_groupby_sum_batch(value_enc: torch.Tensor, index_enc: torch.Tensor, k
     return sum_rows_batch(products.reshape(k, B, w), alice_paillier, rho=rho)
 
 
+def secure_groupby_mean_batch(value_enc: torch.Tensor, index_enc: torch.Tensor, k: int, bits: int, group_counts, alice_paillier: Paillier,
+                              bob_paillier: Paillier, alice_dgk, bob_dgk, signed: bool = False, index_bits: int | None = None,
+                              kappa: int = 40, draws: OnehotDraws | None = None, mul_draws: MulDraws | None = None,
+                              div_draws=None) -> torch.Tensor:
+    """[[floor(sum_{b : i_b mod k == t} v_b / n_t)]], t < k -> [k][2nw]: secure_groupby_sum_batch, then one division batch of k rows
+    (division.py) by the PUBLIC group sizes n_t = group_counts[t] >= 1 (a list or CPU int64 tensor of [k]).  The counts are an input: a
+    division by the ENCRYPTED counts of secure_groupby_count_batch is out of scope.  The division is told x_bits = bits + bits(B): an
+    unsigned sum is below 2^x_bits, and a signed one lies in [-2^(x_bits - 1), 2^(x_bits - 1)), inside the division's signed range
+    [-2^x_bits, 2^x_bits), so no further bit is added.  draws / mul_draws / div_draws (division.DivDraws for k rows) inject the three
+    steps' randomness."""
+    from .division import secure_divide_batch
+
+    sums = secure_groupby_sum_batch(value_enc, index_enc, k, bits, alice_paillier, bob_paillier, signed, index_bits, kappa, draws, mul_draws)
+    width = int(bits) + int(index_enc.shape[0]).bit_length()
+    return secure_divide_batch(sums, group_counts, width, alice_paillier, bob_paillier, alice_dgk, bob_dgk, signed, kappa, div_draws)
+
+
 # ---- the two players over a Communicator (Initiator / KeyHolder.perform_secure_{histogram,majority,groupby_sum,cdf,quantile}_batch) -----
 # Sequences of the existing sessions -- one-hot, multiplication, the argmax's rounds -- with Alice's local sums in between: no message
 # id of their own and none changed.

@@ -5,7 +5,7 @@ families, schemes, top-m network; what they share is declared in csrc/sc_host.h,
 csrc/sc_bigint.h), the instances of the two interpreter
 kernels in three parts each (csrc/sc_launch_vm.hip / sc_launch_pvm.hip with -DSC_PART=0/1/2, each part expanding its rows of the
 instance list in csrc/sc_route.h and exporting one look-up of them) and the remaining kernels
-(csrc/sc_launch_misc.hip with csrc/sc_kernel_plain.h; each of these defined in the unit that launches it, over the bit-field helpers of csrc/sc_plain_words.h: the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip, the running product in csrc/sc_launch_scan.hip, the linear map with public weights in csrc/sc_launch_lin.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
+(csrc/sc_launch_misc.hip with csrc/sc_kernel_plain.h and, from the subdirectory csrc/div/, the division's k_divmod_words; each of these defined in the unit that launches it, over the bit-field helpers of csrc/sc_plain_words.h: the secure multiplication's two in csrc/sc_launch_mul.hip, the inner product's two in csrc/sc_launch_dot.hip, the one-hot encoding's three in csrc/sc_launch_lookup.hip, the product along an axis in csrc/sc_launch_reduce.hip, the running product in csrc/sc_launch_scan.hip, the linear map with public weights in csrc/sc_launch_lin.hip).  The parts compile in parallel; an object is rebuilt only when one of the files it includes changed,
 so a change of host logic costs the seconds of the host units it touches and a kernel change only the parts that hold that kernel.
 """
 from __future__ import annotations
@@ -37,7 +37,9 @@ LINEAR_UNITS = [("sc_launch_lin", "sc_launch_lin.hip", [])]
 # The host units beside sc_lib.hip; each begins with its own includes and compiles on its own.
 HOST_UNITS = [(n, n + ".hip", []) for n in ("sc_families", "sc_schemes", "sc_topk")]
 ALL_UNITS = UNITS + LINEAR_UNITS + HOST_UNITS
-DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
+# every source under csrc/, its subdirectories included (csrc/div/ holds k_divmod_words, which sc_launch_misc.hip includes; _closure
+# follows an include into a subdirectory as it follows any other)
+DEPS = sorted(os.path.join(d, f) for d, _, fs in os.walk(CSRC) for f in fs if f.endswith((".hip", ".h"))) + [
     os.path.join(INCLUDE, "sc_amd.h"), os.path.join(INCLUDE, "sc_amd_dev.h")]
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 

@@ -431,5 +431,8 @@ int onehot_rotate(sc_ctx* ctx, const char* who, int words, int k, int m, const u
 // sc_schemes.hip: the key tables of a context (sc_ctx::scheme_keys), whose types stay in that unit
 // ================================================================================================
 void free_scheme_keys(void* p);
+// The zero-divisor verdict of sc_plain_divmod: SC_OK, or SC_ERR_ARG once (the verdict is cleared) when a division queued on this context
+// met a divisor of zero.  The caller has synchronised the context's stream (sc_ctx_synchronize asks after it has).
+int div_verdict_check(sc_ctx* ctx);
 
 }  // namespace sc_host

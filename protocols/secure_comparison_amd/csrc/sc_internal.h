@@ -226,4 +226,6 @@ int launch_rng_below(hipStream_t stream, const sc::RngKey& key, uint64_t call, c
 int launch_rng_coins(hipStream_t stream, const sc::RngKey& key, uint64_t call, uint64_t* out, uint64_t count);
 int launch_rng_perm(hipStream_t stream, const sc::RngKey& key, uint64_t call, int k, int64_t* out, uint64_t count);
 int launch_peak_probe(hipStream_t stream, int grid, uint32_t* out, uint32_t a0, uint32_t b0, int iters);
+// div/sc_kernel_divmod.h, compiled by sc_launch_misc.hip: q [count][nw] = x div d, rem = x mod d per row (k_divmod_words); q may be x
+int launch_divmod_words(hipStream_t stream, const uint32_t* x, int nw, const uint64_t* d, uint64_t count, uint32_t* q, uint64_t* rem, uint32_t* bad);
 }  // namespace sc_host

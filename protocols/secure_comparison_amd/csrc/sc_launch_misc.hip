@@ -4,6 +4,7 @@
 #include "sc_kernel_plain.h"
 #include "sc_rng.h"
 #include "sc_xgcd.h"
+#include "div/sc_kernel_divmod.h"   // k_divmod_words and its launcher (why it stands in a subdirectory)
 
 using namespace sc;
 

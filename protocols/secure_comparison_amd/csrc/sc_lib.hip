@@ -293,7 +293,8 @@ int sc_ctx_set_stream(sc_ctx* ctx, void* hip_stream) {
   ctx->stream = s;
   return SC_OK;
 }
-int sc_ctx_synchronize(sc_ctx* ctx) { if (!ctx) return SC_ERR_ARG; HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return SC_OK; }
+// (a division by zero met by an earlier sc_plain_divmod of this context is reported here: include/sc_amd_dev.h)
+int sc_ctx_synchronize(sc_ctx* ctx) { if (!ctx) return SC_ERR_ARG; HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return div_verdict_check(ctx); }
 const char* sc_last_error(sc_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 int64_t sc_last_bad_index(sc_ctx* ctx) { return ctx ? ctx->last_bad_index : -1; }
 

@@ -49,7 +49,8 @@ struct sc_scheme_keys {
   std::vector<PaillierKey> paillier; std::vector<DgkKey> dgk;
   std::map<int, int> pow2_exps;      // bits -> the registered exponent 2^bits (the selection's Horner chain)
   uint32_t* select_verdict = nullptr; // pinned word the key holder's split kernel writes (sc_keyholder_select_mult)
-  ~sc_scheme_keys() { if (select_verdict) (void)hipHostFree(select_verdict); }
+  uint32_t* div_verdict = nullptr;    // pinned word k_divmod_words sets on a zero divisor (sc_plain_divmod); zero whenever nothing is pending
+  ~sc_scheme_keys() { if (select_verdict) (void)hipHostFree(select_verdict); if (div_verdict) (void)hipHostFree(div_verdict); }
 };
 
 void sc_host::free_scheme_keys(void* p) { delete (sc_scheme_keys*)p; }
@@ -1238,6 +1239,80 @@ int sc_initiator_onehot_finish(sc_ctx* ctx, int paillier_key_id, int kappa, int 
   return onehot_rotate(ctx, "sc_initiator_onehot_finish", 2 * kp->nw, kk, m, e_enc, rot, out, count);
 }
 
+// ---- secure division by public divisors ------------------------------------------------------------------------------
+// one pinned, device-visible word per context for k_divmod_words' zero-divisor verdict (the selection's verdict word's twin)
+static int div_verdict_word(sc_ctx* ctx, uint32_t** out) {
+  auto* ks = keys_of(ctx);
+  if (!ks->div_verdict) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipHostMalloc((void**)&ks->div_verdict, sizeof(uint32_t), hipHostMallocMapped));
+    *(volatile uint32_t*)ks->div_verdict = 0;
+  }
+  *out = ks->div_verdict;
+  return SC_OK;
+}
+static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int sc_plain_divmod(sc_ctx* ctx, const uint32_t* x, int nw, const uint64_t* d, uint64_t count, uint32_t* q, uint64_t* rem) {
+  if (!ctx) return SC_ERR_ARG;
+  if (!x || !d || !q || !rem) return fail(ctx, SC_ERR_ARG, "sc_plain_divmod: null pointer");
+  if (nw < 1) return fail(ctx, SC_ERR_ARG, "sc_plain_divmod: nw = %d: expected at least one word per row", nw);
+  if (count == 0) return SC_OK;
+  const size_t rows = (size_t)count * nw * 4, words = (size_t)count * 8;
+  if (q != x && bytes_overlap(q, rows, x, rows))
+    return fail(ctx, SC_ERR_ARG, "sc_plain_divmod: q partly overlaps x (q is x itself, in place, or an array apart from it)");
+  if (bytes_overlap(rem, words, x, rows) || bytes_overlap(rem, words, q, rows) || bytes_overlap(d, words, q, rows) || bytes_overlap(d, words, rem, words))
+    return fail(ctx, SC_ERR_ARG, "sc_plain_divmod: rem overlaps x, q or d, or d overlaps q");
+  uint32_t* bad;
+  int rc = div_verdict_word(ctx, &bad); if (rc) return rc;
+  if (launch_divmod_words(ctx->stream, x, nw, d, count, q, rem, bad)) return fail(ctx, SC_ERR_HIP, "sc_plain_divmod: launch failed");
+  return SC_OK;
+}
+
+int sc_div_fits(int nbits_n, int kappa, int x_bits, int is_signed) {
+  if (kappa < 1 || kappa > 62 || x_bits < 1) return 0;
+  // signed: the dividend is x + c d with c = ceil(2^x_bits / d), below 2^(x_bits + 2) where d <= 2^x_bits and below 2 d < 2^65 elsewhere
+  const long long width = is_signed ? std::max<long long>((long long)x_bits + 2, 65) : x_bits;
+  return width + kappa + 2 < (long long)nbits_n - 1 ? 1 : 0;
+}
+
+int sc_initiator_div_blind(sc_ctx* ctx, int paillier_key_id, int kappa, int x_bits, int is_signed, const uint32_t* x_enc, const uint32_t* r,
+                           const uint32_t* rho, int flags, const uint64_t* d, uint32_t* z_out, uint32_t* rq, uint64_t* rm, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !x_enc || !r || !rho || !d || !z_out || !rq || !rm) return fail(ctx, SC_ERR_ARG, "sc_initiator_div_blind: bad argument");
+  const PaillierKey k = *kp;
+  if (!sc_div_fits(big_bits(k.n), kappa, x_bits, is_signed))
+    return fail(ctx, SC_ERR_ARG, "sc_initiator_div_blind: x_bits = %d (%s), kappa = %d: the blinded dividend does not fit below a %d-bit N", x_bits,
+                is_signed ? "signed" : "unsigned", kappa, big_bits(k.n));
+  const int w2 = 2 * k.nw;
+  const Prog* p;                                                          // the packing program of the four families: [[x + r]]
+  int rc = cached_prog(ctx, "selpk:" + std::to_string(k.mod_n2) + ":" + std::to_string(k.cst_n), k.mod_n2, [&](Builder& bd) {
+    const int cn = bd.use_const(k.cst_n);
+    bd.loadw(1, 0, 0, k.nw); bd.mul_const(cn); bd.add1();                 // [[r]] = 1 + r N
+    bd.mul_const(0); bd.mul_extw(0);                                      // [[x + r]]
+    bd.storew(2);
+  }, &p); if (rc) return rc;
+  VmExt ex[3] = {mk_ext(x_enc, w2, w2), mk_ext(r, k.nw, k.nw), mk_ext(z_out, w2, w2)};
+  rc = run_vm(ctx, k.mod_n2, *p, ex, 3, count); if (rc) return rc;
+  if (flags & SC_STEP_RANDOMIZERS_READY) rc = sc_modmul(ctx, k.mod_n2, z_out, w2, rho, w2, z_out, count);
+  else rc = sc_paillier_randomize(ctx, paillier_key_id, z_out, rho, z_out, count);
+  if (rc) return rc;
+  return sc_plain_divmod(ctx, r, k.nw, d, count, rq, rm);
+}
+
+int sc_keyholder_div_open(sc_ctx* ctx, int paillier_key_id, const uint32_t* z_enc, const uint64_t* d, uint32_t* zq, uint64_t* zm, uint64_t count) {
+  if (ctx && count == 0) return SC_OK;
+  const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
+  if (!kp || !z_enc || !d || !zq || !zm) return fail(ctx, SC_ERR_ARG, "sc_keyholder_div_open: bad argument");
+  const int nw = kp->nw;
+  int rc = sc_paillier_decrypt(ctx, paillier_key_id, z_enc, zq, count); if (rc) return rc;      // z, divided where it stands
+  return sc_plain_divmod(ctx, zq, nw, d, count, zq, zm);
+}
+
 int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64_t count, double* out_ghz, double* out_ms) {
   const PaillierKey* kp = paillier_key(ctx, paillier_key_id);
   if (!kp || !rho || count == 0 || !out_ghz) return fail(ctx, SC_ERR_ARG, "sc_clock_probe: bad argument");
@@ -1276,3 +1351,10 @@ int sc_clock_probe(sc_ctx* ctx, int paillier_key_id, const uint32_t* rho, uint64
 }
 
 }  // extern "C"
+
+int sc_host::div_verdict_check(sc_ctx* ctx) {
+  auto* ks = (sc_scheme_keys*)ctx->scheme_keys;
+  if (!ks || !ks->div_verdict || !*(volatile uint32_t*)ks->div_verdict) return SC_OK;
+  *(volatile uint32_t*)ks->div_verdict = 0;
+  return fail(ctx, SC_ERR_ARG, "sc_plain_divmod: a divisor is zero (the row's quotient and remainder were written as zero)");
+}

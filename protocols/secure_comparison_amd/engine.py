@@ -660,6 +660,63 @@ class Engine:
                                           self._ptr(zeta1), self._ptr(zeta2)))
         return beta, dbit, zeta1, zeta2
 
+    # ------------------------------------------------------------------ secure division (division.py)
+    def _divisors(self, d: torch.Tensor, count: int) -> torch.Tensor:
+        self._arr(d, "divisor", dtype=torch.int64)
+        if tuple(d.shape) != (count,):
+            raise ValueError(f"divisor: shape {tuple(d.shape)}, expected [{count}] (uint64 divisors as int64)")
+        return d
+
+    def plain_divmod(self, x: torch.Tensor, d: torch.Tensor, in_place: bool = False):
+        """(x div d [count][nw], x mod d [count] u64 as int64) for x [count][nw] and d [count] u64 (sc_plain_divmod, k_divmod_words).
+        in_place: the quotient overwrites x.  A zero divisor is reported by the next `ctx_synchronize()`, not here."""
+        self._arr(x, "x")
+        if x.dim() != 2 or x.shape[1] < 1:
+            raise ValueError("x: expected [count][nwords]")
+        count, nw = x.shape
+        self._divisors(d, count)
+        q = x if in_place else self.empty(count, nw)
+        rem = torch.empty((count,), dtype=torch.int64, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_plain_divmod(self.ctx, self._ptr(x), nw, self._ptr(d), count, self._ptr(q), self._ptr(rem)))
+        return q, rem
+
+    def ctx_synchronize(self) -> None:
+        """Waits for the context's stream (sc_ctx_synchronize) and raises what the context reports lazily: a division by zero."""
+        self._sync_stream()
+        self._check(self.lib.sc_ctx_synchronize(self.ctx))
+
+    def div_fits(self, nbits: int, kappa: int, x_bits: int, signed: bool) -> bool:
+        """The library's copy of division.div_fits (sc_div_fits)."""
+        clip = lambda v: max(-1, min(int(v), 2 ** 31 - 1))                                          # noqa: E731
+        return bool(self.lib.sc_div_fits(clip(nbits), clip(kappa), clip(x_bits), int(bool(signed))))
+
+    def initiator_div_blind(self, key: PaillierKey, kappa: int, x_bits: int, signed: bool, x_enc: torch.Tensor, r: torch.Tensor,
+                            rho: torch.Tensor, d: torch.Tensor, ready: bool = False, out: torch.Tensor | None = None):
+        """([[z]] = [[x + r]] rho^N [B][2nw], r div d [B][nw], r mod d [B] u64): sc_initiator_div_blind.  r: [B][nw]; rho: [B][nw], or with
+        `ready` the finished randomizers [B][2nw]."""
+        count, nw = self._items(x_enc), key.mod_n.nwords
+        self._arr(x_enc, "x_enc", count, 2 * nw)
+        self._arr(r, "r", count, nw)
+        self._arr(rho, "rho", count, 2 * nw if ready else nw)
+        self._divisors(d, count)
+        z = self._result(out, (count, 2 * nw), "z_out")
+        rq, rm = self.empty(count, nw), torch.empty((count,), dtype=torch.int64, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_initiator_div_blind(self.ctx, key.id, int(kappa), int(x_bits), int(bool(signed)), self._ptr(x_enc), self._ptr(r),
+                                                    self._ptr(rho), int(ready), self._ptr(d), self._ptr(z), self._ptr(rq), self._ptr(rm), count))
+        return z, rq, rm
+
+    def keyholder_div_open(self, key: PaillierKey, z_enc: torch.Tensor, d: torch.Tensor):
+        """(z div d [B][nw], z mod d [B] u64) for z = Dec([[z]]): sc_keyholder_div_open."""
+        count, nw = self._items(z_enc), key.mod_n.nwords
+        self._arr(z_enc, "z_enc", count, 2 * nw)
+        self._divisors(d, count)
+        zq, zm = self.empty(count, nw), torch.empty((count,), dtype=torch.int64, device=self.device)
+        self._sync_stream()
+        self._check(self.lib.sc_keyholder_div_open(self.ctx, key.id, self._ptr(z_enc), self._ptr(d), self._ptr(zq), self._ptr(zm), count))
+        return zq, zm
+
     def dgk_step4(self, mod: Modulus, g: int, g_inv: int, l: int, beta: torch.Tensor, beta_inv: torch.Tensor,
                   d: torch.Tensor, d_inv: torch.Tensor, alpha: torch.Tensor, alpha_tilde: torch.Tensor,
                   rsmall: torch.Tensor, delta_a: torch.Tensor) -> torch.Tensor:

@@ -18,14 +18,14 @@ def no_chunks(chunks) -> None:
 
 
 async def announce(ini, name: str, tag: str, layout_header: list[int], P: torch.Tensor, reply_shape: tuple[int, ...],
-                   reply_what: str) -> torch.Tensor:
+                   reply_what: str, reply_words: int | None = None) -> torch.Tensor:
     """The initiator's half: the header and P out, the key holder's answer back as [*reply_shape][2nw] (`reply_what` names it in a
-    refusal)."""
+    refusal).  reply_words: the answer's row width where it is not a Paillier ciphertext's (the division's DGK bits)."""
     comm, dev = ini.communicator, P.device
     head = torch.tensor(layout_header, dtype=torch.int32, device=dev)
     await comm.send(ini.other_party, wire.outgoing(comm, head, P), msg_id=f"{name}_1_batch_{tag}")
     (reply,) = wire.incoming(await comm.recv(ini.other_party, msg_id=f"{name}_2_batch_{tag}"), dev, expect=1)
-    return wire.expect_array(reply, (*reply_shape, ini.scheme_paillier.mod_n2.nwords), reply_what)
+    return wire.expect_array(reply, (*reply_shape, ini.scheme_paillier.mod_n2.nwords if reply_words is None else reply_words), reply_what)
 
 
 async def receive_announced(kh, name: str, tag: str, header: list[int], fields: str, lengths: range, lead: tuple[int, ...],

@@ -463,6 +463,23 @@ class Initiator:
 
         return await alice_equal(self, x_enc, y_enc, draws, mul_draws, kappa, source, engine, generator, chunks)
 
+    # ---- secure division by public divisors (division.py)
+    async def perform_secure_divide_batch(self, x_enc: torch.Tensor, divisor, x_bits: int, signed: bool = False, kappa: int = 40, draws=None,
+                                          source: str = "device", engine=None, generator=None, chunks: int = 1) -> torch.Tensor:
+        """[[x // d]] as division.secure_divide_batch, over the announced exchange `div` (header kappa, x_bits, signed, l, rows and a digest
+        of the divisors; P = [[z]]; answer [d], [beta_i]) and the sub-comparison's second round trip `div_3` / `div_4`."""
+        from .division import alice_divide
+
+        return await alice_divide(self, x_enc, divisor, x_bits, signed, kappa, draws, source, engine, generator, chunks, "div")
+
+    async def perform_secure_modulo_batch(self, x_enc: torch.Tensor, divisor, x_bits: int, signed: bool = False, kappa: int = 40, draws=None,
+                                          source: str = "device", engine=None, generator=None, chunks: int = 1, with_quotient: bool = False):
+        """[[x % d]] (with_quotient: ([[x // d]], [[x % d]])): the messages of perform_secure_divide_batch, then Alice's local finish."""
+        from .division import alice_divide
+
+        return await alice_divide(self, x_enc, divisor, x_bits, signed, kappa, draws, source, engine, generator, chunks,
+                                  "divmod" if with_quotient else "mod")
+
     # ---- secure inner product (dotproduct.py)
     async def perform_secure_dot_batch(self, x_enc: torch.Tensor, y_enc: torch.Tensor | None, x_bits: int, y_bits: int = 0,
                                        signed: bool = False, square: bool = False, kappa: int = 40, draws=None, source: str = "device",

@@ -334,6 +334,20 @@ class KeyHolder:
 
         await bob_equal(self, draws, mul_draws, kappa, source, generator)
 
+    # ---- secure division by public divisors (division.py)
+    async def perform_secure_divide_batch(self, count: int, divisor, x_bits: int, signed: bool = False, kappa: int = 40, draws=None,
+                                          source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_divide_batch for `count` rows: the initiator's header must announce this kappa, x_bits,
+        signedness and these divisors (ValueError before anything is decrypted)."""
+        from .division import bob_divide
+
+        await bob_divide(self, count, divisor, x_bits, signed, kappa, draws, source, generator)
+
+    async def perform_secure_modulo_batch(self, count: int, divisor, x_bits: int, signed: bool = False, kappa: int = 40, draws=None,
+                                          source: str = "device", generator=None) -> None:
+        """Bob's side of Initiator.perform_secure_modulo_batch: the division's messages (the modulo's finish is Alice's alone)."""
+        await self.perform_secure_divide_batch(count, divisor, x_bits, signed, kappa, draws, source, generator)
+
     # ---- secure inner product (dotproduct.py)
     async def perform_secure_dot_batch(self, k: int, x_bits: int, y_bits: int = 0, signed: bool = False, square: bool = False,
                                        kappa: int = 40, draws=None, source: str = "device", generator=None,
